@@ -292,6 +292,39 @@ class DictInputs:
 
 PEAK_BF16_MFMA_TFLOPS = 2500.0       # MI355X_MICROARCH.md: dense bf16 MFMA peak; a bf16-split fp32 product costs six of them
 
+DUMP_SEED = 20240601                 # fixed: the sampled elements of a large dumped array are the same in every run and every build
+DUMP_OUTPUT_CAP = 4 << 20            # elements kept per output tensor (16 MB of float32; bs <= 10 keeps the whole mask)
+DUMP_STATE_CAP = 1 << 20             # elements kept of the parameters / gradients / running statistics (4 MB each)
+
+
+def _dump_sample(x, cap):
+    """x (a device tensor) -> float32 numpy: all of it when it holds <= cap elements, else `cap` elements at sorted positions drawn once
+    from DUMP_SEED (flattened order), so that two runs of the same arguments sample the same positions."""
+    flat = x.detach().reshape(-1).float()
+    if flat.numel() > cap:
+        idx = np.sort(np.random.default_rng(DUMP_SEED).choice(flat.numel(), cap, replace=False))
+        flat = flat[torch.from_numpy(idx).to(flat.device)]
+        return flat.cpu().numpy()
+    return flat.cpu().numpy().reshape(tuple(x.shape))
+
+
+def dump_outputs(eng, losses, d):
+    """--dump-outputs DIR: what the headline leg's LAST timed step computed, as a caller of the step receives it -- the labeled / flipped
+    pass's output masks and the predicted actions (shuffled order, StepEngine.outputs), the loss scalars (float64), and the state the step
+    left behind (parameters after Adam, their gradients, the BN running statistics; seeded samples).  At most ~45 MB in all."""
+    eng.synchronize()
+    out, flip, pred = eng.outputs()
+    arrays = {"output": _dump_sample(out, DUMP_OUTPUT_CAP), "flip_output": _dump_sample(flip, DUMP_OUTPUT_CAP),
+              "predicted_action": _dump_sample(pred, DUMP_OUTPUT_CAP),
+              "params_sample": _dump_sample(eng.P, DUMP_STATE_CAP), "grads_sample": _dump_sample(eng.G, DUMP_STATE_CAP),
+              "running_stats_sample": _dump_sample(eng.R, DUMP_STATE_CAP)}
+    for k, v in losses.items():
+        arrays["loss_" + k] = np.asarray(v, dtype=np.float64)
+    os.makedirs(d, exist_ok=True)
+    for name, v in arrays.items():
+        np.save(os.path.join(d, name + ".npy"), v)
+    return sorted(arrays)
+
 
 def main():
     ap = argparse.ArgumentParser()
@@ -314,7 +347,11 @@ def main():
     ap.add_argument("--dry-launch", action="store_true", help="ranks only rendezvous + all-reduce ones (launcher test; no GPU work)")
     ap.add_argument("--dry-backend", default="auto", choices=["auto", "gloo", "nccl"])
     ap.add_argument("--launch-timeout", type=float, default=0.0, help="seconds after which the launcher stops its ranks (0 = never)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="after the timed steps, write what the last timed step computed "
+                    "(output masks, predicted actions, losses, sampled parameters / gradients / running statistics) to DIR/<name>.npy (rank 0)")
     a = ap.parse_args()
+    if a.steps < 1 or a.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
 
     if a.gpus > 1 and "RANK" not in os.environ:
         # the launcher: nothing above or below in this branch touches the GPU (importing torch does not)
@@ -425,6 +462,9 @@ def main():
         torch.cuda.synchronize()
         reducer_stats = reducer.stats()
     ms_step = ms_total / a.steps
+    dumped = None
+    if a.dump_outputs and rank == 0:                     # outside every timed region, before any later leg overwrites the step's results
+        dumped = dump_outputs(eng, last, a.dump_outputs)
     value = world * a.bs * a.steps / (ms_total / 1e3)
     main_ms, main_count = eng.kind_ms, eng.kind_count
 
@@ -653,6 +693,7 @@ def main():
         "roofline_step": roof_step,
         "ranks_observed": ranks_observed,
         "busy_steps_outside_timed_regions": busy_steps,
+        "dumped_outputs": None if dumped is None else {"dir": os.path.abspath(a.dump_outputs), "arrays": dumped},
         "reducer": None if reducer is None else dict(reducer_stats, buckets=len(reducer.buckets), backend=torch.distributed.get_backend(),
                                                      forced_single_rank=forced, bucket_table=reducer.bucket_table()),
     }

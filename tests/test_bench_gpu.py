@@ -107,3 +107,26 @@ def test_bench_dp_schedule_through_rccl_on_one_rank():
     tab = rd["bucket_table"]
     assert len(tab) == rd["buckets"] and all(t["bytes"] > 0 and t["ready_op"] > 0 for t in tab)
     assert [t["ready_op"] for t in tab] == sorted(t["ready_op"] for t in tab) and sum(t["bytes"] for t in tab) > 150e6
+
+
+def test_bench_dump_outputs(tmp_path):
+    """--dump-outputs DIR: the last timed step's outputs as float32 / float64 .npy files (<= 64 MB in all), the losses equal to the line's,
+    and two runs with the same arguments (hence the same inputs) computing the same step."""
+    import numpy as np
+    flags = ("--gpus", "1", "--steps", "3", "--warmup", "1", "--no-cpu-baseline", "--no-extra-legs", "--no-kernel-timing")
+    runs = []
+    for tag in ("a", "b"):
+        d = tmp_path / tag
+        j = _run(*flags, "--dump-outputs", str(d))
+        assert j["steps"] == 3 and j["ms_per_step"] > 0 and sorted(j["dumped_outputs"]["arrays"]) == sorted(f[:-4] for f in os.listdir(str(d)))
+        arrs = {f[:-4]: np.load(str(d / f)) for f in os.listdir(str(d))}
+        assert sum(v.nbytes for v in arrs.values()) <= 64 << 20
+        assert all(v.dtype in (np.float32, np.float64) and np.isfinite(v).all() for v in arrs.values())
+        assert arrs["output"].shape == (8, 1, 8, 224, 224) and arrs["flip_output"].shape == (8, 1, 8, 224, 224)
+        assert arrs["predicted_action"].shape == (8, 24) and arrs["params_sample"].size == 1 << 20
+        assert all(float(arrs["loss_" + k]) == j["loss"][k] for k in j["loss"])
+        runs.append(arrs)
+    a, b = runs
+    assert sorted(a) == sorted(b)
+    for k in a:
+        np.testing.assert_allclose(a[k], b[k], rtol=1e-4, atol=1e-5, err_msg=k)

@@ -12,6 +12,7 @@ import pytest
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+RECORDS = os.path.join(ROOT, "test_records")      # side records of the checks (git-ignored)
 
 
 def _free_port():
@@ -43,13 +44,13 @@ def test_two_rank_dp_step_on_one_gpu(tmp_path, full):
                 q.kill()
             raise
         logs.append(o)
-    os.makedirs(os.path.join(ROOT, "gpurun_out"), exist_ok=True)
+    os.makedirs(RECORDS, exist_ok=True)
     verdicts = []
     for rank in range(2):
         path = "%s.%d" % (out, rank)
         assert os.path.exists(path), "rank %d wrote no verdict:\n%s" % (rank, logs[rank][-3000:])
         verdicts.append(json.load(open(path)))
-    with open(os.path.join(ROOT, "gpurun_out", "dp_two_rank_checks%s.json" % ("_full" if full else "")), "w") as f:
+    with open(os.path.join(RECORDS, "dp_two_rank_checks%s.json" % ("_full" if full else "")), "w") as f:
         json.dump(verdicts, f, indent=1)
     for rank, v in enumerate(verdicts):
         failed = {k: c for k, c in v["checks"].items() if not c["ok"]}
@@ -101,7 +102,8 @@ def test_rccl_one_rank_group_runs_the_dp_schedule(tmp_path):
                        stderr=subprocess.STDOUT, text=True, timeout=600)
     assert p.returncode == 0 and os.path.exists(out), p.stdout[-3000:]
     v = json.load(open(out))
-    with open(os.path.join(ROOT, "gpurun_out", "rccl_one_rank.json"), "w") as f:
+    os.makedirs(RECORDS, exist_ok=True)
+    with open(os.path.join(RECORDS, "rccl_one_rank.json"), "w") as f:
         json.dump(v, f)
     assert v["buckets"] >= 3 and v["launched"] == v["buckets"], v
     assert v["rel"] < 2e-4 and v["ones"] == [1.0] * 4 and v["gscale"] == 1.0, v
@@ -152,7 +154,8 @@ def test_early_adam_under_the_reducer_matches_the_late_adam(tmp_path):
                        text=True, timeout=600)
     assert p.returncode == 0 and os.path.exists(out), p.stdout[-3000:]
     v = json.load(open(out))
-    with open(os.path.join(ROOT, "gpurun_out", "early_adam_dp.json"), "w") as f:
+    os.makedirs(RECORDS, exist_ok=True)
+    with open(os.path.join(RECORDS, "early_adam_dp.json"), "w") as f:
         json.dump(v, f)
     e, l = v["early"], v["late"]
     # the early op took everything behind the bucket that leaves last (the head of the flat buffer: the trunk's first layers) ...

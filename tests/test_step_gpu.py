@@ -13,6 +13,8 @@ import torch
 from oracle import step as ostep
 from picons_amd import capi, spec, step as pstep, synthetic
 
+OUT = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "test_records")     # side records of the checks (git-ignored)
+
 pytestmark = pytest.mark.gpu
 
 
@@ -52,8 +54,8 @@ def check_gradients_fp64_anchored(eng, P, P64, tag, floor=5e-3):
         if rel_g > max(4 * rel_c, floor) and (g - r64).abs().max().item() > 1e-7:
             bad.append((name, rel_g, rel_c, den))
     tot_g, tot_c = (num_g / den_all) ** 0.5, (num_c / den_all) ** 0.5
-    os.makedirs("gpurun_out", exist_ok=True)
-    with open("gpurun_out/step_grad_err_%s.txt" % tag, "w") as f:
+    os.makedirs(OUT, exist_ok=True)
+    with open(os.path.join(OUT, "step_grad_err_%s.txt" % tag), "w") as f:
         f.write("whole-gradient rel-L2 vs fp64 oracle: hip %.3e   fp32-oracle %.3e\n" % (tot_g, tot_c))
         for r in sorted(rows, key=lambda r: -r[1])[:40]:
             f.write("%-44s hip %.3e  cpu32 %.3e  |g| %.3e\n" % r)
@@ -153,14 +155,14 @@ def test_step_vs_reference_golden_full_size(golden_dir, tag):
     # gradient norms within 2 % of the fp32 reference's.  The PrimaryCaps activation-capsule parameters are the
     # worst-conditioned in the model (their gradient passes through all of EM routing's sigmoid / log terms): the fp32
     # reference itself is 4.6-5.1 % (rel-L2) from an fp64 run there and this path 4.2-4.4 % (test_step_vs_oracle_small,
-    # gpurun_out/step_grad_err_*.txt); at this size fp64 gives |g| = 1.7307e-5, the reference 1.7111..1.7225e-5 depending
+    # test_records/step_grad_err_*.txt); at this size fp64 gives |g| = 1.7307e-5, the reference 1.7111..1.7225e-5 depending
     # on its thread count, so they get the noise-sized bar
     loose = {"primary_caps.a.weight": 6e-2, "primary_caps.a.bias": 6e-2}
     bad = [(n, float(eng.grad(n).norm()), r) for n, r in gn.items()
            if abs(float(eng.grad(n).norm()) - r) > loose.get(n, 2e-2) * max(r, 1e-6) + 1e-7]
     assert not bad, bad[:10]
     # element-wise against the fp32 reference's own gradients: 2 % of the tensor's max at bs = 2; 5 % at bs = 8, where both this
-    # path and the fp32 reference are 1.2-1.4 % (whole-gradient rel-L2) from an fp64 run (gpurun_out/step_grad_err_*_bs8.txt) --
+    # path and the fp32 reference are 1.2-1.4 % (whole-gradient rel-L2) from an fp64 run (test_records/step_grad_err_*_bs8.txt) --
     # the tight per-tensor bar at that size is the fp64-anchored one of test_step_bs8_full_size_vs_oracle
     #
     # Round 5: the bs = 2 fixtures also hold an fp64 run of the reference (tools/make_goldens.py --only steps_f64; their fp32 contents are
@@ -272,8 +274,8 @@ def test_step_reference_init_vs_reference_fp64(golden_dir):
             lines.append("%-44s grad rel-L2 vs fp64 reference: hip %.3e   fp32 reference %.3e" % (name, r_hip, r_ref))
             if not r_hip <= max(2 * r_ref, 5e-3):
                 fails.append(("tensor", name, r_hip, r_ref))
-    os.makedirs("gpurun_out", exist_ok=True)
-    with open("gpurun_out/step_refinit.txt", "w") as f:
+    os.makedirs(OUT, exist_ok=True)
+    with open(os.path.join(OUT, "step_refinit.txt"), "w") as f:
         f.write("\n".join(lines) + "\n")
         for w in sorted(worst, reverse=True)[:40]:
             f.write("|g| rel. error vs fp64: hip %.3e  fp32 reference %.3e  %s\n" % w)
@@ -574,8 +576,8 @@ def test_training_trajectory_vs_reference(tmp_path, mode):
                        text=True, timeout=900)
     assert p.returncode == 0 and os.path.exists(out), p.stdout[-3000:]
     v = json.load(open(out))
-    os.makedirs(os.path.join(root, "gpurun_out"), exist_ok=True)
-    json.dump(v, open(os.path.join(root, "gpurun_out", "trajectory_%s.json" % mode), "w"), indent=1)
+    os.makedirs(OUT, exist_ok=True)
+    json.dump(v, open(os.path.join(OUT, "trajectory_%s.json" % mode), "w"), indent=1)
     assert v["lanes"] == 4 and v["early_adam_op"] and v["step_count"] == 3
     # Step 1 starts from identical parameters: the loss scalars agree with the reference's fp32 run to 1e-4 (north_star's bar).  From step 2
     # on no two fp32 implementations can: Adam's first updates are +-lr per element whatever the gradient's size, and every fp32 gradient is
@@ -606,7 +608,7 @@ def test_training_trajectory_vs_reference(tmp_path, mode):
     # every parameter tensor's norm: distance from the fp64 run beyond 3x the fp32 reference's own, relative to max(norm, 1).  The tensors at the
     # top are BatchNorm biases of the trunk (norm ~ 1, a few hundred elements, each moved by +-lr = 1e-4 per step): one element whose step-3
     # sign differs moves the norm by up to 1e-4 (measured 7.1e-5; 1.19e-4 with Conv3d_2c's forward in Winograd F(4x4, 3x3), which is one of
-    # the reasons that launch stays in F(2x2, 3x3): gpurun_out/trajectory_*.json, param_norm_excess_top)
+    # the reasons that launch stays in F(2x2, 3x3): test_records/trajectory_*.json, param_norm_excess_top)
     assert v["param_norm_excess"] <= 1e-4, v.get("param_norm_excess_top")
     # Adam's moments after step 3 (round 5): what guards the optimiser's state machine.  Element-wise, the well-conditioned tensors (decoder,
     # capsule head: 2e-6 .. 1e-2 from the fp64 run) pin the early-Adam range to the reference; the trunk's moments are noise from step 2 on in
