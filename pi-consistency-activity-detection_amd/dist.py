@@ -76,6 +76,9 @@ class GradReducer:
         identity) -- how the RCCL path is executed on a one-GPU box (tests/test_dp_gpu.py, bench.py PICONS_FORCE_REDUCER=1)."""
         self.g = flat_grad
         self.buckets = list(buckets)
+        # (target_floats, joined) of Plan.grad_buckets when StepEngine.make_reducer built it: how a step on a plan for another batch size
+        # derives its own ready-after-op indices for the SAME parameter ranges (StepEngine._bucket_ready)
+        self.schedule_args = None
         self.group = group
         self.world = dist.get_world_size(group) if dist.is_initialized() else 1
         self.active = self.world > 1 or (bool(force) and dist.is_initialized())

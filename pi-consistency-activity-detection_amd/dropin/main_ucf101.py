@@ -6,7 +6,12 @@ model, the bv/gv masks and the optimiser step running on MI355X HIP kernels.
 New behaviour is switched by environment variables only, so the CLI is unchanged:
   PICONS_SYNTHETIC=1     synthetic UCF101-24-shaped minibatches (no dataset / decoder libs on the box)
   PICONS_SYNTHETIC=u8    synthetic decoded uint8 videos + box annotations through the device input pipeline (picons_amd.inputpipe)
+  PICONS_SYNTHETIC=0     the caller's datasets from PYTHONPATH (datasets.ucf_dataloader.UCF101DataLoader; for JHMDB
+                         datasets.load_jhmdb_pytorch_multi.JHMDB) in the reference's DataLoaders (real_loaders)
   PICONS_STEPS=<n>       steps per epoch in synthetic mode (default 4)
+  PICONS_LABELED_CLIPS=<n>    synthetic mode: the labeled set has n clips, batched like DataLoader(batch_size=bs // 2, drop_last=False)
+  PICONS_UNLABELED_CLIPS=<n>  the same for the unlabeled set; it sets the steps per epoch (PICONS_STEPS is then not used).  Unset: every
+                         batch is full (bs // 2 clips) and an epoch is PICONS_STEPS steps
   PICONS_FUSED=0         use the nn.Module + autograd path (model called twice, torch.optim.Adam) instead of
                          the fused step engine (default 1: picons_amd.step.StepEngine, both passes batched)
   PICONS_HW=<px>         frame size (default 224, the only size the reference accepts)
@@ -109,17 +114,24 @@ def train_model_interface(args, label_minibatch, unlabel_minibatch, epoch, wt_ra
 
 
 class SyntheticLoader:
-    """Stands in for torch DataLoader(UCF101DataLoader(...)) with the same minibatch dict contract."""
+    """Stands in for torch DataLoader(UCF101DataLoader(...)) with the same minibatch dict contract.  items=None: `steps` batches of n
+    clips; items=k: the batches of DataLoader(batch_size=n, drop_last=False) over k clips (the last one short when n does not divide k)."""
 
-    def __init__(self, n, labeled, steps, rank, num_classes, hw, salt):
+    def __init__(self, n, labeled, steps, rank, num_classes, hw, salt, items=None):
         self.n, self.labeled, self.steps, self.rank, self.nc, self.hw, self.salt = n, labeled, steps, rank, num_classes, hw, salt
+        self.items = items
+
+    def batch_sizes(self):
+        if self.items is None:
+            return [self.n] * self.steps
+        return [min(self.n, self.items - i) for i in range(0, self.items, self.n)]
 
     def __len__(self):
-        return self.steps
+        return len(self.batch_sizes())
 
     def __iter__(self):
-        for i in range(self.steps):
-            mb = synthetic.make_minibatch(self.n, self.labeled, (1234 + self.rank) * 7919 + 2 * i + self.salt, self.nc, self.hw)
+        for i, m in enumerate(self.batch_sizes()):
+            mb = synthetic.make_minibatch(m, self.labeled, (1234 + self.rank) * 7919 + 2 * i + self.salt, self.nc, self.hw)
             yield {k: torch.from_numpy(v) for k, v in mb.items()}
 
 
@@ -130,14 +142,57 @@ class SyntheticVideoLoader(SyntheticLoader):
 
     def __iter__(self):
         from picons_amd import inputpipe
-        for i in range(self.steps):
+        for i, m in enumerate(self.batch_sizes()):
             samples = []
-            for j in range(self.n):
+            for j in range(m):
                 frames, ann = synthetic.make_decoded_video(((1234 + self.rank) * 7919 + 2 * i + self.salt) * 64 + j, self.labeled, self.nc)
                 samples.append(inputpipe.get_item(frames, ann, train=True))
             yield {'data': torch.stack([s['data'] for s in samples]), 'aug_data': torch.stack([s['aug_data'] for s in samples]),
                    'loc_msk': torch.stack([s['loc_msk'] for s in samples]), 'action': torch.stack([s['action'] for s in samples]),
                    'label_vid': torch.tensor([s['label_vid'] for s in samples])}
+
+
+def real_loaders(args, rank=0, world=1):
+    """PICONS_SYNTHETIC=0: the caller's datasets, imported from PYTHONPATH as the reference imports them, in the DataLoaders of
+    main_ucf101.py:345-372 (bs // 2 clips per train batch, shuffled, no drop_last -- so each train loader may end on a short batch --
+    and bs per validation batch).  JHMDB (main_jhmdb.py:338-363) imports datasets.load_jhmdb_pytorch_multi.JHMDB, a module the reference
+    tree does not ship: the caller supplies it, and its absence is an ImportError naming it.  Data parallel (WORLD_SIZE > 1): every rank
+    loads its own contiguous shard of each set (pdist.shard_indices through a Subset, DistributedSampler-style without padding) and
+    shuffles within it."""
+    from torch.utils.data import DataLoader, Subset
+    if DATASET == "jhmdb":
+        try:
+            from datasets.load_jhmdb_pytorch_multi import JHMDB
+        except ImportError as e:
+            raise ImportError("PICONS_SYNTHETIC=0 for JHMDB imports datasets.load_jhmdb_pytorch_multi (class JHMDB, main_jhmdb.py:338) from "
+                              "PYTHONPATH; it is not importable: %s" % e) from e
+        labeled = JHMDB('train', [224, 224], file_id=args.pkl_file_label, use_random_start_frame=False)
+        unlabeled = JHMDB('train', [224, 224], file_id=args.pkl_file_unlabel, use_random_start_frame=False)
+        val = JHMDB('test', [224, 224], file_id='testlist.txt', use_random_start_frame=False)
+    else:
+        from datasets.ucf_dataloader import UCF101DataLoader          # the caller's loader (needs skvideo / the dataset)
+        labeled = UCF101DataLoader('train', [224, 224], file_id=args.pkl_file_label, use_random_start_frame=False)
+        unlabeled = UCF101DataLoader('train', [224, 224], file_id=args.pkl_file_unlabel, use_random_start_frame=False)
+        val = UCF101DataLoader('validation', [224, 224], file_id="test_annots.pkl", use_random_start_frame=False)
+    print(len(labeled), len(unlabeled), len(val))
+    if world > 1:
+        labeled, unlabeled, val = (Subset(d, pdist.shard_indices(len(d), rank, world)) for d in (labeled, unlabeled, val))
+    return (DataLoader(dataset=labeled, batch_size=args.bs // 2, num_workers=args.workers, shuffle=True),
+            DataLoader(dataset=unlabeled, batch_size=args.bs // 2, num_workers=args.workers, shuffle=True),
+            DataLoader(dataset=val, batch_size=args.bs, num_workers=args.workers, shuffle=False))
+
+
+def synthetic_loaders(args, mode, hw, rank=0, world=1):
+    """PICONS_SYNTHETIC=1 / u8: stand-ins for the three loaders.  PICONS_LABELED_CLIPS / PICONS_UNLABELED_CLIPS give the train sets a
+    size (this rank's shard of it), batched as the reference's DataLoaders batch it."""
+    n = args.bs // 2
+    steps = int(os.environ.get("PICONS_STEPS", "4"))
+    clips = lambda key: None if os.environ.get(key) is None else len(pdist.shard_indices(int(os.environ[key]), rank, world))
+    Loader = SyntheticVideoLoader if (mode == "u8" and hw == 224 and DATASET == "ucf101") else SyntheticLoader
+    labeled_loader = Loader(n, True, steps, rank, NUM_CLASSES, hw, 0, items=clips("PICONS_LABELED_CLIPS"))
+    unlabeled_loader = Loader(n, False, steps, rank, NUM_CLASSES, hw, 1, items=clips("PICONS_UNLABELED_CLIPS"))
+    val_loader = SyntheticLoader(args.bs, True, 1, rank, NUM_CLASSES, hw, 5)
+    return labeled_loader, unlabeled_loader, val_loader
 
 
 def train(args, model, labeled_train_loader, unlabeled_train_loader, optimizer, epoch, save_path, writer, ramp_wt, engine=None, reducer=None):
@@ -261,15 +316,17 @@ def run(args):
         random.seed(args.seed); np.random.seed(args.seed); torch.manual_seed(args.seed + rank)
     hw = int(os.environ.get("PICONS_HW", "224"))
     fused = os.environ.get("PICONS_FUSED", "1") != "0"
-    steps = int(os.environ.get("PICONS_STEPS", "4"))
     mode = os.environ.get("PICONS_SYNTHETIC", "1")          # read only: the process environment is not written to
-    if mode not in ("1", "u8"):
-        raise RuntimeError("real UCF101/JHMDB loaders need skvideo/cv2 + the dataset, neither is available here; set PICONS_SYNTHETIC=1 (or u8)")
-    n = args.bs // 2
-    Loader = SyntheticVideoLoader if (mode == "u8" and hw == 224 and DATASET == "ucf101") else SyntheticLoader
-    labeled_loader = Loader(n, True, steps, rank, NUM_CLASSES, hw, 0)
-    unlabeled_loader = Loader(n, False, steps, rank, NUM_CLASSES, hw, 1)
-    val_loader = SyntheticLoader(args.bs, True, 1, rank, NUM_CLASSES, hw, 5)
+    if mode not in ("0", "1", "u8"):
+        raise RuntimeError("PICONS_SYNTHETIC=%r: expected 0 (the caller's datasets), 1 or u8" % mode)
+    if args.bs < 2:
+        raise RuntimeError("--bs %d: each train loader takes bs // 2 clips per batch, so bs must be at least 2" % args.bs)
+    if mode == "0":
+        if hw != 224:
+            raise RuntimeError("PICONS_SYNTHETIC=0: the reference's loaders make 224x224 clips; PICONS_HW=%d is for synthetic data" % hw)
+        labeled_loader, unlabeled_loader, val_loader = real_loaders(args, rank, world)
+    else:
+        labeled_loader, unlabeled_loader, val_loader = synthetic_loaders(args, mode, hw, rank, world)
     print(len(labeled_loader), len(unlabeled_loader), len(val_loader))
 
     # the reference's CapsNet() loads ../weights/rgb_charades.pt and raises without it (capsules_ucf101.py:344).  In synthetic mode a
@@ -277,7 +334,7 @@ def run(args):
     # constructs CapsNet() himself, still gets the hard error for a wrong path
     pt_path = '../weights/rgb_charades.pt'
     if not os.path.exists(pt_path):
-        print("WARNING: %s not found; synthetic mode (PICONS_SYNTHETIC=%s): the I3D trunk keeps its random initialisation" % (pt_path, mode), file=sys.stderr)
+        print("WARNING: %s not found (PICONS_SYNTHETIC=%s): the I3D trunk keeps its random initialisation" % (pt_path, mode), file=sys.stderr)
         pt_path = None
     model = CapsNet(pt_path=pt_path, num_classes=NUM_CLASSES, hw=hw, seed=args.seed) if NUM_CLASSES != 24 or hw != 224 else CapsNet(pt_path=pt_path, seed=args.seed)
     model = model.cuda()
@@ -292,7 +349,8 @@ def run(args):
         # the nn.Module path has no gradient exchange: N ranks would train N independent models and rank 0's would be saved
         raise RuntimeError("WORLD_SIZE > 1 needs the fused step (PICONS_FUSED=1): the autograd path does no gradient all-reduce")
     if fused:
-        engine = pstep.StepEngine(args, bs=args.bs, hw=hw, num_classes=NUM_CLASSES, jhmdb=(DATASET == "jhmdb"), state=model.state_dict(),
+        # the largest minibatch the two loaders can produce (an odd --bs gives bs // 2 + bs // 2); shorter ones run on plans of their own
+        engine = pstep.StepEngine(args, bs=2 * (args.bs // 2), hw=hw, num_classes=NUM_CLASSES, jhmdb=(DATASET == "jhmdb"), state=model.state_dict(),
                                   device="cuda:%d" % local)
         reducer = engine.make_reducer() if world > 1 else None
     save_path = os.path.join('train_log_wts', args.exp_id)

@@ -7,6 +7,7 @@ PyTorch is used for device memory, streams and (in dist.py) the RCCL collective 
 """
 import ctypes as C
 import os
+from collections import OrderedDict
 from types import SimpleNamespace
 
 import numpy as np
@@ -36,6 +37,17 @@ def exp_rampup(rampup_length):
 
 
 class StepEngine:
+    """One training step of the reference on a minibatch of m <= bs clips (m_lab labeled + m_unl unlabeled, both >= 1).
+
+    Plans per batch size: `bs` sizes the primary plan (self.plan, self.bs), which runs every full step exactly as it always has.  A step of
+    m < bs runs on a plan built for n = m the first time that size is staged, over the SAME P / G / M / V / R buffers (parameters,
+    gradients, Adam moments, BatchNorm running statistics), the same lanes, loss read-back, step count and num_batches_tracked -- one Adam
+    step and two BatchNorm updates, like a full step -- but with an arena of its own (its constants and its zero-once workspaces belong to
+    it alone).  At most SHORT_PLANS short plans are kept (least recently used arena freed beyond that): a reference epoch, whose two
+    loaders each end on one short batch, needs two.  self.active names the plan of the last staged step."""
+
+    SHORT_PLANS = 2
+
     def __init__(self, args, bs=8, hw=224, num_classes=24, device="cuda:0", jhmdb=False, state=None, seed=47, lanes=None, exp=None):
         if not torch.cuda.is_available():
             raise RuntimeError("StepEngine needs a GPU: the hot path is HIP-only (no CPU fallback)")
@@ -52,6 +64,7 @@ class StepEngine:
             # measured best on MI355X: lane 1 for the second Inception branch, lane 2 for the decoder's skip convs,
             # lane 3 for the weight gradients
             lanes = int(sw.get("PICONS_LANES", "4"))
+        self.lanes = lanes
         p = Plan(num_classes, hw, n=bs, groups=2, training=True, jhmdb=jhmdb, lanes=lanes, early_adam=True, exp=self.exp)
         self.side = [torch.cuda.Stream(device=self.dev) for _ in range(lanes - 1)]   # lanes 1.. of the op lists
         # ROCm binds a stream to one of its (by default four) hardware queues when the stream is first used, and two lanes on one
@@ -84,9 +97,14 @@ class StepEngine:
         self.R = torch.zeros(p.nrunning, **f32)
         base_a = (self.arena.data_ptr() + 255) // 256 * 256
         self._a0 = base_a - self.arena.data_ptr()
+        # per-plan state (arena, resolved op lists, input-op originals); self._cur / self.active / self.ops / self.bases follow the staged step
+        self._primary = self._cur = SimpleNamespace(plan=p, n=bs, arena=self.arena, a0=self._a0, to_ndhwc_orig=None, sched={})
+        self._short = OrderedDict()                   # n -> per-plan state, least recently used first
+        self.active = p
         p.upload_consts(self.aview)
         self.bases = dict(A=base_a, P=self.P.data_ptr(), G=self.G.data_ptr(), M=self.M.data_ptr(), V=self.V.data_ptr(), R=self.R.data_ptr())
         self.ops = p.resolve(self.bases)
+        self._primary.bases, self._primary.ops = self.bases, self.ops
         self.step_count = 0
         self.kind_ms, self.kind_count = 0.0, 0
         # the loss scalars are final before the backward starts: their D2H goes out on a stream of its own behind the loss list and
@@ -102,8 +120,84 @@ class StepEngine:
 
     # ------------------------------------------------------------------ views
     def aview(self, ref, nfloats, dtype=torch.float32):
-        o = self._a0 + ref[1]
-        return self.arena[o:o + 4 * nfloats].view(dtype)
+        """View of the ACTIVE plan's arena (ref: an arena reference of self.active)."""
+        c = self._cur
+        o = c.a0 + ref[1]
+        return c.arena[o:o + 4 * nfloats].view(dtype)
+
+    # ------------------------------------------------------------------ plans per batch size
+    def _build_short(self, n):
+        """Plan for n < bs clips over the shared parameter buffers, with an arena of its own (constants uploaded, zero-once workspaces zeroed)."""
+        p0 = self.plan
+        p = Plan(self.C, self.hw, n=n, groups=2, training=True, jhmdb=self.jhmdb, lanes=self.lanes, early_adam=True, exp=self.exp)
+        p.build_forward()
+        p.build_loss(self.args)
+        p.build_backward()
+        p.build_adam()
+        if p.nparams != p0.nparams or p.nrunning != p0.nrunning or p.poff != p0.poff or p.roff != p0.roff or p.adam_split != p0.adam_split:
+            raise RuntimeError("the plan for %d clips lays out the parameters differently from the plan for %d" % (n, self.bs))
+        arena = torch.empty(p.arena_bytes + 256, device=self.dev, dtype=torch.uint8)
+        base_a = (arena.data_ptr() + 255) // 256 * 256
+        c = SimpleNamespace(plan=p, n=n, arena=arena, a0=base_a - arena.data_ptr(), sched={})
+        bases = dict(self._primary.bases, A=base_a)
+        c.bases, c.ops = bases, p.resolve(bases)
+        c.to_ndhwc_orig = {idx: (int(c.ops["fwd"][idx]["i"][0]), int(c.ops["fwd"][idx]["p"][0])) for idx in p.op_to_ndhwc}
+        prev, self._cur = self._cur, c
+        try:
+            p.upload_consts(self.aview)            # on the current stream, ahead of the step that reads them
+        finally:
+            self._cur = prev
+        return c
+
+    def _activate(self, m):
+        """Make the plan for m clips the active one (built and cached on first use)."""
+        if m == self.bs:
+            c = self._primary
+        else:
+            c = self._short.get(m)
+            if c is None:
+                while len(self._short) >= self.SHORT_PLANS:
+                    # the evicted arena may still be read by the lanes of a step in flight: drain before torch may hand its memory out again
+                    self.synchronize()
+                    self._short.popitem(last=False)
+                c = self._short[m] = self._build_short(m)
+            else:
+                self._short.move_to_end(m)
+        if c is not self._cur:
+            self._cur, self.active, self.ops, self.bases = c, c.plan, c.ops, c.bases
+
+    def check_minibatch(self, label_mb, unlabel_mb, perm, drops, keys=("data", "aug_data", "loc_msk")):
+        """Refuse (ValueError) a minibatch the engine cannot run, before anything is enqueued or changed.  -> (m, m_lab)."""
+        sizes = []
+        for what, mb in (("labeled", label_mb), ("unlabeled", unlabel_mb)):
+            ks = tuple(keys) + ("action",) + (() if self.jhmdb else ("label_vid",))
+            try:
+                lens = {k: len(mb[k]) for k in ks}
+            except (KeyError, TypeError) as e:
+                raise ValueError("%s minibatch: %r" % (what, e)) from None
+            if len(set(lens.values())) != 1:
+                raise ValueError("%s minibatch: per-key sizes disagree: %s" % (what, lens))
+            k0 = next(iter(lens.values()))
+            if k0 < 1:
+                raise ValueError("%s minibatch is empty: a step needs at least one labeled and one unlabeled clip" % what)
+            sizes.append(k0)
+        m = sizes[0] + sizes[1]
+        if m > self.bs:
+            raise ValueError("minibatch of %d clips on an engine built for at most %d" % (m, self.bs))
+        self._check_perm_drops(m, perm, drops)
+        return m, sizes[0]
+
+    @staticmethod
+    def _check_perm_drops(m, perm, drops):
+        pm = np.asarray(perm)
+        if pm.shape != (m,) or not np.array_equal(np.sort(pm.astype(np.int64)), np.arange(m)):
+            raise ValueError("perm must be a permutation of range(%d), got shape %s" % (m, pm.shape))
+        if len(drops) != 4:
+            raise ValueError("drops: four Dropout3d scale arrays expected, got %d" % len(drops))
+        for d, c in zip(drops, (spec.TRUNK_OUT_CH, 128, spec.TRUNK_OUT_CH, 128)):
+            shp = tuple(d.shape) if hasattr(d, "shape") else np.shape(d)
+            if shp != (m, c):
+                raise ValueError("drops: shape %s, expected %s" % (shp, (m, c)))
 
     def param(self, name):
         shp = self.plan.pshape[name]
@@ -141,13 +235,14 @@ class StepEngine:
     # ------------------------------------------------------------------ staging
     def stage(self, label_mb, unlabel_mb, perm, drops):
         """Concat labeled+unlabeled, apply the shuffle (main_ucf101.py:65-79) and copy to the arena.
-        drops: four (bs,C) scale arrays [d832 pass0, d128 pass0, d832 pass1, d128 pass1]."""
-        p = self.plan
+        drops: four (m,C) scale arrays [d832 pass0, d128 pass0, d832 pass1, d128 pass1]; m = clips in both dicts, 2 <= m <= bs."""
+        n, _nl = self.check_minibatch(label_mb, unlabel_mb, perm, drops)
+        self._activate(n)
+        p = self.active
         self._restore_input_ops()
         T = lambda a: torch.as_tensor(np.asarray(a) if not torch.is_tensor(a) else a)
         cat = lambda k: torch.cat([T(label_mb[k]), T(unlabel_mb[k])], dim=0)
         perm = torch.as_tensor(np.asarray(perm)).long()
-        n = self.bs
         per = 3 * spec.FRAMES * self.hw * self.hw
         from . import inputpipe
         perm_d = None
@@ -222,11 +317,12 @@ class StepEngine:
 
     def _restore_input_ops(self):
         """stage() feeds the fp32 arena staging buffers: undo a HostDictStager.commit() that pointed the clip conversion at its own."""
-        for idx, (flag, ptr) in getattr(self, "_to_ndhwc_orig", {}).items():
+        c = self._cur
+        for idx, (flag, ptr) in (c.to_ndhwc_orig or {}).items():
             self.ops["fwd"][idx]["i"][0] = flag
-            self.ops["fwd"][idx]["i"][1] = self.bs
+            self.ops["fwd"][idx]["i"][1] = c.n
             self.ops["fwd"][idx]["p"][0] = ptr
-        for base, readers in getattr(self, "_patched", {}).values():
+        for base, readers in (getattr(self, "_patched", {}) if c is self._primary else {}).values():      # SampleStager: full steps only
             for name, idx, q, offb in readers:
                 self.ops[name][idx]["p"][q] = base + offb
 
@@ -236,7 +332,7 @@ class StepEngine:
         conv launches (csrc/conv_x6.hip).  Done once when the arena is created; again here after a step that raised, because a launch that
         failed or never ran can leave a counter mid-count, after which that tile's epilogue would never run again."""
         torch.cuda.synchronize(self.dev)
-        for ref, n in self.plan.zero_once:
+        for ref, n in self.active.zero_once:
             self.aview(ref, n).zero_()
         torch.cuda.synchronize(self.dev)
 
@@ -255,7 +351,7 @@ class StepEngine:
         backward list is replayed in segments and each gradient bucket's all-reduce is launched as soon
         as the ops that finalise it are enqueued.  timed_kind: accumulate hipEvent time of that op kind
         (bench.py roofline leg) into self.kind_ms / self.kind_count."""
-        p, o = self.plan, self.ops
+        p, o = self.active, self.ops
         o["fwd"][p.op_cmask]["i"][3] = 0 if epoch < self.args.thresh_epoch else 1
         o["loss"][p.op_loss]["f"][6] = wt_ramp
 
@@ -304,7 +400,7 @@ class StepEngine:
                 if end > done:
                     run(o["bwd"][done:end])
                     done = end
-            for i, (ready, _a, _b) in enumerate(reducer.buckets):
+            for i, ready in enumerate(self._bucket_ready(reducer)):
                 if ready > done:
                     run_to(ready)
                 reducer.launch(i, self.side)
@@ -314,7 +410,7 @@ class StepEngine:
         """on: the backward list's Adam op (plan.early_adam) updates every parameter but the stem's beside the stem's weight gradient,
         with THIS step's count and lr; adam() then updates the stem alone.  Off (a reducer is active: the gradients are only final
         after the all-reduce; or a caller that runs the lists by hand): the op is a no-op and adam() covers everything."""
-        k = self.plan.op_adam_early
+        k = self.active.op_adam_early
         self._early_armed = bool(on) and k is not None
         self._early_dp, self._early_lo = False, None
         if k is None:
@@ -334,7 +430,7 @@ class StepEngine:
         own lane, with 1/world folded in; adam() then covers the rest -- the trunk's last bucket, reduced at the end of the backward.
         forward_backward() fills in the range when it gets there."""
         self.arm_early_adam(lr, on=False)
-        k = self.plan.op_adam_early
+        k = self.active.op_adam_early
         ok = (k is not None and reducer is not None and reducer.active and reducer.cuda and not reducer.host_staged
               and sw.get("PICONS_EARLY_ADAM_DP", "1") != "0")
         self._early_dp = bool(ok)
@@ -355,8 +451,8 @@ class StepEngine:
         self.last_adam_split = int(a["l"][0])          # diagnostics / tests: the final Adam covered [0, last_adam_split), the early op the rest
         self._early_armed = False
         self._early_dp, self._early_lo = False, None
-        if self.plan.op_adam_early is not None:
-            self.ops["bwd"][self.plan.op_adam_early]["l"][0] = 0       # a backward replayed by hand must not step the optimiser
+        if self.active.op_adam_early is not None:
+            self.ops["bwd"][self.active.op_adam_early]["l"][0] = 0       # a backward replayed by hand must not step the optimiser
         for k in self.nbt:
             self.nbt[k] += 2           # two forward passes per step
 
@@ -364,7 +460,7 @@ class StepEngine:
         self._loss_done.record(torch.cuda.current_stream())
         self.scal_stream.wait_event(self._loss_done)
         with torch.cuda.stream(self.scal_stream):
-            self.scal_host.copy_(self.aview(self.plan.scalars, 20), non_blocking=True)   # spread_out sits at scalars + 16 (plan.build_loss)
+            self.scal_host.copy_(self.aview(self.active.scalars, 20), non_blocking=True)   # spread_out sits at scalars + 16 (plan.build_loss)
             self._scal_event.record(self.scal_stream)
         self.scal_event = self._scal_event
 
@@ -372,7 +468,7 @@ class StepEngine:
         """One packed D2H for the step's loss scalars (replaces the reference's five .item() syncs); the copy was enqueued behind
         the loss list by forward_backward, this waits for it (not for the backward / Adam)."""
         if self.scal_event is None:                           # the loss list was replayed by hand (tools/bench_loss.py): blocking copy
-            s = self.aview(self.plan.scalars, 20).cpu()
+            s = self.aview(self.active.scalars, 20).cpu()
         else:
             self.scal_event.synchronize()
             s = self.scal_host.clone()
@@ -393,12 +489,12 @@ class StepEngine:
         self.scal_stream.synchronize()
 
     def outputs(self):
-        """(output (bs,1,8,H,W), flip_op, predicted_action (bs,C)) of the last forward, shuffled order."""
-        p = self.plan
+        """(output (m,1,8,H,W), flip_op, predicted_action (m,C)) of the last forward, shuffled order; m = clips of the last staged step."""
+        p, n = self.active, self._cur.n
         per = spec.FRAMES * self.hw * self.hw
-        out = self.aview(p.out.ref, 2 * self.bs * per).view(2 * self.bs, 1, spec.FRAMES, self.hw, self.hw)
-        pred = self.aview(p.pred, 2 * self.bs * self.C).view(2 * self.bs, self.C)
-        return out[:self.bs], out[self.bs:], pred[:self.bs]
+        out = self.aview(p.out.ref, 2 * n * per).view(2 * n, 1, spec.FRAMES, self.hw, self.hw)
+        pred = self.aview(p.pred, 2 * n * self.C).view(2 * n, self.C)
+        return out[:n], out[n:], pred[:n]
 
     def make_reducer(self, group=None, target_floats=3_000_000, force=False, check=True):
         """check: refuse to train if the ranks do not hold identical parameters (dist.check_replicas_agree: one 3-number all-reduce)."""
@@ -406,7 +502,26 @@ class StepEngine:
         joined = sw.exp("PICONS_BUCKETS_JOINED", "0", self.exp) != "0"      # A/B switch: buckets only where lane 0 has joined their lane
         if check:
             pdist.check_replicas_agree(self.P, group)
-        return pdist.GradReducer(self.G, self.plan.grad_buckets(target_floats, joined=joined), group, force=force)
+        red = pdist.GradReducer(self.G, self.plan.grad_buckets(target_floats, joined=joined), group, force=force)
+        red.schedule_args = (target_floats, joined)
+        return red
+
+    def _bucket_ready(self, reducer):
+        """Ready-after-op indices of the reducer's buckets in the ACTIVE plan's backward list.  The buckets' parameter ranges -- what every
+        rank's collectives are issued over -- are the primary plan's; a short plan must give the same ranges in the same order, or ranks
+        running steps of different sizes would issue different collectives."""
+        if self._cur is self._primary:
+            return [b[0] for b in reducer.buckets]
+        args = getattr(reducer, "schedule_args", None)
+        if args is None:
+            raise RuntimeError("a short step under a reducer needs one made by StepEngine.make_reducer (its bucket schedule)")
+        got = self._cur.sched.get(args)
+        if got is None:
+            sched = self.active.grad_buckets(args[0], joined=args[1])
+            if [b[1:] for b in sched] != [b[1:] for b in reducer.buckets]:
+                raise RuntimeError("the plan for %d clips buckets the gradient differently from the plan for %d" % (self._cur.n, self.bs))
+            got = self._cur.sched[args] = [b[0] for b in sched]
+        return got
 
     def collect_timing(self):
         """Read the event pairs the timed replays left pending (pc_run_ops_timed_collect) into kind_ms / kind_count."""
@@ -459,7 +574,8 @@ class HostDictStager:
       commit(i+1)   at the head of step i+1 the main stream waits for that upload and the step's first kernels read the float64 staging
                     directly: pc_ncdhw_to_ndhwc converts f64 -> f32 while it re-lays the clip out (its op is re-pointed), the mask is cast
                     into the arena, the per-sample scalars and Dropout3d draws follow in one small packed upload.
-    The host never waits for the GPU here; its only wait stays StepEngine.read_scalars()."""
+    The host never waits for the GPU here; its only wait stays StepEngine.read_scalars().
+    A short minibatch (m < bs clips) uses the first m rows of the bs-sized buffers; commit() makes the plan for m the engine's active one."""
 
     def __init__(self, eng, dtype=torch.float64, host=True):
         self.eng = eng
@@ -479,17 +595,19 @@ class HostDictStager:
         self.consumed = [torch.cuda.Event(), torch.cuda.Event()]
         self.used = [False, False]
         self.host = [None, None]
+        self.m = [n, n]                                 # clips staged in each slot
         # the 180 MB gather is 24 sample-sized memcpys: one thread moves ~5 GB/s (33 ms per step, more than the step itself); tensor.copy_
         # releases the GIL, so a small pool brings it to a few ms
         from concurrent.futures import ThreadPoolExecutor
         self.pool = ThreadPoolExecutor(max_workers=int(sw.get("PICONS_STAGE_THREADS", "8"))) if host else None
-        if not hasattr(eng, "_to_ndhwc_orig"):
-            eng._to_ndhwc_orig = {idx: (int(eng.ops["fwd"][idx]["i"][0]), int(eng.ops["fwd"][idx]["p"][0])) for idx in eng.plan.op_to_ndhwc}
+        c = eng._primary
+        if c.to_ndhwc_orig is None:
+            c.to_ndhwc_orig = {idx: (int(c.ops["fwd"][idx]["i"][0]), int(c.ops["fwd"][idx]["p"][0])) for idx in c.plan.op_to_ndhwc}
 
     def prepare(self, slot, label_mb, unlabel_mb, perm, drops):
         """Host side of one minibatch: gather into the pinned slot in shuffled order, enqueue the uploads.  Returns at once."""
-        eng, n = self.eng, self.eng.bs
-        nl = len(label_mb["action"])
+        eng = self.eng
+        n, nl = eng.check_minibatch(label_mb, unlabel_mb, perm, drops, keys=tuple(self.shapes))
         T_ = lambda a: a if torch.is_tensor(a) else torch.from_numpy(np.asarray(a))
         perm = np.asarray(perm)
         if self.used[slot]:
@@ -507,17 +625,18 @@ class HostDictStager:
             lab_flag = torch.cat([torch.ones(nl), torch.zeros(n - nl)])[perm]
         else:
             lab_flag = torch.cat([T_(label_mb["label_vid"]), T_(unlabel_mb["label_vid"])]).float()[perm]
+        self.m[slot] = n
         self._pack_small(slot, act, lab_flag, drops)
         with torch.cuda.stream(self.copy_stream):
             for k in self.shapes:
-                self.dev[slot][k].copy_(self.pin[slot][k], non_blocking=True)
+                self.dev[slot][k][:n].copy_(self.pin[slot][k][:n], non_blocking=True)
             self.dev_small[slot].copy_(self.pin_small[slot], non_blocking=True)
             self.ready[slot].record(self.copy_stream)
         self.used[slot] = True
 
     def _pack_small(self, slot, act, lab_flag, drops):
         """Per-sample scalars and the four Dropout3d draws of a step into the slot's page-locked vector (uploaded in one copy)."""
-        n = self.eng.bs
+        n = self.m[slot]
         T_ = lambda a: a if torch.is_tensor(a) else torch.from_numpy(np.asarray(a))
         ps = self.pin_small[slot]
         ps[:n] = act
@@ -531,9 +650,11 @@ class HostDictStager:
     def commit(self, slot):
         """Head of the step (main stream): wait for the slot's upload, point the clip conversion at its float64 staging, cast the mask
         and scatter the small inputs into the arena."""
-        eng, p, n = self.eng, self.eng.plan, self.eng.bs
+        eng = self.eng
         main = torch.cuda.current_stream(eng.dev)
         main.wait_event(self.ready[slot])
+        eng._activate(self.m[slot])
+        p = eng.active
         eng._restore_input_ops()                      # whatever another stager left re-pointed
         fwd = eng.ops["fwd"]
         for g, idx in enumerate(p.op_to_ndhwc):
@@ -542,9 +663,9 @@ class HostDictStager:
         self._commit_small(slot)
 
     def _commit_small(self, slot):
-        eng, p, n = self.eng, self.eng.plan, self.eng.bs
+        eng, p, n = self.eng, self.eng.active, self.m[slot]
         per = spec.FRAMES * eng.hw * eng.hw
-        eng.aview(p.in_seg, n * per).copy_(self.dev[slot]["loc_msk"].reshape(-1))         # (f64 -> f32 on the device)
+        eng.aview(p.in_seg, n * per).copy_(self.dev[slot]["loc_msk"][:n].reshape(-1))     # (f64 -> f32 on the device)
         ds = self.dev_small[slot]
         eng.aview(p.in_cls, 2 * n).copy_(torch.cat([ds[:n], ds[:n]]))
         eng.aview(p.in_labeled, 2 * n, torch.int32).copy_(torch.cat([ds[n:2 * n], ds[n:2 * n]]).to(torch.int32))
@@ -566,9 +687,12 @@ class SampleStager(HostDictStager):
     current step runs, and IN THE LAYOUT THE FIRST CONV READS ([2 bs][T][H][W][4]: clip and flipped clip, RGB padded to one 16-byte piece,
     pc_clip_from_u8_ndhwc4).  No stack, no cat, no gather, no copy into the arena and no NCDHW -> NDHWC conversion: commit() re-points the
     readers of the clip (the stem's conv and its weight gradient) at the buffer and switches the conversion ops off; the only per-step copies left
-    are the mask (6 MB) and the small vectors."""
+    are the mask (6 MB) and the small vectors.
+    Full steps only (m = bs, the primary plan): its buffers are re-pointed into the primary plan's op lists, and prepare() refuses any other
+    size with a ValueError before it writes anything."""
 
     def __init__(self, eng):
+        eng._activate(eng.bs)                          # readers_of() scans the active plan's lists
         super().__init__(eng, dtype=torch.float32, host=False)
         n, hw, T = eng.bs, eng.hw, spec.FRAMES
         p = eng.plan
@@ -619,6 +743,9 @@ class SampleStager(HostDictStager):
         random draws come in the reference's order whatever the shuffle."""
         eng, n = self.eng, self.eng.bs
         perm = np.asarray(perm)
+        if perm.shape != (n,) or not 1 <= nl < n:
+            raise ValueError("SampleStager stages full minibatches only: %d clips (%d labeled) on an engine built for %d" % (perm.size, nl, n))
+        eng._check_perm_drops(n, perm, drops)
         where = np.empty(n, np.int64)
         where[perm] = np.arange(n)                     # sample i lands at position where[i]
         x, m = self.x[slot], self.dev[slot]["loc_msk"]
@@ -648,6 +775,7 @@ class SampleStager(HostDictStager):
         conversion is switched off.  No kernel, no copy."""
         eng, p = self.eng, self.eng.plan
         torch.cuda.current_stream(eng.dev).wait_event(self.ready[slot])
+        eng._activate(eng.bs)
         for idx in p.op_to_ndhwc:
             eng.ops["fwd"][idx]["i"][1] = 0                                    # N = 0: nothing to convert
         ds = self.dev_small[slot].data_ptr()

@@ -143,6 +143,20 @@ def make_step_inputs(bs, rank=0, step=0, num_classes=24, hw=224):
     return lab, unl, perm, drops
 
 
+def make_step_inputs_split(n_lab, n_unl, rank=0, step=0, num_classes=24, hw=224):
+    """make_step_inputs with n_lab labeled and n_unl unlabeled clips (the reference's loaders end an epoch on a short batch,
+    main_ucf101.py:353-366 has no drop_last): the two dicts, a permutation of n_lab + n_unl and the four (n_lab + n_unl, C) Dropout3d
+    draws, all from PCG64 seeds of (rank, step, n_lab, n_unl)."""
+    m = n_lab + n_unl
+    base = 1234 + rank + 1000003 * step + 7919 * (64 * n_lab + n_unl)
+    lab = make_minibatch(n_lab, True, base * 2 + 0, num_classes, hw)
+    unl = make_minibatch(n_unl, False, base * 2 + 1, num_classes, hw)
+    g = np.random.default_rng(base * 2 + 7)
+    perm = g.permutation(m)
+    drops = [(g.random((m, c)) < 0.5).astype(np.float32) * 2.0 for c in (spec.TRUNK_OUT_CH, 128, spec.TRUNK_OUT_CH, 128)]
+    return lab, unl, perm, drops
+
+
 def make_eval_videos(n, seed=1234, num_classes=24, hw=224):
     """Synthetic evaluation set in the format the reference's eval loader yields (datasets/ucf_dataloader_eval.py via
     evaluate_ucf101.py:74-77): (video [F,hw,hw,3] float32 in [0,1], bbox [F,hw,hw,1] float32 {0,1}, label), F = 8..40, one
