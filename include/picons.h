@@ -58,10 +58,10 @@ typedef void* pc_stream;            /* hipStream_t */
 
 /* ABI version of this header: bumped whenever a struct in it grows or an op's operands change (101: pc_wino_desc.m, PC_OP_BN_FIN_APPLY,
  * pc_wgrad_desc.ws_slices, pc_transpose_job.nslices / slice_stride, pc_wgrad_slices; 102: the workspace operands of PC_OP_TAIL6_WGRAD_MAP / PC_OP_TAIL6_BIAS_SUMS /
- * PC_OP_TAIL_GRADS).  Descriptors must be zero-initialised by the caller:
+ * PC_OP_TAIL_GRADS; 103: the variant reporters pc_conv_variant / pc_wino_variant / pc_wgrad_variant).  Descriptors must be zero-initialised by the caller:
  * fields added later read as "old behaviour" when 0.  pc_version() returns the value the library was built with; the Python host
  * (capi.lib()) refuses a library whose version differs from the header it mirrors. */
-#define PC_VERSION 102
+#define PC_VERSION 103
 int         pc_version(void);
 const char* pc_last_error(void);
 
@@ -137,6 +137,13 @@ int pc_split_planes_multi(const pc_split_job* jobs, int njobs, pc_stream s);
  *   [6] 1 = LDS-DMA kernel with the per-tile tap box, 0 = register-staged kernel (flattened K).
  * ci_real / co_real: channels that are not padding (0 = Ci / Co). */
 int pc_conv_work(const pc_conv_desc* d, int ci_real, int co_real, double* out);
+/* Host-only (no GPU call): the kernel template instance pc_conv_fwd -- for a PC_F_X6 descriptor pc_conv_fwd_x6_ws with a workspace of ws_floats
+ * floats (0 = none) -- WOULD launch for this descriptor with 16-byte aligned operands, as one NUL-terminated string in buf[cap].  It comes from
+ * the decision code the launch itself runs, so tests can say which variant a case exercises (tests/variant_cases.py):
+ *   conv:<glds|glds_tap8|reg_fast|reg_ragged>:<BM>x<BN>:w<WM>x<WN>[:st<LDS-DMA ring depth>][:ci3]
+ *        glds = LDS-DMA gather, glds_tap8 = its 8-taps-per-chunk form for Ci == 4, reg_* = register-staged gather with K a multiple of 32 / ragged
+ *   x6:<BM>x<BN>:w<WM>x<WN>:ks<K slices of the tail tiles; 1 = no tail split>[:mfast]        mfast = row tiles fastest in the block order */
+int pc_conv_variant(const pc_conv_desc* d, int64_t ws_floats, char* buf, int cap);
 
 /* ------------------------------------------------------------------------------------------
  * Winograd F(2x2, 3x3) form of the stride-1, "same"-padded KT x 3 x 3 convolutions (KT = 3 with temporal padding 1, or 1):
@@ -171,6 +178,9 @@ int pc_wino4_weights(const float* w, int64_t sO, int64_t sT, int64_t sI, int O, 
 int pc_wino_bnpart_rows(const pc_wino_desc* d);
 /* host-only work accounting (see pc_conv_work): out[0] issued, out[1] executed multiply-accumulates, out[2] blocks */
 int pc_wino_work(const pc_wino_desc* d, double* out);
+/* host-only, as pc_conv_variant: wino2:<BTH>x<BTW>|strips:<vec|scalar> or wino4:<BTH>x<BTW>:<vec|scalar> -- F(2x2) / F(4x4), the tile rectangle of a
+ * block (or strip mode), 16-byte or four-byte stores in the epilogue.  Of `out` only the alignment counts (NULL = 16-byte aligned). */
+int pc_wino_variant(const pc_wino_desc* d, const float* out, char* buf, int cap);
 
 /* Weight gradient:  g[m][ (a,b,c) , cs ] += sum_{n,q} D[n,q,m] * S[n, q*istr+ioff0+(a,b,c)*istep, cs]
  * D dense over the lattice (Tq,Hq,Wq), S gathered.  g layout [Cd][KT*KH*KW][Cs], tap (a,b,c) -> wk0+(a,b,c),
@@ -205,6 +215,10 @@ int pc_conv_wgrad(const pc_wgrad_desc* d, const float* D, const float* S, float*
 /* K slices the launch(es) of pc_conv_wgrad make for this problem (host-only, no GPU call; ws_slices is ignored): the number of workspace
  * images a caller that sets ws_slices has to provide.  -1 on a bad descriptor. */
 int pc_wgrad_slices(const pc_wgrad_desc* d);
+/* host-only, as pc_conv_variant (a dry run of pc_conv_wgrad): <kernel><template arguments>[+<second launch>]:k<K slices>:<store|atomic|ws> with
+ * wgrad4[_x6] the 7 x 7 stem, wgrad3[_x6]<BM,BKP,CSB,WMW[,KW]> the row-segment kernels, wgrad[_x6]<BM,BN[,positions per chunk]> generic split-K;
+ * store = plain stores of one slice (splitk = -1), atomic = fp32 atomics, ws = ordered K-slice images (ws_slices > 0). */
+int pc_wgrad_variant(const pc_wgrad_desc* d, char* buf, int cap);
 /* Folds the K-slice images of a workspace in place, for launches with many slices: image g*G of every group of G = pc_wgrad_fold_group()
  * consecutive images becomes the sum of its group (slice order); the consumer then adds ceil(nslices / G) images G*image_floats apart. */
 int pc_wgrad_fold_group(void);

@@ -79,7 +79,7 @@ ACT_NONE, ACT_RELU, ACT_SIGMOID = 0, 1, 2
 F_ACCUM, F_BIAS, F_CSCALE, F_BNPART, F_NFAST, F_TOUT, F_CI3, F_X6, F_STRIPS = 1, 2, 4, 8, 16, 32, 64, 128, 256
 WG_CS3, WG_X6 = 1, 2
 
-ABI_VERSION = 102          # PC_VERSION of include/picons.h
+ABI_VERSION = 103          # PC_VERSION of include/picons.h
 
 _SIGS = {
     "pc_version": (i32, []),
@@ -93,6 +93,9 @@ _SIGS = {
     "pc_split_planes": (i32, [vp, vp, i64, i64, vp]),
     "pc_split_planes_multi": (i32, [vp, i32, vp]),
     "pc_conv_work": (i32, [C.POINTER(ConvDesc), i32, i32, C.POINTER(C.c_double)]),
+    "pc_conv_variant": (i32, [C.POINTER(ConvDesc), i64, C.c_char_p, i32]),
+    "pc_wino_variant": (i32, [C.POINTER(WinoDesc), vp, C.c_char_p, i32]),
+    "pc_wgrad_variant": (i32, [C.POINTER(WgradDesc), C.c_char_p, i32]),
     "pc_conv_wgrad": (i32, [C.POINTER(WgradDesc), vp, vp, vp, vp]),
     "pc_conv_wgrad_multi": (i32, [vp, i32, vp]),
     "pc_wgrad_slices": (i32, [C.POINTER(WgradDesc)]),
@@ -206,6 +209,13 @@ def lib():
 def check(rc):
     if rc != 0:
         raise RuntimeError("libpicons error %d: %s" % (rc, lib().pc_last_error().decode()))
+
+
+def variant(name, desc, *args):
+    """The kernel template instance a launch of `desc` would take (pc_conv_variant / pc_wino_variant / pc_wgrad_variant; host-only)."""
+    buf = C.create_string_buffer(160)
+    check(getattr(lib(), name)(desc, *args, buf, 160))
+    return buf.value.decode()
 
 
 def call(name, *args):

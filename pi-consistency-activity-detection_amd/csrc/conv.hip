@@ -5,6 +5,7 @@
 // Replaces the ATen/cuDNN convolution call sites listed in SURVEY.md §2a (K1, K6, K9-K12).
 #include "conv_common.h"
 #include <stdlib.h>
+#include <string.h>
 #include <type_traits>
 #include <algorithm>
 #include <vector>
@@ -494,21 +495,46 @@ int launch_conv_glds_v(const ConvK& k, hipStream_t s) {
     return PC_OK;
 }
 
+// Which kernel template instance a launch takes: ONE decision (conv_choice) for the launch (launch_conv) and for the host-only reporter
+// (pc_conv_variant), so a test can name the variant it exercises without re-deriving the heuristics.
+enum ConvFamily { CF_GLDS, CF_GLDS_TAP8, CF_REG_FAST, CF_REG_RAGGED };
+struct ConvChoice { ConvFamily fam; int var; };          // var: VAR of conv_gemm_glds_kernel (ring depth = 2 + ((var >> 3) & 3), bit 5 = PC_F_CI3)
+
 // PICONS_CONV_VARIANT (tuning, tools/ablate_conv.py): bit 0 = s_setprio around the MFMA groups, bit 1 = issue the next
 // tile's LDS-DMA after the first MFMA group instead of before it.  Same results in every variant.
-template <int BM, int BN, int WM, int WN>
-int launch_conv_glds(const ConvK& k, hipStream_t s) {
+inline int conv_glds_var(int bm, int bn, int groups, int Mg, int Co) {
     static const int var = getenv("PICONS_CONV_VARIANT") ? atoi(getenv("PICONS_CONV_VARIANT")) : CONV_DEFAULT_VARIANT;
     // LDS-DMA ring depth.  Default: 3 stages for launches of at most one block per CU (the 196-block 28x28 layers: 10-25 % faster --
     // nothing else on the CU covers the latency of a tile fetch that misses L2), the double buffer otherwise (a ring costs full
     // launches 5-8 %).  PICONS_CONV_STAGES=2|3|4 forces a depth where two blocks of it still fit a CU.
     static const int stages = getenv("PICONS_CONV_STAGES") ? atoi(getenv("PICONS_CONV_STAGES")) : 0;
-    if constexpr (BM * BN <= 128 * 64) {
-        const size_t per_stage = (size_t)(BM + BN) * BK * sizeof(float);
-        const long long grid = (long long)k.groups * cdiv(k.Mg, BM) * cdiv(k.Co, BN);
+    if (bm * bn <= 128 * 64) {
+        const size_t per_stage = (size_t)(bm + bn) * BK * sizeof(float);
+        const long long grid = (long long)groups * cdiv(Mg, bm) * cdiv(Co, bn);
         const int want = stages ? stages : (grid <= 256 ? 3 : 2);
-        if (want == 4 && 4 * per_stage <= 72 * 1024) return launch_conv_glds_v<BM, BN, WM, WN, 16>(k, s);
-        if (want >= 3 && 3 * per_stage <= 76 * 1024) return launch_conv_glds_v<BM, BN, WM, WN, 8>(k, s);
+        if (want == 4 && 4 * per_stage <= 72 * 1024) return 16;
+        if (want >= 3 && 3 * per_stage <= 76 * 1024) return 8;
+    }
+    return var & 3;
+}
+
+inline ConvChoice conv_choice(const ConvK& k, int bm, int bn) {
+    static const int no_glds = getenv("PICONS_CONV_NO_GLDS") ? atoi(getenv("PICONS_CONV_NO_GLDS")) : 0;
+    static const int no_tap4 = getenv("PICONS_CONV_NO_TAP4") ? atoi(getenv("PICONS_CONV_NO_TAP4")) : 0;
+    const bool fast = k.Ci % BK == 0;
+    const bool small_taps = k.ntap[0] <= 10 && k.ntap[1] <= 10 && k.ntap[2] <= 10;
+    if (bm == 128 && bn == 64)
+        if (k.Ci == 4 && !no_glds && !no_tap4 && small_taps && ((uintptr_t)k.in % 16 == 0) && k.ldi % 4 == 0 && k.ldw % 4 == 0)
+            return {CF_GLDS_TAP8, (k.flags & PC_F_CI3) ? (4 | 32) : 4};
+    if (fast && !no_glds && small_taps && ((uintptr_t)k.in % 16 == 0) && k.ldi % 4 == 0) return {CF_GLDS, conv_glds_var(bm, bn, k.groups, k.Mg, k.Co)};
+    return {fast ? CF_REG_FAST : CF_REG_RAGGED, 0};
+}
+
+template <int BM, int BN, int WM, int WN>
+int launch_conv_glds(const ConvK& k, hipStream_t s, int var) {
+    if constexpr (BM * BN <= 128 * 64) {
+        if (var == 16) return launch_conv_glds_v<BM, BN, WM, WN, 16>(k, s);
+        if (var == 8) return launch_conv_glds_v<BM, BN, WM, WN, 8>(k, s);
     }
     switch (var & 3) {
         case 1: return launch_conv_glds_v<BM, BN, WM, WN, 1>(k, s);
@@ -559,16 +585,12 @@ int launch_conv(const ConvK& k, hipStream_t s) {
         return launch_ablate<BM, BN, WM, WN, 3>(k, s);
     }
 #endif
-    static const int no_glds = getenv("PICONS_CONV_NO_GLDS") ? atoi(getenv("PICONS_CONV_NO_GLDS")) : 0;
-    const bool fast = k.Ci % BK == 0;
-    static const int no_tap4 = getenv("PICONS_CONV_NO_TAP4") ? atoi(getenv("PICONS_CONV_NO_TAP4")) : 0;
+    const ConvChoice c = conv_choice(k, BM, BN);
     if constexpr (BM == 128 && BN == 64)
-        if (k.Ci == 4 && !no_glds && !no_tap4 && k.ntap[0] <= 10 && k.ntap[1] <= 10 && k.ntap[2] <= 10 && ((uintptr_t)k.in % 16 == 0) && k.ldi % 4 == 0 &&
-            k.ldw % 4 == 0)
-            return (k.flags & PC_F_CI3) ? launch_conv_glds_v<BM, BN, WM, WN, 4 | 32>(k, s) : launch_conv_glds_v<BM, BN, WM, WN, 4>(k, s);
-    if (fast && !no_glds && k.ntap[0] <= 10 && k.ntap[1] <= 10 && k.ntap[2] <= 10 && ((uintptr_t)k.in % 16 == 0) && k.ldi % 4 == 0)
-        return launch_conv_glds<BM, BN, WM, WN>(k, s);
-    return fast ? launch_conv2<BM, BN, WM, WN, true>(k, s) : launch_conv2<BM, BN, WM, WN, false>(k, s);
+        if (c.fam == CF_GLDS_TAP8)
+            return (c.var & 32) ? launch_conv_glds_v<BM, BN, WM, WN, 4 | 32>(k, s) : launch_conv_glds_v<BM, BN, WM, WN, 4>(k, s);
+    if (c.fam == CF_GLDS) return launch_conv_glds<BM, BN, WM, WN>(k, s, c.var);
+    return c.fam == CF_REG_FAST ? launch_conv2<BM, BN, WM, WN, true>(k, s) : launch_conv2<BM, BN, WM, WN, false>(k, s);
 }
 
 // tile choice: minimise padded work, prefer larger tiles when the grid still fills the chip
@@ -607,6 +629,17 @@ inline TileCfg launch_tile(const pc_conv_desc* d, int groups) {
         if (per_row % 128 != 0 && per_row % 64 == 0) { c.bm = 64; c.bn = d->Co >= 128 ? 128 : 64; c.wm = d->Co >= 128 ? 1 : 2; }
     }
     return c;
+}
+
+// The template instance <BM, BN, WM, WN> pc_conv_fwd instantiates for launch_tile's answer (anything else runs on the 128 x 32 tile)
+struct ConvInst { int bm, bn, wm, wn; };
+inline ConvInst conv_inst(const pc_conv_desc* d, int groups) {
+    const TileCfg c = launch_tile(d, groups);
+    if (c.bm == 64 && c.bn == 128) return {64, 128, 1, 4};
+    if (c.bm == 128 && c.bn == 128) return {128, 128, 2, 2};
+    if (c.bm == 128 && c.bn == 64) return {128, 64, 2, 2};
+    if (c.bm == 64 && c.bn == 64) return {64, 64, 2, 2};
+    return {128, 32, 4, 1};
 }
 
 }  // namespace
@@ -723,7 +756,7 @@ static int pc_conv_fwd_g(const pc_conv_desc* d, int groups, const float* in, con
     k.M = (int)M; k.groups = groups; k.Mg = (int)(M / groups);
     static const int scalar_epi = getenv("PICONS_CONV_SCALAR_EPI") ? atoi(getenv("PICONS_CONV_SCALAR_EPI")) : 0;
     k.act = d->act; k.flags = (d->flags & ~F_SCALAR_EPI) | (scalar_epi ? F_SCALAR_EPI : 0); k.act_c0 = d->act_c0; k.wgstride = d->wgstride; k.bgstride = d->bgstride;
-    const TileCfg c = launch_tile(d, groups);
+    const ConvInst c = conv_inst(d, groups);
     if (c.bm == 64 && c.bn == 128) return launch_conv<64, 128, 1, 4>(k, s);
     if (c.bm == 128 && c.bn == 128) return launch_conv<128, 128, 2, 2>(k, s);
     if (c.bm == 128 && c.bn == 64) return launch_conv<128, 64, 2, 2>(k, s);
@@ -734,6 +767,30 @@ static int pc_conv_fwd_g(const pc_conv_desc* d, int groups, const float* in, con
 extern "C" int pc_conv_fwd(const pc_conv_desc* d, const float* in, const float* w, const float* bias,
                            const float* cscale, float* out, float* bnpart, pc_stream s) {
     return pc_conv_fwd_g(d, d && d->groups > 0 ? d->groups : 1, in, w, bias, cscale, out, bnpart, (hipStream_t)s);
+}
+
+// Host-only (no GPU call): the kernel template instance pc_conv_fwd -- or, for a PC_F_X6 descriptor, pc_conv_fwd_x6_ws with a workspace of
+// ws_floats floats -- WOULD launch for this descriptor with 16-byte aligned operands, from the decision code the launches themselves run
+// (conv_inst / conv_choice here, pc_x6_tile / x6_split in conv_x6.hip).  One string:
+//   conv:<glds|glds_tap8|reg_fast|reg_ragged>:<BM>x<BN>:w<WM>x<WN>[:st<ring depth>][:ci3]      (glds = LDS-DMA, reg = register-staged gather)
+//   x6:<BM>x<BN>:w<WM>x<WN>:ks<K slices of the tail tiles, 1 = no tail split>[:mfast]        (mfast = row tiles fastest in the block order)
+extern "C" int pc_conv_variant(const pc_conv_desc* d, int64_t ws_floats, char* buf, int cap) {
+    PC_CHECK_ARG(d && buf && cap > 0, "pc_conv_variant: null pointer");
+    const int groups = d->groups > 0 ? d->groups : 1;
+    PC_CHECK_ARG(d->N > 0 && d->N % groups == 0, "pc_conv_variant: N %% groups");
+    if (d->flags & PC_F_X6) return pc_x6_variant(d, ws_floats, buf, cap);
+    PC_CHECK_ARG(d->Ci % 4 == 0 && d->ldi % 4 == 0 && d->ldw % 4 == 0, "pc_conv_variant: Ci/ldi/ldw must be multiples of 4 (Ci=%d ldi=%d ldw=%d)", d->Ci, d->ldi, d->ldw);
+    const ConvInst t = conv_inst(d, groups);
+    ConvK k = {};
+    k.Ci = d->Ci; k.ldi = d->ldi; k.ldw = d->ldw; k.Co = d->Co; k.flags = d->flags; k.groups = groups;
+    k.Mg = (int)((int64_t)(d->N / groups) * d->Tq * d->Hq * d->Wq);
+    for (int i = 0; i < 3; ++i) k.ntap[i] = d->ntap[i];
+    const ConvChoice c = conv_choice(k, t.bm, t.bn);
+    static const char* const fam[] = {"glds", "glds_tap8", "reg_fast", "reg_ragged"};
+    int n = snprintf(buf, (size_t)cap, "conv:%s:%dx%d:w%dx%d", fam[c.fam], t.bm, t.bn, t.wm, t.wn);
+    if (n > 0 && n < cap && (c.fam == CF_GLDS || c.fam == CF_GLDS_TAP8)) n += snprintf(buf + n, (size_t)(cap - n), ":st%d%s", 2 + ((c.var >> 3) & 3), (c.var & 32) ? ":ci3" : "");
+    PC_CHECK_ARG(n > 0 && n < cap, "pc_conv_variant: the buffer holds %d bytes", cap);
+    return PC_OK;
 }
 
 // =============================================================================================
@@ -1715,6 +1772,31 @@ inline WgSplit wg_generic_split(const pc_wgrad_desc* d) {
     return w;
 }
 
+// Which kernel template instance a problem's launch takes, per route: ONE choice for the launch (wgrad_run) and for the reporter
+// (pc_wgrad_variant).  The index selects the launch in wgrad_run's switches and the name in these tables.
+static const char* const WG_STEM_NAME[] = {"wgrad4_x6<7,2,7>", "wgrad4<28,7,2,7,pack3>", "wgrad4<28,7,2,7>"};
+inline int wg_stem_inst(const pc_wgrad_desc* d) {
+    static const int pack3 = getenv("PICONS_WGRAD_STEM_PACK3") ? atoi(getenv("PICONS_WGRAD_STEM_PACK3")) : 1;
+    return wg_stem_x6(d) ? 0 : (((d->flags & PC_WG_CS3) && pack3) ? 1 : 2);
+}
+static const char* const WG_ROW_NAME[] = {"wgrad3_x6<64,64,64,2>", "wgrad3_x6<64,32,64,2>", "wgrad3_x6<128,64,32,4>", "wgrad3_x6<128,32,32,4>", "wgrad3<64,20,64,2,9>",
+                                          "wgrad3<128,28,32,4>",   "wgrad3<64,56,64,2>",    "wgrad3<64,28,64,2>",     "wgrad3<128,28,64,2>"};
+inline int wg_row_inst(const Row3Geo& geo, bool row9) {
+    if (geo.x6) return (geo.csb64 && geo.bkp == 64) ? 0 : geo.csb64 ? 1 : geo.bkp == 64 ? 2 : 3;
+    if (row9) return 4;
+    if (!geo.csb64) return 5;
+    if (geo.small_m && geo.bkp == 56) return 6;
+    return geo.small_m ? 7 : 8;
+}
+static const char* const WG_GEN_NAME[] = {"wgrad_x6<64,128>", "wgrad_x6<128,128>", "wgrad<64,256,16>", "wgrad<64,128,32>", "wgrad<128,256,16>", "wgrad<128,128,32>"};
+inline int wg_generic_inst(const pc_wgrad_desc* d, bool small_m, bool wide) {
+    if (d->flags & PC_WG_X6) return small_m ? 0 : 1;
+    if (small_m) return wide ? 2 : 3;
+    return wide ? 4 : 5;
+}
+// what a dry run of wgrad_run reports: K slices (workspace images) of the launch, and its kernel instance(s)
+struct WgDry { int nslices; char name[96]; };
+
 }  // namespace
 
 // Host-only work accounting of one pc_conv_wgrad call (no GPU call), see pc_conv_work.  out[5]: multiply-accumulates ISSUED to
@@ -1791,8 +1873,8 @@ inline long long wg_image_floats(const pc_wgrad_desc* d) {
         else hipLaunchKernelGGL(kernel, grid, dim3(256), 0, s, arg);                                           \
     } while (0)
 
-// dry != NULL: no launch -- *dry = the number of K slices (workspace images) the launch would write (pc_wgrad_slices)
-static int wgrad_run(const pc_wgrad_desc* d, const float* D, const float* S, float* g, pc_stream s_, int* dry) {
+// dry != NULL: no launch -- dry->nslices = the number of K slices (workspace images) the launch would write (pc_wgrad_slices), dry->name = its kernel(s)
+static int wgrad_run(const pc_wgrad_desc* d, const float* D, const float* S, float* g, pc_stream s_, WgDry* dry) {
     hipStream_t s = (hipStream_t)s_;
     PC_CHECK_ARG(d && (dry || (D && S && g)), "pc_conv_wgrad: null pointer");
     PC_CHECK_ARG(d->Cd % 4 == 0 && d->Cs % 4 == 0 && d->ldd % 4 == 0 && d->lds % 4 == 0,
@@ -1838,8 +1920,8 @@ static int wgrad_run(const pc_wgrad_desc* d, const float* D, const float* S, flo
         q.ntap_t = d->ntap[0]; q.wk0_t = d->wk0[0]; q.wk0_h = d->wk0[1]; q.KH = d->KH;
         q.Ts = d->Ts; q.Hs = d->Hs; q.Wsw = d->Ws; q.istr_t = d->istr[0]; q.istr_h = d->istr[1]; q.ioff_t = d->ioff0[0]; q.ioff_h = d->ioff0[1];
         q.padw = -d->ioff0[2];
-        static const int pack3 = getenv("PICONS_WGRAD_STEM_PACK3") ? atoi(getenv("PICONS_WGRAD_STEM_PACK3")) : 1;
-        const bool x6 = wg_stem_x6(d);                  // bf16-split kernel: chunks of two 16-position sub-chunks
+        const int inst = wg_stem_inst(d);
+        const bool x6 = inst == 0;                      // bf16-split kernel: chunks of two 16-position sub-chunks
         q.nseg = x6 ? cdiv(d->Wq, 16) : d->Wq / 28; q.mt = cdiv(d->Cd, 64); q.taps_full = d->KT * d->KH * d->KW;
         // K slices per kt in proportion to the output t planes whose source plane exists
         int ntv[10], tot = 0;
@@ -1862,7 +1944,7 @@ static int wgrad_run(const pc_wgrad_desc* d, const float* D, const float* S, flo
         }
         const dim3 grid((unsigned)(q.pre[q.ntap_t] * q.mt));
         for (int a = 0; a < q.ntap_t; ++a) nslices = std::max(nslices, q.pre[a + 1] - q.pre[a]);
-        if (dry) { *dry = nslices; return PC_OK; }
+        if (dry) { dry->nslices = nslices; snprintf(dry->name, sizeof dry->name, "%s", WG_STEM_NAME[inst]); return PC_OK; }
         PC_CHECK_ARG(!wss || nslices <= d->ws_slices, "pc_conv_wgrad: the workspace holds %d slice images, this launch writes %d (pc_wgrad_slices)", d->ws_slices, nslices);
         q.wss = wss;
         {   // block order: slices sorted by where in the volume they are (their relative position inside their kt's slice range), kt as tie-break
@@ -1879,8 +1961,8 @@ static int wgrad_run(const pc_wgrad_desc* d, const float* D, const float* S, flo
                 for (int i = 0; i < tot_sl; ++i) q.order[i] = (unsigned short)key[i].second;
             }
         }
-        if (x6) WG_LAUNCH((wgrad4_x6_kernel<7, 2, 7>), grid, s, q);
-        else if ((d->flags & PC_WG_CS3) && pack3) WG_LAUNCH((wgrad4_kernel<28, 7, 2, 7, true>), grid, s, q);
+        if (inst == 0) WG_LAUNCH((wgrad4_x6_kernel<7, 2, 7>), grid, s, q);
+        else if (inst == 1) WG_LAUNCH((wgrad4_kernel<28, 7, 2, 7, true>), grid, s, q);
         else WG_LAUNCH((wgrad4_kernel<28, 7, 2, 7, false>), grid, s, q);
         PC_CHECK_LAUNCH("wgrad4_kernel");
         return PC_OK;
@@ -1912,23 +1994,22 @@ static int wgrad_run(const pc_wgrad_desc* d, const float* D, const float* S, flo
         q.chunks_per_split = cdiv(q.nchunks, splitk);
         q.nsplit = cdiv(q.nchunks, q.chunks_per_split);
         q.store = d->splitk == -1;
-        if (dry) { *dry = q.nsplit; return PC_OK; }
+        const int inst = wg_row_inst(geo, row9);
+        if (dry) { dry->nslices = q.nsplit; snprintf(dry->name, sizeof dry->name, "%s", WG_ROW_NAME[inst]); return PC_OK; }
         PC_CHECK_ARG(!wss || q.nsplit <= d->ws_slices, "pc_conv_wgrad: the workspace holds %d slice images, this launch writes %d (pc_wgrad_slices)", d->ws_slices, q.nsplit);
         q.wss = wss;
         const dim3 grid((unsigned)(tiles * q.nsplit * nprob));
-        if (geo.x6) {
-            if (csb64 && bkp == 64) WG_LAUNCH((wgrad3_x6_kernel<64, 64, 64, 2>), grid, s, q);
-            else if (csb64) WG_LAUNCH((wgrad3_x6_kernel<64, 32, 64, 2>), grid, s, q);
-            else if (bkp == 64) WG_LAUNCH((wgrad3_x6_kernel<128, 64, 32, 4>), grid, s, q);
-            else WG_LAUNCH((wgrad3_x6_kernel<128, 32, 32, 4>), grid, s, q);
-            PC_CHECK_LAUNCH("wgrad3_x6_kernel");
-            return PC_OK;
+        switch (inst) {
+            case 0: WG_LAUNCH((wgrad3_x6_kernel<64, 64, 64, 2>), grid, s, q); break;
+            case 1: WG_LAUNCH((wgrad3_x6_kernel<64, 32, 64, 2>), grid, s, q); break;
+            case 2: WG_LAUNCH((wgrad3_x6_kernel<128, 64, 32, 4>), grid, s, q); break;
+            case 3: WG_LAUNCH((wgrad3_x6_kernel<128, 32, 32, 4>), grid, s, q); break;
+            case 4: WG_LAUNCH((wgrad3_kernel<64, 20, 64, 2, 9>), grid, s, q); break;
+            case 5: WG_LAUNCH((wgrad3_kernel<128, 28, 32, 4>), grid, s, q); break;
+            case 6: WG_LAUNCH((wgrad3_kernel<64, 56, 64, 2>), grid, s, q); break;
+            case 7: WG_LAUNCH((wgrad3_kernel<64, 28, 64, 2>), grid, s, q); break;
+            default: WG_LAUNCH((wgrad3_kernel<128, 28, 64, 2>), grid, s, q); break;
         }
-        if (row9) WG_LAUNCH((wgrad3_kernel<64, 20, 64, 2, 9>), grid, s, q);
-        else if (!csb64) WG_LAUNCH((wgrad3_kernel<128, 28, 32, 4>), grid, s, q);
-        else if (small_m && bkp == 56) WG_LAUNCH((wgrad3_kernel<64, 56, 64, 2>), grid, s, q);
-        else if (small_m) WG_LAUNCH((wgrad3_kernel<64, 28, 64, 2>), grid, s, q);
-        else WG_LAUNCH((wgrad3_kernel<128, 28, 64, 2>), grid, s, q);
         PC_CHECK_LAUNCH("wgrad3_kernel");
         return PC_OK;
     }
@@ -1964,7 +2045,8 @@ static int wgrad_run(const pc_wgrad_desc* d, const float* D, const float* S, flo
         kk.nsplit = splitk;
         kk.mt = mt; kk.ntl = ntl;
         nslices = std::max(nslices, splitk);
-        if (dry) return;
+        const int inst = wg_generic_inst(d, small_m, wide);
+        if (dry) { const size_t n = strlen(dry->name); snprintf(dry->name + n, sizeof dry->name - n, "%s%s", n ? "+" : "", WG_GEN_NAME[inst]); return; }
         if (wss && splitk > d->ws_slices) { ws_short = true; return; }
         kk.wss = wss;
         dim3 grid((unsigned)((int64_t)mt * ntl * nb * splitk));
@@ -1993,16 +2075,16 @@ static int wgrad_run(const pc_wgrad_desc* d, const float* D, const float* S, flo
                 else WG_LAUNCH((wgrad_x6_kernel<128, 128, false>), grid, s, kk);
             } else
 #endif
-            if (small_m) WG_LAUNCH((wgrad_x6_kernel<64, 128>), grid, s, kk);
+            if (inst == 0) WG_LAUNCH((wgrad_x6_kernel<64, 128>), grid, s, kk);
             else WG_LAUNCH((wgrad_x6_kernel<128, 128>), grid, s, kk);
-        } else if (small_m && wide) WG_LAUNCH((wgrad_kernel<64, 256, 0, 16>), grid, s, kk);
-        else if (small_m) WG_LAUNCH((wgrad_kernel<64, 128>), grid, s, kk);
-        else if (wide) WG_LAUNCH((wgrad_kernel<128, 256, 0, 16>), grid, s, kk);
+        } else if (inst == 2) WG_LAUNCH((wgrad_kernel<64, 256, 0, 16>), grid, s, kk);
+        else if (inst == 3) WG_LAUNCH((wgrad_kernel<64, 128>), grid, s, kk);
+        else if (inst == 4) WG_LAUNCH((wgrad_kernel<128, 256, 0, 16>), grid, s, kk);
         else WG_LAUNCH((wgrad_kernel<128, 128>), grid, s, kk);
     };
     const WgSplit w = wg_generic_split(d);
     for (int i = 0; i < w.n; ++i) launch(w.lo[i], w.hi[i], w.small_m[i]);
-    if (dry) { *dry = nslices; return PC_OK; }
+    if (dry) { dry->nslices = nslices; return PC_OK; }
     PC_CHECK_ARG(!ws_short, "pc_conv_wgrad: the workspace holds %d slice images, this launch writes %d (pc_wgrad_slices)", d->ws_slices, nslices);
     PC_CHECK_LAUNCH("wgrad_kernel");
     return PC_OK;
@@ -2015,11 +2097,26 @@ extern "C" int pc_conv_wgrad(const pc_wgrad_desc* d, const float* D, const float
 extern "C" int pc_wgrad_uses_x6(const pc_wgrad_desc* d) { return d && wg_uses_x6(d) ? 1 : 0; }
 
 extern "C" int pc_wgrad_slices(const pc_wgrad_desc* d) {
-    int n = 0;
+    WgDry n = {};
     pc_wgrad_desc e;
     if (!d) { pc_set_error("pc_wgrad_slices: null descriptor"); return -1; }
     e = *d; e.ws_slices = 0;
-    return wgrad_run(&e, nullptr, nullptr, nullptr, nullptr, &n) == PC_OK ? n : -1;
+    return wgrad_run(&e, nullptr, nullptr, nullptr, nullptr, &n) == PC_OK ? n.nslices : -1;
+}
+
+// Host-only (no GPU call): the kernel template instance(s) pc_conv_wgrad WOULD launch for this descriptor -- a dry run of the launch code itself.
+//   <kernel><template arguments>[+<second launch>]:k<K slices>:<store|atomic|ws>
+// wgrad4[_x6] = the 7 x 7 stem, wgrad3[_x6]<BM,BKP,CSB,WMW[,KW]> = row segments, wgrad[_x6]<BM,BN[,positions per chunk]> = generic split-K;
+// store = one slice with plain stores (splitk = -1), atomic = fp32 atomics, ws = ordered K-slice images in a workspace (ws_slices > 0)
+extern "C" int pc_wgrad_variant(const pc_wgrad_desc* d, char* buf, int cap) {
+    PC_CHECK_ARG(d && buf && cap > 0, "pc_wgrad_variant: null pointer");
+    WgDry r = {};
+    const int rc = wgrad_run(d, nullptr, nullptr, nullptr, nullptr, &r);
+    if (rc != PC_OK) return rc;
+    PC_CHECK_ARG(d->ws_slices == 0 || r.nslices <= d->ws_slices, "pc_wgrad_variant: the workspace holds %d slice images, this launch writes %d (pc_wgrad_slices)", d->ws_slices, r.nslices);
+    const int n = snprintf(buf, (size_t)cap, "%s:k%d:%s", r.name, r.nslices, d->splitk == -1 ? "store" : (d->ws_slices > 0 ? "ws" : "atomic"));
+    PC_CHECK_ARG(n > 0 && n < cap, "pc_wgrad_variant: the buffer holds %d bytes", cap);
+    return PC_OK;
 }
 
 

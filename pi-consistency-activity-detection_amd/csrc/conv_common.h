@@ -156,3 +156,4 @@ __device__ __forceinline__ void x6_split2(float x0, float x1, uint32_t& h, uint3
 struct X6Tile { int bm, bn, wm, wn; };
 bool pc_x6_eligible(const pc_conv_desc* d);
 X6Tile pc_x6_tile(const pc_conv_desc* d, int groups);
+int pc_x6_variant(const pc_conv_desc* d, int64_t ws_floats, char* buf, int cap);       // the PC_F_X6 half of pc_conv_variant (conv_x6.hip)

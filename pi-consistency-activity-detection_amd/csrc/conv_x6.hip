@@ -415,6 +415,12 @@ __global__ __launch_bounds__(64 * WM * WN, 1) void conv_x6_kernel(const ConvX6 p
     }
 }
 
+// block order with the row tiles fastest: few row tiles over >= 2 MB of weights per column tile
+inline bool x6_mfast(int mtiles_g, int K, int bn) {
+    static const int mf = getenv("PICONS_X6_MFAST") ? atoi(getenv("PICONS_X6_MFAST")) : 1;
+    return mf && mtiles_g <= 8 && mtiles_g > 1 && (long long)K * bn * 6 >= (2ll << 20);
+}
+
 template <int BM, int BN, int WM, int WN>
 int launch_x6(const ConvX6& kx, hipStream_t s) {
     constexpr int OPBYTES = 2 * (BM * BK * 4 + 3 * BN * BK * 2);
@@ -425,8 +431,7 @@ int launch_x6(const ConvX6& kx, hipStream_t s) {
     p.k.ntiles = cdiv(p.k.Co, BN);
     const int tiles = p.k.groups * p.k.mtiles_g * p.k.ntiles;
     if (p.ksplit <= 1 || p.rem <= 0 || !p.ws) { p.full = tiles; p.rem = 0; p.ksplit = 1; }
-    static const int mf = getenv("PICONS_X6_MFAST") ? atoi(getenv("PICONS_X6_MFAST")) : 1;
-    p.mfast = mf && p.k.mtiles_g <= 8 && p.k.mtiles_g > 1 && (long long)p.k.K * BN * 6 >= (2ll << 20);     // few row tiles over >= 2 MB of weights per column tile
+    p.mfast = x6_mfast(p.k.mtiles_g, p.k.K, BN);
     const dim3 grid(p.full + p.rem * p.ksplit), block(64 * WM * WN);
     if (pc_tl_ev_start) hipExtLaunchKernelGGL((conv_x6_kernel<BM, BN, WM, WN>), grid, block, lds, s, pc_tl_ev_start, pc_tl_ev_stop, 0, p);
     else hipLaunchKernelGGL((conv_x6_kernel<BM, BN, WM, WN>), grid, block, lds, s, p);
@@ -459,6 +464,9 @@ inline X6Split x6_split(const pc_conv_desc* d, int groups, const X6Tile& t) {
     r.ws_floats = (long long)rem * ks * t.bm * t.bn + ((rem + 3) / 4) * 4;        // the slices, then one counter per split tile
     return r;
 }
+
+// the tail split runs only when the caller brings a workspace (one too small for it is refused, never a silent unsplit launch)
+inline bool x6_splits(const X6Split& sp, bool have_ws) { return have_ws && sp.ksplit > 1; }
 
 }  // namespace
 
@@ -551,6 +559,23 @@ extern "C" int64_t pc_conv_x6_ws_floats(const pc_conv_desc* d) {
     return x6_split(d, groups, pc_x6_tile(d, groups)).ws_floats;
 }
 
+// the PC_F_X6 half of pc_conv_variant (conv.hip): tile and wave layout of the launch, and the K slices of its tail tiles with a workspace of
+// ws_floats floats (0 = none: no split)
+int pc_x6_variant(const pc_conv_desc* d, int64_t ws_floats, char* buf, int cap) {
+    PC_CHECK_ARG(pc_x6_eligible(d), "pc_conv_variant: the descriptor does not take the bf16-split kernel (Ci=%d ldi=%d ldw=%d flags=%d)", d->Ci, d->ldi, d->ldw, d->flags);
+    const int groups = d->groups > 0 ? d->groups : 1;
+    const X6Tile c = pc_x6_tile(d, groups);
+    const X6Split sp = x6_split(d, groups, c);
+    const bool split = x6_splits(sp, ws_floats > 0);
+    PC_CHECK_ARG(!split || ws_floats >= sp.ws_floats, "pc_conv_variant: the workspace holds %lld floats, this launch needs %lld (pc_conv_x6_ws_floats)",
+                 (long long)ws_floats, (long long)sp.ws_floats);
+    const long long Mg = (long long)(d->N / groups) * d->Tq * d->Hq * d->Wq;
+    const bool mfast = x6_mfast((int)cdiv(Mg, c.bm), d->ntap[0] * d->ntap[1] * d->ntap[2] * d->Ci, c.bn);
+    const int n = snprintf(buf, (size_t)cap, "x6:%dx%d:w%dx%d:ks%d%s", c.bm, c.bn, c.wm, c.wn, split ? sp.ksplit : 1, mfast ? ":mfast" : "");
+    PC_CHECK_ARG(n > 0 && n < cap, "pc_conv_variant: the buffer holds %d bytes", cap);
+    return PC_OK;
+}
+
 extern "C" int pc_conv_fwd_x6(const pc_conv_desc* d, const float* in, const uint16_t* wplanes, int64_t plane_stride, const float* bias,
                               const float* cscale, float* out, float* bnpart, pc_stream s) {
     return pc_conv_fwd_x6_ws(d, in, wplanes, plane_stride, bias, cscale, out, bnpart, nullptr, 0, s);
@@ -597,7 +622,7 @@ extern "C" int pc_conv_fwd_x6_ws(const pc_conv_desc* d, const float* in, const u
     const X6Tile c = pc_x6_tile(d, groups);
     const X6Split sp = x6_split(d, groups, c);
     kx.full = sp.tiles; kx.rem = 0; kx.ksplit = 1; kx.ws = nullptr; kx.ctr = nullptr;
-    if (ws && sp.ksplit > 1) {
+    if (x6_splits(sp, ws != nullptr)) {
         PC_CHECK_ARG(ws_floats >= sp.ws_floats && (uintptr_t)ws % 16 == 0, "pc_conv_fwd_x6_ws: the workspace holds %lld floats, this launch needs %lld (pc_conv_x6_ws_floats)",
                      (long long)ws_floats, (long long)sp.ws_floats);
         kx.full = sp.full; kx.rem = sp.rem; kx.ksplit = sp.ksplit; kx.ws = ws;

@@ -27,6 +27,10 @@ __device__ __forceinline__ void glds16b(dma_rsrc_t rs, unsigned voff, float* l) 
     if (ON) __builtin_amdgcn_raw_ptr_buffer_load_lds(rs, (__attribute__((address_space(3))) void*)l, 16, voff, 0, 0, 0);
 }
 
+// the epilogue stages the block's outputs in LDS and stores them as 16-byte pieces when the output rows allow it, else four-byte stores straight
+// from the accumulators: ONE predicate for the kernel and for the reporter (pc_wino_variant)
+__host__ __device__ inline bool wino_vec_epilogue(int ldo, int Co, uintptr_t out, int scalar_epi) { return !scalar_epi && ldo % 4 == 0 && Co % 4 == 0 && out % 16 == 0; }
+
 struct WinoK {
     const float* in; const float* U; const float* bias; float* out; float* bnpart;
     int N, T, H, W, Ci, ldi, Co, ldo;
@@ -322,7 +326,7 @@ __global__ __launch_bounds__(256, 1) void wino_conv_kernel(const WinoK p) {
     // loop ended with a barrier) and leave as row-contiguous 16-byte stores, 16 per thread -- instead of 64 four-byte stores per thread, each
     // with its own 64-bit address (12 k cycles of a conv112 block's 130 k).  Needs 16-byte aligned channel slices AND whole 4-channel chunks
     // (Co % 4 == 0: a chunk that straddles Co would overwrite the neighbouring slice of a wider tensor); otherwise the scalar path.
-    const bool vec_ok = !(VAR & (8 | 32)) && !p.scalar_epi && p.ldo % 4 == 0 && p.Co % 4 == 0 && ((uintptr_t)p.out % 16 == 0);
+    const bool vec_ok = !(VAR & (8 | 32)) && wino_vec_epilogue(p.ldo, p.Co, (uintptr_t)p.out, p.scalar_epi);
     float* Tst = smem;                                    // [2 BTH * 2 BTW positions][WC channels]
     const int OW2 = 2 * p.BTW;
     float* obase = p.out + ((size_t)n * p.T + t) * plane_out + co;
@@ -483,6 +487,7 @@ static inline int64_t wino_spatial_blocks(const WinoK& k) {
 int pc_wino4_bnpart_rows_impl(const pc_wino_desc* d);
 int pc_wino4_work_impl(const pc_wino_desc* d, double* out);
 int pc_wino4_conv_impl(const pc_wino_desc* d, const float* in, const float* U, const float* bias, float* out, float* bnpart, pc_stream s);
+int pc_wino4_variant_impl(const pc_wino_desc* d, const float* out, char* buf, int cap);
 #define WINO_M_CHECK(d) PC_CHECK_ARG(!(d) || (d)->m == 0 || (d)->m == 2 || (d)->m == 4, "pc_wino: m must be 2 (or 0) or 4, got %d", (d)->m)
 
 extern "C" int64_t pc_wino_u_floats(int O, int I, int KT) {
@@ -523,6 +528,23 @@ extern "C" int pc_wino_work(const pc_wino_desc* d, double* out) {
     out[0] = blocks * taps * 16.0 * WT * WC * k.Ci;                                  // issued: 16 transform-domain GEMMs of 64 x 64 x Ci per tap
     out[1] = (double)k.N * taps * 16.0 * ((double)k.TH * k.TW) * k.Co * k.Ci;        // executed on real tiles / channels
     out[2] = blocks * k.T;                                                          // blocks
+    return PC_OK;
+}
+
+// Host-only (no GPU call): the kernel instance pc_wino_conv WOULD launch for this descriptor and output address (only its alignment counts; NULL =
+// aligned), from the launch's own fill() and the kernels' own epilogue predicate:
+//   wino2:<BTH>x<BTW>|strips:<vec|scalar>        F(2x2, 3x3), tile rectangle of a block or strip mode
+//   wino4:<BTH>x<BTW>:<vec|scalar>               F(4x4, 3x3)
+extern "C" int pc_wino_variant(const pc_wino_desc* d, const float* out, char* buf, int cap) {
+    WINO_M_CHECK(d);
+    PC_CHECK_ARG(buf && cap > 0, "pc_wino_variant: null pointer");
+    if (d && d->m == 4) return pc_wino4_variant_impl(d, out, buf, cap);
+    WinoK k;
+    const int rc = fill(d, k);
+    if (rc != PC_OK) return rc;
+    const char* epi = wino_vec_epilogue(k.ldo, k.Co, (uintptr_t)out, k.scalar_epi) ? "vec" : "scalar";
+    const int n = k.strip ? snprintf(buf, (size_t)cap, "wino2:strips:%s", epi) : snprintf(buf, (size_t)cap, "wino2:%dx%d:%s", k.BTH, k.BTW, epi);
+    PC_CHECK_ARG(n > 0 && n < cap, "pc_wino_variant: the buffer holds %d bytes", cap);
     return PC_OK;
 }
 

@@ -38,6 +38,9 @@ __device__ __forceinline__ void static_for(F&& f) {
     }
 }
 
+// 16-byte stores from the LDS staging image when the output rows allow it, else four-byte stores: ONE predicate for the kernel and pc_wino_variant
+__host__ __device__ inline bool wino4_vec_epilogue(int ldo, int Co, uintptr_t out) { return ldo % 4 == 0 && Co % 4 == 0 && out % 16 == 0; }
+
 struct Wino4K {
     const float* in; const float* U; const float* bias; float* out; float* bnpart;
     int N, T, H, W, Ci, ldi, Co, ldo;
@@ -390,7 +393,7 @@ __global__ __launch_bounds__(256, 1) void wino4_conv_kernel(const Wino4K p) {
     const bool accum = p.flags & PC_F_ACCUM;
     float s1 = 0.f, s2 = 0.f;
     const size_t plane_out = (size_t)p.H * p.W * p.ldo;
-    const bool vec_ok = !(VAR & (8 | 32)) && p.ldo % 4 == 0 && p.Co % 4 == 0 && ((uintptr_t)p.out % 16 == 0);
+    const bool vec_ok = !(VAR & (8 | 32)) && wino4_vec_epilogue(p.ldo, p.Co, (uintptr_t)p.out);
     float* Tst = smem;                                    // [4 BTH rows][2 BTW column pairs][XC channels][2]
     const int OP2 = 2 * p.BTW, rowf = OP2 * XC * 2;        // column pairs per row / floats per row
     const int ntile = p.BTH * p.BTW;
@@ -625,6 +628,15 @@ int pc_wino4_work_impl(const pc_wino_desc* d, double* out) {
     out[0] = blocks * taps * 36.0 * XT * XC * k.Ci;                                  // issued: 36 transform-domain GEMMs of 32 x 64 x Ci per tap
     out[1] = (double)k.N * taps * 36.0 * ((double)k.TH * k.TW) * k.Co * k.Ci;        // executed on real tiles / channels
     out[2] = blocks * k.T;
+    return PC_OK;
+}
+
+int pc_wino4_variant_impl(const pc_wino_desc* d, const float* out, char* buf, int cap) {
+    Wino4K k;
+    const int rc = fill(d, k);
+    if (rc != PC_OK) return rc;
+    const int n = snprintf(buf, (size_t)cap, "wino4:%dx%d:%s", k.BTH, k.BTW, wino4_vec_epilogue(k.ldo, k.Co, (uintptr_t)out) ? "vec" : "scalar");
+    PC_CHECK_ARG(n > 0 && n < cap, "pc_wino_variant: the buffer holds %d bytes", cap);
     return PC_OK;
 }
 

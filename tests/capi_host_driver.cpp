@@ -34,6 +34,35 @@ int main() {
     cd.Ci = cd.ldi = cd.ldw = 4;
     EXPECT(pc_conv_fwd(&cd, nullptr, fp, nullptr, nullptr, fp, nullptr, nullptr) == PC_E_ARG);
     EXPECT(pc_conv_bnpart_rows(&cd) >= 1);
+    {   // variant reporters (host-only): the answer goes into caller memory and never beyond `cap`
+        char name[160], tiny[6];
+        EXPECT(pc_conv_variant(&cd, 0, name, (int)sizeof name) == PC_OK && std::strcmp(name, "conv:glds_tap8:128x64:w2x2:st2") == 0);
+        EXPECT(pc_conv_variant(&cd, 0, tiny, (int)sizeof tiny) == PC_E_ARG && pc_conv_variant(nullptr, 0, name, 160) == PC_E_ARG);
+        pc_conv_desc big = cd;                                   // a 1 x 1 x 1 layer of Mixed_4f at two clips: LDS-DMA with a ring depth; ragged K stays register-staged
+        big.N = 4; big.Hi = big.Wi = big.Hq = big.Wq = big.Ho = big.Wo = 28; big.Ci = big.ldi = big.ldw = 832; big.Co = big.ldo = 128; big.groups = 2;
+        EXPECT(pc_conv_variant(&big, 0, name, (int)sizeof name) == PC_OK && std::strstr(name, "conv:glds:") == name && std::strstr(name, ":st") != nullptr);
+        big.Ci = big.ldi = big.ldw = 528;
+        EXPECT(pc_conv_variant(&big, 0, name, (int)sizeof name) == PC_OK && std::strstr(name, "conv:reg_ragged:") == name);
+        big.Ci = big.ldi = big.ldw = 832; big.flags = PC_F_X6;
+        EXPECT(pc_conv_variant(&big, 0, name, (int)sizeof name) == PC_OK && std::strstr(name, "x6:") == name && std::strstr(name, ":ks1") != nullptr);
+        const long long nws = pc_conv_x6_ws_floats(&big);
+        if (nws > 0) {
+            EXPECT(pc_conv_variant(&big, nws, name, (int)sizeof name) == PC_OK && std::strstr(name, ":ks1") == nullptr);
+            EXPECT(pc_conv_variant(&big, nws - 1, name, (int)sizeof name) == PC_E_ARG);          // as the launch: a short workspace is refused
+        }
+        big.Ci = big.ldi = 24;
+        EXPECT(pc_conv_variant(&big, 0, name, (int)sizeof name) == PC_E_ARG);
+        pc_wino_desc wn;
+        std::memset(&wn, 0, sizeof(wn));
+        wn.N = 4; wn.T = wn.Ti = 2; wn.H = wn.W = 56; wn.Ci = wn.ldi = 64; wn.Co = wn.ldo = 192; wn.KT = 3; wn.ta = 1; wn.tc = -1; wn.tden = 1;
+        EXPECT(pc_wino_variant(&wn, nullptr, name, (int)sizeof name) == PC_OK && std::strstr(name, "wino2:") == name && std::strstr(name, ":vec") != nullptr);
+        EXPECT(pc_wino_variant(&wn, reinterpret_cast<const float*>(static_cast<uintptr_t>(20)), name, (int)sizeof name) == PC_OK && std::strstr(name, ":scalar") != nullptr);      // only the alignment counts
+        wn.m = 4;
+        EXPECT(pc_wino_variant(&wn, nullptr, name, (int)sizeof name) == PC_OK && std::strcmp(name, "wino4:14x2:vec") == 0);
+        EXPECT(pc_wino_variant(&wn, nullptr, tiny, (int)sizeof tiny) == PC_E_ARG);
+        wn.m = 3;
+        EXPECT(pc_wino_variant(&wn, nullptr, name, (int)sizeof name) == PC_E_ARG);
+    }
     pc_wgrad_desc wd;
     std::memset(&wd, 0, sizeof(wd));
     EXPECT(pc_conv_wgrad(&wd, nullptr, nullptr, nullptr, nullptr) == PC_E_ARG);
@@ -57,6 +86,12 @@ int main() {
             EXPECT(pc_wgrad_uses_x6(&w) == ((c.flags & PC_WG_X6) ? 1 : 0));
             double wk[5];
             EXPECT(pc_wgrad_work(&w, 0, c.Cs == 4 ? 3 : 0, wk) == PC_OK && wk[0] >= wk[1] && wk[1] > 0);
+            {   // the variant reporter: a dry run of the launch code that writes its answer into caller memory, never beyond `cap`
+                char name[160], tiny[8];
+                EXPECT(pc_wgrad_variant(&w, name, (int)sizeof name) == PC_OK && std::strstr(name, "wgrad") == name && std::strstr(name, ":atomic") != nullptr);
+                EXPECT(std::strstr(name, (c.flags & PC_WG_X6) && (c.Cs != 4 || (c.flags & PC_WG_CS3)) ? "_x6<" : "<") != nullptr);
+                EXPECT(pc_wgrad_variant(&w, tiny, (int)sizeof tiny) == PC_E_ARG && pc_wgrad_variant(&w, nullptr, 16) == PC_E_ARG);
+            }
             if (ns > 1) {
                 w.ws_slices = ns - 1;                                                   // one image short: refused before any launch
                 EXPECT(pc_conv_wgrad(&w, fp, fp, fp, nullptr) == PC_E_ARG);

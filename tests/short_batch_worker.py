@@ -3,7 +3,8 @@ planned size (the reference's loaders end each epoch on a short batch: main_ucf1
 
     python tests/short_batch_worker.py <case> <verdict.json>
 
-Cases: oracle_bv5 / oracle_jhmdb_bv (short steps against the CPU oracle), equal_large (a short step on a bs-8 engine equals the step
+Cases: oracle_bv5 / oracle_jhmdb_bv (short steps against the CPU oracle), oracle224_<ucf|jhmdb>_<labeled>+<unlabeled> (one short step of a
+bs-8 engine at the product shape, 224 x 224, against the CPU oracle in float32 and float64), equal_large (a short step on a bs-8 engine equals the step
 on a bs-5 engine), mixed (full / short / full / short against fresh engines of the exact size), stager (HostDictStager on short
 float64 dicts equals stage()), refusal (bad minibatches raise ValueError and leave the engine usable), dp (one rank of a two-rank
 gloo group: rank 0 full, rank 1 short).  Writes {"checks": {name: {"ok", "info"}}, "ok"} (dp: <verdict.json>.<rank>); exit 0 only if
@@ -63,10 +64,49 @@ def load_full_state(dst, src):
 
 
 # ---------------------------------------------------------------------------------------------------------------- cases
-def case_oracle(tag):
-    """Short steps against the CPU oracle at the bars of test_step_vs_oracle_small."""
+def oracle_checks(eng, name, tag, bs, nl, nu, ncls, jhmdb, hw, floor, units):
+    """One short step of `eng` against oracle.step.train_step in float32 and float64 on the same clips: scalars 1e-4, logits / masks 1e-3,
+    every gradient per tensor (check_gradients_fp64_anchored with `floor`), the running statistics of `units` 1e-5."""
     from oracle import step as ostep
     from tests.test_step_gpu import check_gradients_fp64_anchored
+    state = synthetic.init_state(47, ncls)
+    eng.load_state(state)
+    lab, unl, perm, drops = synthetic.make_step_inputs_split(nl, nu, num_classes=ncls, hw=hw)
+    eng.stage(lab, unl, perm, drops)
+    eng.forward_backward(EPOCH, RAMP)
+    eng.synchronize()
+    check(name + "_active_plan", eng.active.n == nl + nu and eng.plan.n == bs, [eng.active.n, eng.plan.n])
+    oa = ostep.default_args(dataset="jhmdb" if jhmdb else "ucf101", **AKW)
+    P = ostep.as_torch_params(state)
+    ref = ostep.train_step(P, oa, lab, unl, EPOCH, RAMP, perm, drops)
+    ref["total"].backward()
+    P64 = ostep.as_torch_params(state, dtype=torch.float64)
+    ref64 = ostep.train_step(P64, oa, lab, unl, EPOCH, RAMP, perm, drops, dtype=torch.float64)
+    ref64["total"].backward()
+    got = eng.read_scalars()
+    out, flip, pred = eng.outputs()
+    dl = max(abs(got[k] - float(ref[k])) for k in ("total", "loc", "cls", "cons"))
+    check(name + "_loss", dl <= 1e-4, dl)
+    check(name + "_outputs_shape", tuple(out.shape[:1]) == (nl + nu,) and tuple(pred.shape) == (nl + nu, ncls), list(pred.shape))
+    for k, g in (("output", out), ("flip_op", flip), ("predicted_action", pred)):
+        d = (g.cpu() - ref[k]).abs().max().item()
+        check("%s_%s" % (name, k), d <= 1e-3, d)
+    try:
+        check_gradients_fp64_anchored(eng, P, P64, "short_%s_%s" % (tag, name), floor=floor)
+        check(name + "_gradients_fp64_anchored", True)
+    except AssertionError as e:
+        check(name + "_gradients_fp64_anchored", False, str(e)[:800])
+    worst = 0.0
+    for pre, _ci, co, _k, _s in units:
+        for nm in ("running_mean", "running_var"):
+            key = pre + ".bn." + nm
+            o = eng.plan.roff[key]
+            worst = max(worst, (eng.R[o:o + co].cpu() - P[key]).abs().max().item())
+    check(name + "_bn_running_stats", worst <= 1e-5, worst)
+
+
+def case_oracle(tag):
+    """Short steps against the CPU oracle at the bars of test_step_vs_oracle_small."""
     jhmdb = tag == "jhmdb_bv"
     ncls = 21 if jhmdb else 24
     hw = 112
@@ -75,45 +115,29 @@ def case_oracle(tag):
         name = "bs%d_%d+%d" % (bs, nl, nu)
         if bs not in engines:
             engines[bs] = engine(bs, hw, ncls, jhmdb)
-        eng = engines[bs]
-        state = synthetic.init_state(47, ncls)
-        eng.load_state(state)
-        lab, unl, perm, drops = synthetic.make_step_inputs_split(nl, nu, num_classes=ncls, hw=hw)
-        eng.stage(lab, unl, perm, drops)
-        eng.forward_backward(EPOCH, RAMP)
-        eng.synchronize()
-        check(name + "_active_plan", eng.active.n == nl + nu and eng.plan.n == bs, [eng.active.n, eng.plan.n])
-        oa = ostep.default_args(dataset="jhmdb" if jhmdb else "ucf101", **AKW)
-        P = ostep.as_torch_params(state)
-        ref = ostep.train_step(P, oa, lab, unl, EPOCH, RAMP, perm, drops)
-        ref["total"].backward()
-        P64 = ostep.as_torch_params(state, dtype=torch.float64)
-        ref64 = ostep.train_step(P64, oa, lab, unl, EPOCH, RAMP, perm, drops, dtype=torch.float64)
-        ref64["total"].backward()
-        got = eng.read_scalars()
-        out, flip, pred = eng.outputs()
-        dl = max(abs(got[k] - float(ref[k])) for k in ("total", "loc", "cls", "cons"))
-        check(name + "_loss", dl <= 1e-4, dl)
-        check(name + "_outputs_shape", tuple(out.shape[:1]) == (nl + nu,) and tuple(pred.shape) == (nl + nu, ncls), list(pred.shape))
-        for k, g in (("output", out), ("flip_op", flip), ("predicted_action", pred)):
-            d = (g.cpu() - ref[k]).abs().max().item()
-            check("%s_%s" % (name, k), d <= 1e-3, d)
         # per-tensor floor: 2 % on the bs-6 engine's five-clip plan, as test_step_vs_oracle_other_batch_and_frame_sizes allows off the
         # default sizes (a pre-activation within fp32 rounding of zero flips its ReLU mask against the fp64 run and moves one small
         # tensor's gradient by ~1 %: upsample1.bias, |g| 3e-5, in the JHMDB case); the whole-gradient bar is unchanged
-        floor = 5e-3 if bs == 4 else 2e-2
-        try:
-            check_gradients_fp64_anchored(eng, P, P64, "short_%s_%s" % (tag, name), floor=floor)
-            check(name + "_gradients_fp64_anchored", True)
-        except AssertionError as e:
-            check(name + "_gradients_fp64_anchored", False, str(e)[:800])
-        worst = 0.0
-        for pre, _ci, co, _k, _s in spec.trunk_units()[:6] + spec.trunk_units()[-3:]:
-            for nm in ("running_mean", "running_var"):
-                key = pre + ".bn." + nm
-                o = eng.plan.roff[key]
-                worst = max(worst, (eng.R[o:o + co].cpu() - P[key]).abs().max().item())
-        check(name + "_bn_running_stats", worst <= 1e-5, worst)
+        oracle_checks(engines[bs], name, tag, bs, nl, nu, ncls, jhmdb, hw, 5e-3 if bs == 4 else 2e-2, spec.trunk_units()[:6] + spec.trunk_units()[-3:])
+
+
+def case_oracle224(tag):
+    """ONE short step of the product engine (bs 8, 8 x 224 x 224, four lanes) against the CPU oracle, at the bars of
+    test_step_bs8_full_size_vs_oracle: every m = 3..7 runs kernel template instances that neither m = 2 nor m = 8 selects
+    (tests/variant_cases.py), and this is where they meet the step's own bars.  tag: <ucf|jhmdb>_<labeled>+<unlabeled>."""
+    # Per-tensor floor: check_gradients_fp64_anchored's default 5e-3, except 4+3 -- there ONE channel of Mixed_4f.b2a takes a discrete flip against
+    # the float64 run (a ReLU mask at a pre-activation within fp32 rounding of zero): tools/probe_bs_grads.py 4+3 shows channel 26 of its
+    # BatchNorm bias gradient carrying 77 % of that tensor's squared error (1.9e-5 on 9e-4, the other channels at 1e-6) and every one of the
+    # conv weight's worst elements in row 26, identically with the fp32 MFMA kernels (PICONS_SPLIT=0), so no kernel variant makes it
+    # (profiles/short_4+3_relu_flip.txt; rel-L2 6.7e-3 and 8.2e-3 against the fp32 oracle's own 1.5e-3 and 1.6e-3).  It gets the 2e-2 that
+    # test_step_vs_oracle_other_batch_and_frame_sizes grants such a flip; the whole-gradient bar is unchanged.
+    floor = {"ucf_4+3": 2e-2}.get(tag, 5e-3)
+    ds, split = tag.split("_")
+    nl, nu = (int(v) for v in split.split("+"))
+    jhmdb = ds == "jhmdb"
+    ncls = 21 if jhmdb else 24
+    eng = engine(8, 224, ncls, jhmdb)
+    oracle_checks(eng, "bs8_%d+%d" % (nl, nu), "224_" + tag, 8, nl, nu, ncls, jhmdb, 224, floor, spec.trunk_units()[:4] + spec.trunk_units()[-3:])
 
 
 def case_equal_large():
@@ -252,7 +276,9 @@ def case_dp(out_path):
 def main():
     case, out = sys.argv[1], sys.argv[2]
     torch.set_num_threads(min(os.cpu_count() or 1, 16))
-    if case.startswith("oracle_"):
+    if case.startswith("oracle224_"):
+        case_oracle224(case[len("oracle224_"):])
+    elif case.startswith("oracle_"):
         case_oracle(case[len("oracle_"):])
     elif case == "dp":
         out = case_dp(out)

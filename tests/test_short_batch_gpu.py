@@ -41,6 +41,22 @@ def test_short_step(tmp_path, case, limit):
     _verdict(out, p.stdout, p.returncode)
 
 
+# the product engine (bs 8, 8 x 224 x 224) on every short size m = 3..7 against the oracle: labeled + unlabeled clips; UCF-101 for all five sizes
+# (m = 5 both ways round), JHMDB for one odd m.  One process and time limit each.
+ORACLE_224 = ["ucf_2+1", "ucf_2+2", "ucf_3+2", "ucf_1+4", "ucf_3+3", "ucf_4+3", "jhmdb_3+2"]
+
+
+@pytest.mark.parametrize("tag", ORACLE_224)
+def test_short_step_at_the_product_shape_vs_oracle(tmp_path, tag):
+    """tests/short_batch_worker.py case_oracle224: scalars 1e-4, logits / masks 1e-3, check_gradients_fp64_anchored with its default floor,
+    running statistics 1e-5 -- the bars of test_step_bs8_full_size_vs_oracle (4+3: a 2e-2 floor for one shown ReLU-mask flip, see the worker)."""
+    case = "oracle224_" + tag
+    out = str(tmp_path / case)
+    p = subprocess.run([sys.executable, WORKER, case, out], env=_env(), cwd=ROOT, stdout=subprocess.PIPE, stderr=subprocess.STDOUT,
+                       text=True, timeout=900)
+    _verdict(out, p.stdout, p.returncode)
+
+
 def _free_port():
     s = socket.socket()
     s.bind(("127.0.0.1", 0))
