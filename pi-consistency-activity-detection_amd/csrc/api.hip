@@ -192,8 +192,6 @@ static hipEvent_t take_event() {
     return e;
 }
 
-static const bool g_no_ext_events = getenv("PICONS_TIMED_RECORD") && atoi(getenv("PICONS_TIMED_RECORD"));   // 1: hipEventRecord pairs for conv ops too
-
 static int run_list(const pc_op* ops, int n, const pc_stream* lanes, int nlanes, int kind, float* ms, int* count) {
     if (!ops && n > 0) { pc_set_error("pc_run_ops: null ops"); return PC_E_ARG; }
     if (nlanes < 1 || nlanes > PC_MAX_LANES || !lanes) { pc_set_error("pc_run_ops: nlanes=%d (1..%d)", nlanes, PC_MAX_LANES); return PC_E_ARG; }
@@ -250,7 +248,7 @@ static int run_list(const pc_op* ops, int n, const pc_stream* lanes, int nlanes,
         // a conv op is exactly one kernel: its event pair rides in the dispatch itself (no extra packets on the stream);
         // any other kind is bracketed by recorded events.  (A weight-gradient op is one kernel too, except the direct PrimaryCaps form's
         // two row ranges, where the pair brackets the last of the two launches.)
-        const bool ext = t && (op.kind == PC_OP_CONV || op.kind == PC_OP_CONV_X6 || op.kind == PC_OP_WINO_CONV || op.kind == PC_OP_WGRAD) && !g_no_ext_events;
+        const bool ext = t && (op.kind == PC_OP_CONV || op.kind == PC_OP_CONV_X6 || op.kind == PC_OP_WINO_CONV || op.kind == PC_OP_WGRAD);
         if (ext) { pc_tl_ev_start = ev[2 * j]; pc_tl_ev_stop = ev[2 * j + 1]; }
         else if (t) (void)hipEventRecord(ev[2 * j], (hipStream_t)s);
         rc = run_one(op, s);
@@ -328,20 +326,15 @@ extern "C" int pc_run_ops_timed_collect(float* ms, int* count) {
     float total = 0.f;
     const int pairs = (int)g_pending.size() / 2;
     if (pairs) (void)hipEventSynchronize(g_pending.back());
-    static const char* dump = getenv("PICONS_TIMED_DUMP");       // diagnostics: one line per collected pair (ms) appended to this file
-    FILE* df = dump ? fopen(dump, "a") : nullptr;
-    if (df) fprintf(df, "# collect %d pairs\n", pairs);
     for (int i = 0; i < pairs; ++i) {
         float e = 0.f;
         (void)hipEventSynchronize(g_pending[2 * i + 1]);
         (void)hipEventElapsedTime(&e, g_pending[2 * i], g_pending[2 * i + 1]);
-        if (df) fprintf(df, "%d %.4f\n", i, e);
         total += e;
         g_ev_pool.push_back(g_pending[2 * i]);
         g_ev_pool.push_back(g_pending[2 * i + 1]);
     }
     g_pending.clear();
-    if (df) fclose(df);
     if (ms) *ms = total;
     if (count) *count = pairs;
     return PC_OK;

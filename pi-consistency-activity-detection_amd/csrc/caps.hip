@@ -415,7 +415,8 @@ __global__ __launch_bounds__(64 * BWD_WAVES * BWD_GROUPS) void em_bwd_kernel(con
             for (int e = tid; e < (int)(sizeof(EmSaved) / 16); e += NT) dstp[e] = src[e];
         }
         __syncthreads();
-        if (!state) em_forward<BW>(st, WT, beta_u, beta_a, C, tid, red);
+        // a call, not inlined: the kernel's registers and schedule are those measured with the forward pass out of line
+        if (!state) [[clang::noinline]] em_forward<BW>(st, WT, beta_u, beta_a, C, tid, red);
         // ---- seeds
         const float* dop = dout + pos * (C * 17);
         for (int e = tid; e < 3 * MAXC * 16; e += NT) { (&bs->dmu[0][0][0])[e] = 0.f; (&bs->ds2[0][0][0])[e] = 0.f; }
@@ -786,9 +787,6 @@ __global__ __launch_bounds__(256) void tapsum_bwd_kernel(const float* __restrict
 }
 
 inline int em_bwd_blocks(int npos, int groups = BWD_GROUPS_MAX) { const int b = (npos + groups - 1) / groups; return b < 256 ? b : 256; }
-// PICONS_EM_GROUPS: teams per block of the EM backward.  2 = 154 KB of LDS per block: nothing else fits on the CU while it runs;
-// 1 = 102 KB: one 128x64 GEMM block of another lane (49 KB) can share the CU, so the skip-conv / weight-gradient lanes keep moving.
-inline int em_groups() { static const int g = getenv("PICONS_EM_GROUPS") ? atoi(getenv("PICONS_EM_GROUPS")) : 2; return g == 1 ? 1 : 2; }
 constexpr size_t EM_PART = NB * MAXC * 16 + MAXC * 16 + 32;
 
 }  // namespace
@@ -821,13 +819,13 @@ extern "C" int pc_em_routing_bwd(const float* x, const float* W, const float* be
     PC_CHECK_ARG(x && W && beta_u && beta_a && dout && dx && dW && dbeta_u && dbeta_a && ws, "pc_em_routing_bwd: null");
     PC_CHECK_ARG(!state || (uintptr_t)state % 16 == 0, "pc_em_routing_bwd: state alignment");
     PC_CHECK_ARG(B == NB && C >= 1 && C <= MAXC, "pc_em_routing_bwd: B must be 32 and C <= 24");
-    const int BWD_GROUPS = em_groups();
+    // two teams per block of the EM backward: 154 KB of LDS per block, nothing else fits on the CU while it runs.  One team (102 KB, so that a
+    // 49 KB 128x64 GEMM block of another lane could share the CU) measured slower.
+    constexpr int BWD_GROUPS = BWD_GROUPS_MAX;
     const size_t lds = (size_t)NB * MAXC * 16 * 4 + BWD_GROUPS * ((size_t)EM_SMALL * 4 + sizeof(FwdState) + sizeof(BwdState) + BWD_WAVES * MAXC * 16 * 4);
-    PC_SET_LDS_ONCE(em_bwd_kernel<1>, lds, "em_bwd_kernel<1>");
-    PC_SET_LDS_ONCE(em_bwd_kernel<2>, lds, "em_bwd_kernel<2>");
+    PC_SET_LDS_ONCE(em_bwd_kernel<BWD_GROUPS>, lds, "em_bwd_kernel<2>");
     const int nblk = em_bwd_blocks(npos, BWD_GROUPS);
-    if (BWD_GROUPS == 1) hipLaunchKernelGGL(em_bwd_kernel<1>, dim3(nblk), dim3(64 * BWD_WAVES), lds, s, x, W, beta_u, beta_a, dout, npos, C, dx, ws, (const EmSaved*)state);
-    else hipLaunchKernelGGL(em_bwd_kernel<2>, dim3(nblk), dim3(64 * BWD_WAVES * 2), lds, s, x, W, beta_u, beta_a, dout, npos, C, dx, ws, (const EmSaved*)state);
+    hipLaunchKernelGGL(em_bwd_kernel<BWD_GROUPS>, dim3(nblk), dim3(64 * BWD_WAVES * BWD_GROUPS), lds, s, x, W, beta_u, beta_a, dout, npos, C, dx, ws, (const EmSaved*)state);
     PC_CHECK_LAUNCH("em_bwd");
     hipLaunchKernelGGL(em_reduce_kernel, dim3(cdiv(NB * C * 16 + C * 17, RED_E)), dim3(256), 0, s, ws, nblk * BWD_GROUPS, C, dW, dbeta_u, dbeta_a);
     PC_CHECK_LAUNCH("em_reduce");

@@ -385,7 +385,6 @@ __global__ __launch_bounds__(256, 2) void conv_gemm_glds_kernel(const ConvK p) {
             for (int i = 0; i < TM; ++i) af[i] = *(const f32x4*)(a + aoff[i] + ((q ^ asw[i]) << 2));
 #pragma unroll
             for (int j = 0; j < TN; ++j) bf[j] = *(const f32x4*)(b + boff[j] + ((q ^ bsw[j]) << 2));
-            if (VAR & 1) __builtin_amdgcn_s_setprio(1);
             // TAP4 with PC_F_CI3 (VAR bit 5): a 16-byte slot is one tap's (c0, c1, c2, padding) -- the padding channel's MFMA is not issued
             constexpr int NE = (TAP4 && (VAR & 32)) ? 3 : 4;
 #pragma unroll
@@ -395,8 +394,9 @@ __global__ __launch_bounds__(256, 2) void conv_gemm_glds_kernel(const ConvK p) {
 #pragma unroll
                     for (int j = 0; j < TN; ++j)
                         acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(af[i][e], bf[j][e], acc[i][j], 0, 0, 0);
-            if (VAR & 1) __builtin_amdgcn_s_setprio(0);
-            if (ST == 2 && (VAR & 2) && ks == 0 && c + 1 < nchunks) fetch(buf ^ 1);   // issue the next tile's DMA behind the first MFMA group
+            // VAR bit 1 (next tile's DMA issued behind the first MFMA group instead of before the chunk) is set by no instance.
+            // The line stays because the surviving instances compile to different instructions without this second call of fetch.
+            if (ST == 2 && (VAR & 2) && ks == 0 && c + 1 < nchunks) fetch(buf ^ 1);
         }
     };
     if constexpr (ST == 2) {
@@ -500,48 +500,34 @@ int launch_conv_glds_v(const ConvK& k, hipStream_t s) {
 enum ConvFamily { CF_GLDS, CF_GLDS_TAP8, CF_REG_FAST, CF_REG_RAGGED };
 struct ConvChoice { ConvFamily fam; int var; };          // var: VAR of conv_gemm_glds_kernel (ring depth = 2 + ((var >> 3) & 3), bit 5 = PC_F_CI3)
 
-// PICONS_CONV_VARIANT (tuning, tools/ablate_conv.py): bit 0 = s_setprio around the MFMA groups, bit 1 = issue the next
-// tile's LDS-DMA after the first MFMA group instead of before it.  Same results in every variant.
+// LDS-DMA ring depth, as VAR of conv_gemm_glds_kernel (8 = 3 stages, 0 = the double buffer): 3 stages for launches of at most one block
+// per CU (the 196-block 28x28 layers: 10-25 % faster -- nothing else on the CU covers the latency of a tile fetch that misses L2) where
+// two blocks of it still fit a CU, the double buffer otherwise (a ring costs full launches 5-8 %).
 inline int conv_glds_var(int bm, int bn, int groups, int Mg, int Co) {
-    static const int var = getenv("PICONS_CONV_VARIANT") ? atoi(getenv("PICONS_CONV_VARIANT")) : CONV_DEFAULT_VARIANT;
-    // LDS-DMA ring depth.  Default: 3 stages for launches of at most one block per CU (the 196-block 28x28 layers: 10-25 % faster --
-    // nothing else on the CU covers the latency of a tile fetch that misses L2), the double buffer otherwise (a ring costs full
-    // launches 5-8 %).  PICONS_CONV_STAGES=2|3|4 forces a depth where two blocks of it still fit a CU.
-    static const int stages = getenv("PICONS_CONV_STAGES") ? atoi(getenv("PICONS_CONV_STAGES")) : 0;
     if (bm * bn <= 128 * 64) {
         const size_t per_stage = (size_t)(bm + bn) * BK * sizeof(float);
         const long long grid = (long long)groups * cdiv(Mg, bm) * cdiv(Co, bn);
-        const int want = stages ? stages : (grid <= 256 ? 3 : 2);
-        if (want == 4 && 4 * per_stage <= 72 * 1024) return 16;
-        if (want >= 3 && 3 * per_stage <= 76 * 1024) return 8;
+        if (grid <= 256 && 3 * per_stage <= 76 * 1024) return 8;
     }
-    return var & 3;
+    return 0;
 }
 
+// k.in == nullptr (the host-only callers, pc_conv_variant / pc_conv_work, have no pointer) stands for a 16-byte aligned input
 inline ConvChoice conv_choice(const ConvK& k, int bm, int bn) {
-    static const int no_glds = getenv("PICONS_CONV_NO_GLDS") ? atoi(getenv("PICONS_CONV_NO_GLDS")) : 0;
-    static const int no_tap4 = getenv("PICONS_CONV_NO_TAP4") ? atoi(getenv("PICONS_CONV_NO_TAP4")) : 0;
     const bool fast = k.Ci % BK == 0;
     const bool small_taps = k.ntap[0] <= 10 && k.ntap[1] <= 10 && k.ntap[2] <= 10;
     if (bm == 128 && bn == 64)
-        if (k.Ci == 4 && !no_glds && !no_tap4 && small_taps && ((uintptr_t)k.in % 16 == 0) && k.ldi % 4 == 0 && k.ldw % 4 == 0)
+        if (k.Ci == 4 && small_taps && ((uintptr_t)k.in % 16 == 0) && k.ldi % 4 == 0 && k.ldw % 4 == 0)
             return {CF_GLDS_TAP8, (k.flags & PC_F_CI3) ? (4 | 32) : 4};
-    if (fast && !no_glds && small_taps && ((uintptr_t)k.in % 16 == 0) && k.ldi % 4 == 0) return {CF_GLDS, conv_glds_var(bm, bn, k.groups, k.Mg, k.Co)};
+    if (fast && small_taps && ((uintptr_t)k.in % 16 == 0) && k.ldi % 4 == 0) return {CF_GLDS, conv_glds_var(bm, bn, k.groups, k.Mg, k.Co)};
     return {fast ? CF_REG_FAST : CF_REG_RAGGED, 0};
 }
 
 template <int BM, int BN, int WM, int WN>
 int launch_conv_glds(const ConvK& k, hipStream_t s, int var) {
-    if constexpr (BM * BN <= 128 * 64) {
-        if (var == 16) return launch_conv_glds_v<BM, BN, WM, WN, 16>(k, s);
+    if constexpr (BM * BN <= 128 * 64)
         if (var == 8) return launch_conv_glds_v<BM, BN, WM, WN, 8>(k, s);
-    }
-    switch (var & 3) {
-        case 1: return launch_conv_glds_v<BM, BN, WM, WN, 1>(k, s);
-        case 2: return launch_conv_glds_v<BM, BN, WM, WN, 2>(k, s);
-        case 3: return launch_conv_glds_v<BM, BN, WM, WN, 3>(k, s);
-        default: return launch_conv_glds_v<BM, BN, WM, WN, 0>(k, s);
-    }
+    return launch_conv_glds_v<BM, BN, WM, WN, 0>(k, s);
 }
 
 template <int BM, int BN, int WM, int WN, bool FAST>
@@ -617,11 +603,6 @@ inline TileCfg choose_tile(int Mg, int groups, int Co, int Ci) {
 inline TileCfg launch_tile(const pc_conv_desc* d, int groups) {
     const int64_t Mg = (int64_t)(d->N / groups) * d->Tq * d->Hq * d->Wq;
     TileCfg c = choose_tile((int)Mg, groups, d->Co, d->Ci);
-    static const char* force = getenv("PICONS_CONV_TILE");      // diagnostic: "bm,bn" for grouped launches without BN partials
-    if (force && groups > 2 && !(d->flags & PC_F_BNPART)) {
-        int bm = 0, bn = 0;
-        if (sscanf(force, "%d,%d", &bm, &bn) == 2) { c.bm = bm; c.bn = bn; c.wm = (bm == 64 && bn == 128) ? 1 : (bn == 32 ? 4 : 2); }
-    }
     if (d->flags & PC_F_NFAST) {
         // n-fastest rows: a tile should hold whole groups of N samples of consecutive w so its tap box is tight;
         // when Wq*N is not a multiple of 128 use 64-row tiles (28 w x 16 samples = 7 tiles of 64, none straddles a row)
@@ -640,6 +621,15 @@ inline ConvInst conv_inst(const pc_conv_desc* d, int groups) {
     if (c.bm == 128 && c.bn == 64) return {128, 64, 2, 2};
     if (c.bm == 64 && c.bn == 64) return {64, 64, 2, 2};
     return {128, 32, 4, 1};
+}
+
+// conv_choice's answer for a descriptor alone (the host-only reporters: no operand pointers, so an aligned input is assumed)
+inline ConvChoice conv_choice_desc(const pc_conv_desc* d, int groups, int bm, int bn) {
+    ConvK k = {};
+    k.Ci = d->Ci; k.ldi = d->ldi; k.ldw = d->ldw; k.Co = d->Co; k.flags = d->flags; k.groups = groups;
+    k.Mg = (int)((int64_t)(d->N / groups) * d->Tq * d->Hq * d->Wq);
+    for (int i = 0; i < 3; ++i) k.ntap[i] = d->ntap[i];
+    return conv_choice(k, bm, bn);
 }
 
 }  // namespace
@@ -661,11 +651,10 @@ extern "C" int pc_conv_work(const pc_conv_desc* d, int ci_real, int co_real, dou
     if (x6) { const X6Tile t = pc_x6_tile(d, groups); c.bm = t.bm; c.bn = t.bn; c.wm = t.wm; }
     if (ci_real <= 0) ci_real = d->Ci;
     if (co_real <= 0) co_real = d->Co;
-    const bool small_taps = d->ntap[0] <= 10 && d->ntap[1] <= 10 && d->ntap[2] <= 10;
-    static const int no_glds = getenv("PICONS_CONV_NO_GLDS") ? atoi(getenv("PICONS_CONV_NO_GLDS")) : 0;
-    static const int no_tap4 = getenv("PICONS_CONV_NO_TAP4") ? atoi(getenv("PICONS_CONV_NO_TAP4")) : 0;
-    const bool tap4 = !x6 && c.bm == 128 && c.bn == 64 && d->Ci == 4 && !no_glds && !no_tap4 && small_taps;
-    const bool glds = x6 || tap4 || (d->Ci % BK == 0 && !no_glds && small_taps);
+    // the kernel family is the launch's own decision; the accounting has no input pointer, which conv_choice takes for an aligned one
+    const ConvFamily fam = x6 ? CF_GLDS : conv_choice_desc(d, groups, c.bm, c.bn).fam;
+    const bool tap4 = fam == CF_GLDS_TAP8;
+    const bool glds = fam == CF_GLDS || tap4;
     const int64_t mtiles = cdiv(Mg, c.bm), ntiles = cdiv(d->Co, c.bn);
     const int ng = d->N / groups;
     const int I[3] = {d->Ti, d->Hi, d->Wi};
@@ -754,8 +743,7 @@ static int pc_conv_fwd_g(const pc_conv_desc* d, int groups, const float* in, con
     const int64_t M = (int64_t)d->N * d->Tq * d->Hq * d->Wq;
     PC_CHECK_ARG(M > 0 && M < (1ll << 31) && (int64_t)d->N * d->To * d->Ho * d->Wo < (1ll << 31) && (int64_t)d->N * d->Ti * d->Hi * d->Wi < (1ll << 31), "pc_conv_fwd: position count out of range");
     k.M = (int)M; k.groups = groups; k.Mg = (int)(M / groups);
-    static const int scalar_epi = getenv("PICONS_CONV_SCALAR_EPI") ? atoi(getenv("PICONS_CONV_SCALAR_EPI")) : 0;
-    k.act = d->act; k.flags = (d->flags & ~F_SCALAR_EPI) | (scalar_epi ? F_SCALAR_EPI : 0); k.act_c0 = d->act_c0; k.wgstride = d->wgstride; k.bgstride = d->bgstride;
+    k.act = d->act; k.flags = d->flags & ~F_SCALAR_EPI; k.act_c0 = d->act_c0; k.wgstride = d->wgstride; k.bgstride = d->bgstride;
     const ConvInst c = conv_inst(d, groups);
     if (c.bm == 64 && c.bn == 128) return launch_conv<64, 128, 1, 4>(k, s);
     if (c.bm == 128 && c.bn == 128) return launch_conv<128, 128, 2, 2>(k, s);
@@ -781,11 +769,7 @@ extern "C" int pc_conv_variant(const pc_conv_desc* d, int64_t ws_floats, char* b
     if (d->flags & PC_F_X6) return pc_x6_variant(d, ws_floats, buf, cap);
     PC_CHECK_ARG(d->Ci % 4 == 0 && d->ldi % 4 == 0 && d->ldw % 4 == 0, "pc_conv_variant: Ci/ldi/ldw must be multiples of 4 (Ci=%d ldi=%d ldw=%d)", d->Ci, d->ldi, d->ldw);
     const ConvInst t = conv_inst(d, groups);
-    ConvK k = {};
-    k.Ci = d->Ci; k.ldi = d->ldi; k.ldw = d->ldw; k.Co = d->Co; k.flags = d->flags; k.groups = groups;
-    k.Mg = (int)((int64_t)(d->N / groups) * d->Tq * d->Hq * d->Wq);
-    for (int i = 0; i < 3; ++i) k.ntap[i] = d->ntap[i];
-    const ConvChoice c = conv_choice(k, t.bm, t.bn);
+    const ConvChoice c = conv_choice_desc(d, groups, t.bm, t.bn);
     static const char* const fam[] = {"glds", "glds_tap8", "reg_fast", "reg_ragged"};
     int n = snprintf(buf, (size_t)cap, "conv:%s:%dx%d:w%dx%d", fam[c.fam], t.bm, t.bn, t.wm, t.wn);
     if (n > 0 && n < cap && (c.fam == CF_GLDS || c.fam == CF_GLDS_TAP8)) n += snprintf(buf + n, (size_t)(cap - n), ":st%d%s", 2 + ((c.var >> 3) & 3), (c.var & 32) ? ":ci3" : "");
@@ -1691,8 +1675,7 @@ __global__ __launch_bounds__(256, 2) void wgrad4_x6_kernel(const Wg4K p) {
 }
 
 // Which kernel family pc_conv_wgrad gives a problem to -- ONE classification for pc_conv_wgrad, pc_conv_wgrad_multi and the host-side
-// work accounting (pc_wgrad_work), so the A/B switches mean the same everywhere and the fp32 atomic sum order the goldens were
-// made with cannot drift between copies of the predicates.
+// work accounting (pc_wgrad_work), so the fp32 atomic sum order the goldens were made with cannot drift between copies of the predicates.
 enum WgRoute { WG_STEM, WG_ROW3, WG_ROW9, WG_GENERIC };
 #ifdef PICONS_DIAG
 inline bool wg_ablate() { static const bool a = getenv("PICONS_WGRAD_ABLATE") != nullptr; return a; }
@@ -1700,9 +1683,7 @@ inline bool wg_ablate() { static const bool a = getenv("PICONS_WGRAD_ABLATE") !=
 constexpr bool wg_ablate() { return false; }
 #endif
 inline WgRoute wg_route(const pc_wgrad_desc* d) {
-    static const int s4_env = getenv("PICONS_WGRAD_STEM") ? atoi(getenv("PICONS_WGRAD_STEM")) : 1;
-    static const int row_env = getenv("PICONS_WGRAD_ROW") ? atoi(getenv("PICONS_WGRAD_ROW")) : 1;
-    if (s4_env && d->Cs == 4 && d->lds % 4 == 0 && d->KW == 7 && d->ntap[2] == 7 && d->wk0[2] == 0 && d->istr[2] == 2 && d->ntap[1] == 7 &&
+    if (d->Cs == 4 && d->lds % 4 == 0 && d->KW == 7 && d->ntap[2] == 7 && d->wk0[2] == 0 && d->istr[2] == 2 && d->ntap[1] == 7 &&
         d->ntap[0] <= 10 && d->istep[0] == 1 && d->istep[1] == 1 && d->istep[2] == 1 && d->Td == 0 && d->nbatch <= 1 && d->splitk >= 0 &&
         d->Wq % 28 == 0 && !wg_ablate())
         return WG_STEM;
@@ -1710,31 +1691,33 @@ inline WgRoute wg_route(const pc_wgrad_desc* d) {
     const int padw = -d->ioff0[2], nprob = d->nbatch > 1 ? d->nbatch : 1;
     const bool row3 = d->KW == 3 && padw == 1 && d->Wq == d->Ws && (csb64 || csb32) && d->Ws % 28 == 0 && nprob == 1 && d->splitk >= 0;
     const bool row9 = d->KW == 9 && padw == 0 && d->Wq == d->Ws - 8 && d->Wq == 20 && csb64 && d->Tq == 1 && d->Hq == 1;   // spectral forms
-    if (row_env && !wg_ablate() && d->Td == 0 && d->ntap[2] == d->KW && d->wk0[2] == 0 && d->istr[2] == 1 && d->istep[0] == 1 && d->istep[1] == 1 &&
+    if (!wg_ablate() && d->Td == 0 && d->ntap[2] == d->KW && d->wk0[2] == 0 && d->istr[2] == 1 && d->istep[0] == 1 && d->istep[1] == 1 &&
         d->istep[2] == 1 && (row3 || row9))
         return row9 ? WG_ROW9 : WG_ROW3;
     return WG_GENERIC;
 }
-// the stem's weight gradient on the bf16 matrix cores (wgrad4_x6_kernel): asked for (PC_WG_X6) and the 4th source channel is padding (PC_WG_CS3:
-// the kernel packs the 3 real channels of the 7 x 7 taps into five accumulators)
-inline bool wg_stem_x6(const pc_wgrad_desc* d) {
-    static const int pack3 = getenv("PICONS_WGRAD_STEM_PACK3") ? atoi(getenv("PICONS_WGRAD_STEM_PACK3")) : 1;
-    static const int x6env = getenv("PICONS_WGRAD_STEM_X6") ? atoi(getenv("PICONS_WGRAD_STEM_X6")) : 1;
-    return x6env && pack3 && (d->flags & PC_WG_X6) && (d->flags & PC_WG_CS3) && wg_route(d) == WG_STEM;
+// Which kernel template instance a problem's launch takes, per route: ONE choice for the launch (wgrad_run), the reporter (pc_wgrad_variant)
+// and the accounting (pc_wgrad_work).  The index selects the launch in wgrad_run's switches and the name in these tables.
+// The stem (WG_STEM problems): the 4th source channel is padding (PC_WG_CS3) -> the 3 real channels of the 7 x 7 taps are packed into five
+// accumulators, on the bf16 matrix cores (wgrad4_x6_kernel) when asked for (PC_WG_X6); seven fp32 accumulators otherwise
+static const char* const WG_STEM_NAME[] = {"wgrad4_x6<7,2,7>", "wgrad4<28,7,2,7,pack3>", "wgrad4<28,7,2,7>"};
+inline int wg_stem_inst(const pc_wgrad_desc* d) {
+    if (!(d->flags & PC_WG_CS3)) return 2;
+    return (d->flags & PC_WG_X6) ? 0 : 1;
 }
+inline bool wg_stem_x6(const pc_wgrad_desc* d) { return wg_route(d) == WG_STEM && wg_stem_inst(d) == 0; }
 // does the problem's launch multiply on the bf16 matrix cores?  (the 9-tap spectral planes and un-flagged problems stay on fp32 MFMA)
 inline bool wg_uses_x6(const pc_wgrad_desc* d) {
     if (!(d->flags & PC_WG_X6)) return false;
     const WgRoute r = wg_route(d);
     return r == WG_ROW3 || r == WG_GENERIC || (r == WG_STEM && wg_stem_x6(d));
 }
-// 256-column tiles with 16-position chunks for the long-K launches of the generic kernel (PICONS_WGRAD_WIDE bit 0: 128-row, bit 1: 64-row tiles)
-inline bool wg_wide(const pc_wgrad_desc* d, bool small_m) {
+// 256-column tiles with 16-position chunks for the long-K launches of the generic kernel (128-row and 64-row tiles alike)
+inline bool wg_wide(const pc_wgrad_desc* d) {
     if (d->flags & PC_WG_X6) return false;          // the bf16-split kernel keeps 128-column tiles (two accumulators per tile)
-    static const int wide_env = getenv("PICONS_WGRAD_WIDE") ? atoi(getenv("PICONS_WGRAD_WIDE")) : 3;
     const int64_t P = (int64_t)d->N * d->Tq * d->Hq * d->Wq;
     const int Ntot = d->ntap[0] * d->ntap[1] * d->ntap[2] * d->Cs;
-    return !wg_ablate() && Ntot >= 512 && (((wide_env & 1) && !small_m) || ((wide_env & 2) && small_m)) && P >= 65536;
+    return !wg_ablate() && Ntot >= 512 && P >= 65536;
 }
 // row-segment kernel geometry (shared by the launch and the accounting)
 struct Row3Geo { bool csb64, small_m, x6; int bkp, bm, csb; };
@@ -1772,13 +1755,6 @@ inline WgSplit wg_generic_split(const pc_wgrad_desc* d) {
     return w;
 }
 
-// Which kernel template instance a problem's launch takes, per route: ONE choice for the launch (wgrad_run) and for the reporter
-// (pc_wgrad_variant).  The index selects the launch in wgrad_run's switches and the name in these tables.
-static const char* const WG_STEM_NAME[] = {"wgrad4_x6<7,2,7>", "wgrad4<28,7,2,7,pack3>", "wgrad4<28,7,2,7>"};
-inline int wg_stem_inst(const pc_wgrad_desc* d) {
-    static const int pack3 = getenv("PICONS_WGRAD_STEM_PACK3") ? atoi(getenv("PICONS_WGRAD_STEM_PACK3")) : 1;
-    return wg_stem_x6(d) ? 0 : (((d->flags & PC_WG_CS3) && pack3) ? 1 : 2);
-}
 static const char* const WG_ROW_NAME[] = {"wgrad3_x6<64,64,64,2>", "wgrad3_x6<64,32,64,2>", "wgrad3_x6<128,64,32,4>", "wgrad3_x6<128,32,32,4>", "wgrad3<64,20,64,2,9>",
                                           "wgrad3<128,28,32,4>",   "wgrad3<64,56,64,2>",    "wgrad3<64,28,64,2>",     "wgrad3<128,28,64,2>"};
 inline int wg_row_inst(const Row3Geo& geo, bool row9) {
@@ -1823,11 +1799,10 @@ extern "C" int pc_wgrad_work(const pc_wgrad_desc* d, int cd_real, int cs_real, d
     const WgRoute route = wg_route(d);
     double issued = 0, executed = 0, launches = 1;
     if (route == WG_STEM) {
-        const bool x6 = wg_stem_x6(d);
+        const int inst = wg_stem_inst(d);
+        const bool x6 = inst == 0, p3 = inst != 2;
         const int nseg = x6 ? cdiv(d->Wq, 16) : d->Wq / 28, mt = cdiv(d->Cd, 64);
         const double seg = x6 ? 16.0 : 28.0;
-        static const int pack3 = getenv("PICONS_WGRAD_STEM_PACK3") ? atoi(getenv("PICONS_WGRAD_STEM_PACK3")) : 1;
-        const bool p3 = (d->flags & PC_WG_CS3) && pack3;
         const double nacc = p3 ? (7 * 7 * 3 + 31) / 32 : 7;
         for (int a = 0; a < d->ntap[0]; ++a) {
             const double chunks = (double)d->N * V[0][a] * d->Hq * nseg;          // every kh of the kt tap, all w
@@ -1849,7 +1824,7 @@ extern "C" int pc_wgrad_work(const pc_wgrad_desc* d, int cd_real, int cs_real, d
         const WgSplit w = wg_generic_split(d);
         launches = w.n;
         for (int i = 0; i < w.n; ++i) {
-            const bool wide = wg_wide(d, w.small_m[i]);
+            const bool wide = wg_wide(d);
             const int bm = w.small_m[i] ? 64 : 128, bn = wide ? 256 : 128, kb = wide ? 16 : BK;
             issued += (double)cdiv(P, kb) * kb * ((double)cdiv(w.hi[i] - w.lo[i], bm) * bm) * ((double)cdiv(Ntot, bn) * bn) * nb;
         }
@@ -1909,9 +1884,8 @@ static int wgrad_run(const pc_wgrad_desc* d, const float* D, const float* S, flo
     // rows of D's channels [m_lo, m_hi) with 64- or 128-row tiles
     // conv with 3 taps, stride 1, padding 1 along w and 32- / 64-channel blocks of S: row-segment kernel (the kw taps share
     // one LDS tile)
-    // split-K fills `rounds` rounds of resident-block slots: one round measured best on the step (fewer atomics per weight;
+    // split-K fills one round of resident-block slots: measured best on the step (fewer atomics per weight;
     // the second lane's launches fill what a single round leaves idle)
-    static const double rounds = getenv("PICONS_WGRAD_ROUNDS") ? atof(getenv("PICONS_WGRAD_ROUNDS")) : 1.0;
     const WgRoute route = wg_route(d);
     if (route == WG_STEM) {
         Wg4K q;
@@ -1931,8 +1905,8 @@ static int wgrad_run(const pc_wgrad_desc* d, const float* D, const float* S, flo
             ntv[a] = cnt; tot += cnt;
         }
         PC_CHECK_ARG(tot > 0, "pc_conv_wgrad: no valid tap");
-        static const int s4_slots = getenv("PICONS_WGRAD_STEM_SLOTS") ? atoi(getenv("PICONS_WGRAD_STEM_SLOTS")) : 768;   // 162 VGPRs, 28 KiB LDS: 3 blocks per CU
-        const int slots = d->splitk > 0 ? d->splitk * q.ntap_t : (x6 ? 512 : s4_slots) / q.mt;                         // the bf16-split kernel: two blocks per CU
+        // resident-block slots: the fp32 kernel (162 VGPRs, 28 KiB LDS) holds 3 blocks per CU, the bf16-split kernel two
+        const int slots = d->splitk > 0 ? d->splitk * q.ntap_t : (x6 ? 512 : 768) / q.mt;
         q.pre[0] = 0;
         for (int a = 0; a < q.ntap_t; ++a) {
             int sl = ntv[a] ? (int)((double)slots * ntv[a] / tot) : 0;
@@ -1948,9 +1922,8 @@ static int wgrad_run(const pc_wgrad_desc* d, const float* D, const float* S, flo
         PC_CHECK_ARG(!wss || nslices <= d->ws_slices, "pc_conv_wgrad: the workspace holds %d slice images, this launch writes %d (pc_wgrad_slices)", d->ws_slices, nslices);
         q.wss = wss;
         {   // block order: slices sorted by where in the volume they are (their relative position inside their kt's slice range), kt as tie-break
-            static const int il = getenv("PICONS_WGRAD_STEM_INTERLEAVE") ? atoi(getenv("PICONS_WGRAD_STEM_INTERLEAVE")) : 1;
             const int tot_sl = q.pre[q.ntap_t];
-            q.interleave = il && tot_sl <= 1024;
+            q.interleave = tot_sl <= 1024;
             if (q.interleave) {
                 std::pair<double, int> key[1024];
                 for (int a = 0; a < q.ntap_t; ++a) {
@@ -1987,7 +1960,7 @@ static int wgrad_run(const pc_wgrad_desc* d, const float* D, const float* S, flo
         // resident-block slots of the variant that will run: the fp32 kernels hold three blocks per CU (two with 56-position segments), the
         // bf16-split ones two -- except wgrad3_x6_kernel<128, 64, 32, 4>, whose 82 KiB of LDS admit ONE block per CU
         const int slots = geo.x6 ? ((!csb64 && bkp == 64) ? 256 : 512) : (bkp == 56 ? 512 : 768);
-        int splitk = d->splitk > 0 ? d->splitk : (d->splitk == -1 ? 1 : (int)(rounds * slots / (tiles * nprob)));
+        int splitk = d->splitk > 0 ? d->splitk : (d->splitk == -1 ? 1 : (int)((double)slots / (tiles * nprob)));
         const int maxsplit = q.nchunks / 8 > 0 ? q.nchunks / 8 : 1;
         if (splitk > maxsplit) splitk = maxsplit;
         if (splitk < 1) splitk = 1;
@@ -2018,7 +1991,7 @@ static int wgrad_run(const pc_wgrad_desc* d, const float* D, const float* S, flo
         // 256-column tiles with 16-position chunks for the long-K launches: 17-25 % less tile traffic per FLOP.  The kernel
         // is bound by the LDS-DMA fill rate, not by the MFMA loop (fetch ablation: 148 TF/s without the fetch, 113-118 with either
         // operand tile alone, 103 with both): 3x3x3 128->128 @112^2 103 -> 115 TF/s, the 64-channel layers 87 -> 92
-        const bool wide = wg_wide(d, small_m);
+        const bool wide = wg_wide(d);
         const int bm = small_m ? 64 : 128, bn = wide ? 256 : 128;
         k.nchunks = cdiv(P, wide ? 16 : BK);
         const int mt = cdiv(m_hi - m_lo, bm), ntl = cdiv(k.Ntot, bn);
@@ -2031,7 +2004,7 @@ static int wgrad_run(const pc_wgrad_desc* d, const float* D, const float* S, flo
             // 8 chunks (256 positions) per slice
             const int64_t tiles = (int64_t)mt * ntl * nb;
             const int slots = (small_m || wide) ? 768 : 512;
-            splitk = (int)(rounds * slots / tiles);
+            splitk = (int)((double)slots / tiles);
             const int maxsplit = k.nchunks / 8 > 0 ? k.nchunks / 8 : 1;
             if (splitk > maxsplit) splitk = maxsplit;
             if (splitk < 1) splitk = 1;
@@ -2126,10 +2099,7 @@ namespace {
 // the problems pc_conv_wgrad would give to the generic split-K kernel (not the stem / row-segment kernels, not a forced split)
 bool wg_is_generic(const pc_wgrad_desc* d) {
     if (wg_ablate() || wg_route(d) != WG_GENERIC || d->splitk != 0) return false;
-    const WgSplit w = wg_generic_split(d);
-    for (int i = 0; i < w.n; ++i)
-        if (wg_wide(d, w.small_m[i])) return false;          // long-K launches keep their 256-column tiles
-    return true;
+    return !wg_wide(d);          // long-K launches keep their 256-column tiles
 }
 
 int wg_fill(const pc_wgrad_desc* d, const float* D, const float* S, float* g, WgK& k) {
@@ -2163,10 +2133,9 @@ int wg_fill(const pc_wgrad_desc* d, const float* D, const float* S, float* g, Wg
 extern "C" int pc_conv_wgrad_multi(const pc_wgrad_job* jobs, int njobs, pc_stream s_) {
     hipStream_t s = (hipStream_t)s_;
     PC_CHECK_ARG(jobs && njobs >= 1 && njobs <= 64, "pc_conv_wgrad_multi: jobs=%p njobs=%d (1..64)", (const void*)jobs, njobs);
-    static const int multi_env = getenv("PICONS_WGRAD_MULTI") ? atoi(getenv("PICONS_WGRAD_MULTI")) : 1;
     std::vector<int> gen;
     for (int j = 0; j < njobs; ++j) {
-        if (multi_env && wg_is_generic(&jobs[j].d)) { gen.push_back(j); continue; }
+        if (wg_is_generic(&jobs[j].d)) { gen.push_back(j); continue; }
         const int rc = pc_conv_wgrad(&jobs[j].d, jobs[j].D, jobs[j].S, jobs[j].g, s_);      // stem / row-segment / long-K problems: own launch
         if (rc != PC_OK) return rc;
     }

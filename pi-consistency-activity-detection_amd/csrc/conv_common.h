@@ -5,7 +5,7 @@
 
 namespace {
 
-constexpr int F_SCALAR_EPI = 1 << 29;     // internal flag (PICONS_CONV_SCALAR_EPI=1): 4-byte stores straight from the accumulators
+constexpr int F_SCALAR_EPI = 1 << 29;     // internal flag the kernels test (4-byte stores straight from the accumulators); the host always clears it
 
 struct ConvK {
     const float* in; const float* w; const float* bias; const float* cscale; float* out; float* bnpart;
@@ -18,7 +18,6 @@ struct ConvK {
 };
 
 constexpr int BK = 32;       // K chunk (floats)
-constexpr int CONV_DEFAULT_VARIANT = 0;
 constexpr int LDK = 36;      // padded LDS row (floats): conflict-free ds_read_b128 (9i mod 16 distinct)
 
 // Output tile through LDS (the operand buffers are free once the K loop has ended on a barrier) so that every lane stores

@@ -417,8 +417,7 @@ __global__ __launch_bounds__(64 * WM * WN, 1) void conv_x6_kernel(const ConvX6 p
 
 // block order with the row tiles fastest: few row tiles over >= 2 MB of weights per column tile
 inline bool x6_mfast(int mtiles_g, int K, int bn) {
-    static const int mf = getenv("PICONS_X6_MFAST") ? atoi(getenv("PICONS_X6_MFAST")) : 1;
-    return mf && mtiles_g <= 8 && mtiles_g > 1 && (long long)K * bn * 6 >= (2ll << 20);
+    return mtiles_g <= 8 && mtiles_g > 1 && (long long)K * bn * 6 >= (2ll << 20);
 }
 
 template <int BM, int BN, int WM, int WN>
@@ -450,8 +449,6 @@ inline X6Split x6_split(const pc_conv_desc* d, int groups, const X6Tile& t) {
     X6Split r;
     r.tiles = (int)(groups * cdiv(Mg, t.bm) * cdiv(d->Co, t.bn));
     r.full = r.tiles; r.rem = 0; r.ksplit = 1; r.ws_floats = 0;
-    static const int off = getenv("PICONS_X6_TAIL_SPLIT") ? !atoi(getenv("PICONS_X6_TAIL_SPLIT")) : 0;
-    if (off) return r;
     const int S = x6_slots(t);
     const int rem = r.tiles % S;
     if (rem == 0 || rem * 10 > S * 6) return r;
@@ -514,10 +511,9 @@ extern "C" int pc_conv_x6_ok(const pc_conv_desc* d) {
     const long long Mg = (long long)(d->N / groups) * d->Tq * d->Hq * d->Wq;
     // ... and a K loop long enough to pay for the pipeline's prologue: launches of <= 4 chunks (K <= 128: the 1 x 1 x 1 layers over 32 - 128
     // channels) run 0.73 - 0.92x the fp32 kernel on the 4-wave tiles, 1.02 - 1.04x on the 256 x 128 tile (profiles/r04_x6_launches.txt).
-    // PICONS_X6_KMIN = least number of 32-channel chunks (default 5; 1 = no rule)
-    static const int kmin = getenv("PICONS_X6_KMIN") ? atoi(getenv("PICONS_X6_KMIN")) : 5;
+    // Hence at least 5 chunks of 32 channels on the 4-wave tiles.
     const int chunks = d->ntap[0] * d->ntap[1] * d->ntap[2] * (d->Ci / BK);
-    if (chunks < kmin && t.bm != 256) return 0;
+    if (chunks < 5 && t.bm != 256) return 0;
     return (long long)groups * cdiv(Mg, t.bm) * cdiv(d->Co, t.bn) >= 150 ? 1 : 0;
 }
 

@@ -113,44 +113,13 @@ __device__ __forceinline__ void load_col(const LossK& p, int b, int hw, float* o
     }
 }
 
-// NC adjacent columns (w0 .. w0+NC-1 of one image row) per thread: NC = 4 moves 16 bytes per lane and load / store
-// instruction (W % 4 == 0 and 16-byte aligned tensors), NC = 1 is the general form.  The flipped operand's columns
-// W-1-w0 .. W-NC-w0 are one aligned vector too, read in reverse.
-template <int NC>
-__device__ __forceinline__ void load_cols(const LossK& p, int b, int hw0, float (&o)[NC][8], float (&fp)[NC][8], float (&sg)[NC][8], bool need_fp, bool need_seg) {
-    if (NC == 1) {
-        float fdummy[8];
-        load_col(p, b, hw0, o[0], need_fp ? fp[0] : fdummy, sg[0], need_seg);
-        return;
-    }
-    typedef float vecT __attribute__((ext_vector_type(NC)));
-    const int h = hw0 / p.W, w0 = hw0 - h * p.W;
-    const size_t base = (size_t)b * T8 * p.HW;
-    const int fl = h * p.W + (p.W - NC - w0);
-#pragma unroll
-    for (int t = 0; t < 8; ++t) {
-        const vecT v = *(const vecT*)(p.O + base + (size_t)t * p.HW + hw0);
-#pragma unroll
-        for (int c = 0; c < NC; ++c) o[c][t] = v[c];
-        if (need_fp) {
-            const vecT f = *(const vecT*)(p.F + base + (size_t)t * p.HW + fl);
-#pragma unroll
-            for (int c = 0; c < NC; ++c) fp[c][t] = f[NC - 1 - c];
-        }
-        if (need_seg) {
-            const vecT g = *(const vecT*)(p.seg + base + (size_t)t * p.HW + hw0);
-#pragma unroll
-            for (int c = 0; c < NC; ++c) sg[c][t] = g[c];
-        }
-    }
-}
-
-template <int NC> struct LossGeom { static constexpr int BT = NC == 1 ? 256 : 128; };   // threads per block
-
 // ---- pass 1: per-clip partial statistics.  One wave-level reduction per quantity, ONE block barrier for all thirteen.
+// NC: columns per thread.  Only NC = 1 is built (wider threads measured slower: pc_consistency_loss); the loops over the NC columns keep their
+// form because the kernels compile to other instructions without them.
 template <int NC>
 __global__ __launch_bounds__(256) void loss_pass1(const LossK p) {
-    constexpr int BT = LossGeom<NC>::BT, NW = BT / 64;
+    static_assert(NC == 1, "one column per thread");
+    constexpr int BT = 256, NW = BT / 64;
     __shared__ double sh[NW][Q_N];
     const int b = blockIdx.y, hw0 = (blockIdx.x * BT + threadIdx.x) * NC;
     const bool act = hw0 < p.HW;
@@ -160,7 +129,7 @@ __global__ __launch_bounds__(256) void loss_pass1(const LossK p) {
     for (int k = Q_SSQ; k < Q_N; ++k) q[k] = 0.0;
     if (act) {
         float oa[NC][8], fa[NC][8], sa[NC][8];
-        load_cols<NC>(p, b, hw0, oa, fa, sa, true, lab);
+        load_col(p, b, hw0, oa[0], fa[0], sa[0], lab);
 #pragma unroll
         for (int c = 0; c < NC; ++c) {
             const float* o = oa[c]; const float* fp = fa[c]; const float* sg = sa[c];
@@ -283,7 +252,8 @@ __device__ __forceinline__ double loss_global(const LossK& p, int which) {
 // the B clips' columns (they sit in L2 / Infinity Cache: 12.8 MB), in the same j order as a serial loop.
 template <int NC>
 __global__ __launch_bounds__(256) void loss_pass2(const LossK p) {
-    constexpr int BT = LossGeom<NC>::BT, NW = BT / 64;
+    static_assert(NC == 1, "one column per thread");
+    constexpr int BT = 256, NW = BT / 64;
     __shared__ double sh[NW];
     const int b = blockIdx.y, hw0 = (blockIdx.x * BT + threadIdx.x) * NC;
     const bool act = hw0 < p.HW;
@@ -303,7 +273,7 @@ __global__ __launch_bounds__(256) void loss_pass2(const LossK p) {
         if (p.gv) {
             for (int j = 0; j < p.B; ++j) {
                 float oj[NC][8], fj[NC][8], sj[NC][8];
-                load_cols<NC>(p, j, hw0, oj, fj, sj, false, false);
+                load_col(p, j, hw0, oj[0], fj[0], sj[0], false);
                 const float mg = (float)p.clip[j * 16 + 4], rg = (float)p.clip[j * 16 + 5];
 #pragma unroll
                 for (int c = 0; c < NC; ++c) {
@@ -319,7 +289,7 @@ __global__ __launch_bounds__(256) void loss_pass2(const LossK p) {
             }
         }
         float oa[NC][8], fa[NC][8], sa[NC][8];
-        load_cols<NC>(p, b, hw0, oa, fa, sa, true, lab);
+        load_col(p, b, hw0, oa[0], fa[0], sa[0], lab);
         float goa[NC][8], gca[NC][8];
         const double* cs = p.clip + b * 16;
         const size_t base = (size_t)b * T8 * p.HW;
@@ -360,23 +330,10 @@ __global__ __launch_bounds__(256) void loss_pass2(const LossK p) {
             }
         }
         const int h = hw0 / p.W, w0 = hw0 - h * p.W;
-        if (NC == 1) {
 #pragma unroll
-            for (int t = 0; t < 8; ++t) {
-                p.dO[base + (size_t)t * p.HW + hw0] = goa[0][t];
-                p.dF[base + (size_t)t * p.HW + h * p.W + (p.W - 1 - w0)] = gca[0][t];
-            }
-        } else {
-            typedef float vecT __attribute__((ext_vector_type(NC)));
-            const int fl = h * p.W + (p.W - NC - w0);
-#pragma unroll
-            for (int t = 0; t < 8; ++t) {
-                vecT vo, vf;
-#pragma unroll
-                for (int c = 0; c < NC; ++c) { vo[c] = goa[c][t]; vf[NC - 1 - c] = gca[c][t]; }
-                *(vecT*)(p.dO + base + (size_t)t * p.HW + hw0) = vo;
-                *(vecT*)(p.dF + base + (size_t)t * p.HW + fl) = vf;
-            }
+        for (int t = 0; t < 8; ++t) {
+            p.dO[base + (size_t)t * p.HW + hw0] = goa[0][t];
+            p.dF[base + (size_t)t * p.HW + h * p.W + (p.W - 1 - w0)] = gca[0][t];
         }
     }
     gvacc = wave_sum_d(gvacc);
@@ -584,25 +541,11 @@ extern "C" int pc_consistency_loss(const pc_loss_desc* d, const float* output, c
     else if (d->gv) { k.c_l2 = 0; k.c_bv = 0; k.c_gv = 1; }
     else if (d->bv) { k.c_l2 = 1 - r; k.c_bv = r; k.c_gv = 0; }
     else { k.c_l2 = 1; k.c_bv = 0; k.c_gv = 0; }
-    // four columns per thread (16-byte loads / stores) when a row is a whole number of them and every tensor is 16-byte aligned
-    static const int nc_env = getenv("PICONS_LOSS_NC") ? atoi(getenv("PICONS_LOSS_NC")) : 1;      // columns per thread: 1 measured fastest (89 / 101 / 116 us for 1 / 2 / 4: the passes are bound by the variance arithmetic, not by bytes, and wider threads cost occupancy)
-    const int nc_env2 = nc_env;
-    const bool vec4 = nc_env >= 2 && d->W % 4 == 0 && (((uintptr_t)output | (uintptr_t)flip_op | (uintptr_t)seg | (uintptr_t)d_output | (uintptr_t)d_flip_op) & 15) == 0;
-    if (vec4 && nc_env2 == 2) {
-        k.nbx = cdiv(k.HW / 2, LossGeom<2>::BT); k.nbx2 = k.nbx * k.B;         // = the cdiv(HW, 256) the workspace is sized for
-        hipLaunchKernelGGL(loss_pass1<2>, dim3(k.nbx, k.B), dim3(LossGeom<2>::BT), 0, s, k);
-        hipLaunchKernelGGL(loss_mid, dim3(k.B), dim3(256), 0, s, k);
-        hipLaunchKernelGGL(loss_pass2<2>, dim3(k.nbx, k.B), dim3(LossGeom<2>::BT), 0, s, k);
-    } else if (vec4) {
-        k.nbx = cdiv(k.HW / 4, LossGeom<4>::BT); k.nbx2 = k.nbx * k.B;         // <= the cdiv(HW, 256) the workspace is sized for
-        hipLaunchKernelGGL(loss_pass1<4>, dim3(k.nbx, k.B), dim3(LossGeom<4>::BT), 0, s, k);
-        hipLaunchKernelGGL(loss_mid, dim3(k.B), dim3(256), 0, s, k);
-        hipLaunchKernelGGL(loss_pass2<4>, dim3(k.nbx, k.B), dim3(LossGeom<4>::BT), 0, s, k);
-    } else {
-        hipLaunchKernelGGL(loss_pass1<1>, dim3(k.nbx, k.B), dim3(256), 0, s, k);
-        hipLaunchKernelGGL(loss_mid, dim3(k.B), dim3(256), 0, s, k);
-        hipLaunchKernelGGL(loss_pass2<1>, dim3(k.nbx, k.B), dim3(256), 0, s, k);
-    }
+    // one column per thread: measured fastest (89 / 101 / 116 us for 1 / 2 / 4 columns: the passes are bound by the variance arithmetic,
+    // not by bytes, and wider threads cost occupancy)
+    hipLaunchKernelGGL(loss_pass1<1>, dim3(k.nbx, k.B), dim3(256), 0, s, k);
+    hipLaunchKernelGGL(loss_mid, dim3(k.B), dim3(256), 0, s, k);
+    hipLaunchKernelGGL(loss_pass2<1>, dim3(k.nbx, k.B), dim3(256), 0, s, k);
     hipLaunchKernelGGL(loss_final, dim3(1), dim3(256), 0, s, k);
     PC_CHECK_LAUNCH("consistency_loss");
     return PC_OK;

@@ -317,8 +317,7 @@ extern "C" int pc_tail6_gather(const float* cols, const float* bc, const float* 
     PC_CHECK_ARG(cols && bc && bsm && out && N >= 1 && It >= 1 && Ih >= 1 && Iw >= 1, "pc_tail6_gather: bad args");
     const int64_t total = (int64_t)N * 8 * It * Ih * Iw;
     PC_CHECK_ARG((total + 255) / 256 < (1ll << 31), "pc_tail6_gather: too large");
-    static const int rows_env = getenv("PICONS_TAIL6_GATHER_ROWS") ? atoi(getenv("PICONS_TAIL6_GATHER_ROWS")) : 1;
-    if (rows_env && ((uintptr_t)out & 7) == 0) {
+    if (((uintptr_t)out & 7) == 0) {
         const dim3 grid((unsigned)((int64_t)N * It * Ih));
         hipLaunchKernelGGL((tail6_gather_rows_kernel<0, 0>), grid, dim3(128), 0, (hipStream_t)s, cols, bc, bsm, N, It, Ih, Iw, out);
         hipLaunchKernelGGL((tail6_gather_rows_kernel<0, 1>), grid, dim3(128), 0, (hipStream_t)s, cols, bc, bsm, N, It, Ih, Iw, out);

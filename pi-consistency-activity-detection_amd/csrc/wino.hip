@@ -35,7 +35,7 @@ struct WinoK {
     const float* in; const float* U; const float* bias; float* out; float* bnpart;
     int N, T, H, W, Ci, ldi, Co, ldo;
     int TH, TW, BTH, BTW, nbh, nbw, nct, nc8;
-    int scalar_epi;                         // PICONS_WINO_SCALAR_EPI=1: four-byte stores straight from the accumulators (A/B switch)
+    int scalar_epi;                         // 1: four-byte stores straight from the accumulators; the host always sets 0 (the kernels still test it)
     int KT, act, flags;
     int Ti, ta, tc, tden;
     int btw_magic;
@@ -468,8 +468,7 @@ int fill(const pc_wino_desc* d, WinoK& k) {
     k.nbh = cdiv(k.TH, k.BTH); k.nbw = cdiv(k.TW, k.BTW);
     k.btw_magic = (65536 + k.BTW - 1) / k.BTW;
     k.nct = cdiv(d->Co, WC); k.nc8 = d->Ci / WK;
-    static const int scalar_epi = getenv("PICONS_WINO_SCALAR_EPI") ? atoi(getenv("PICONS_WINO_SCALAR_EPI")) : 0;
-    k.scalar_epi = scalar_epi;
+    k.scalar_epi = 0;
     k.KT = d->KT; k.act = d->act; k.flags = d->flags;
     PC_CHECK_ARG(d->Ti >= 1 && d->ta >= 1 && d->tden >= 1, "pc_wino: Ti / ta / tden must be >= 1 (Ti=%d ta=%d tden=%d)", d->Ti, d->ta, d->tden);
     k.Ti = d->Ti; k.ta = d->ta; k.tc = d->tc; k.tden = d->tden;

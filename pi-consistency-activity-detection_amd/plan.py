@@ -536,7 +536,7 @@ class Plan:
             wp, pstride = self.planes_of(w_ref)
             # workspace for the launch's tail split (csrc/conv_x6.hip: the tiles of the last, partly filled round of resident blocks run as K
             # slices); private to the op, its counters zeroed once by the arena's owner (upload_consts) and left zero by every launch
-            n_ws = int(capi.lib().pc_conv_x6_ws_floats(_cdesc(t))) if sw.get("PICONS_X6_TAIL_SPLIT", "1") != "0" else 0
+            n_ws = int(capi.lib().pc_conv_x6_ws_floats(_cdesc(t)))
             ws = None
             if n_ws > 0:
                 ws = self.alloc(n_ws)

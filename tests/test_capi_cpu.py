@@ -34,11 +34,13 @@ def test_header_symbols_exported(built):
 def test_product_library_holds_no_wrong_result_diagnostics(built):
     """the ablation / stamp variants of the GEMM kernels (some WRONG by design) and their switches are compiled only into
     libpicons_diag.so (make diag); the shipped library does not even contain the variable names, and setting one without the diagnostic
-    library is refused by the loader instead of being ignored."""
+    library is refused by the loader instead of being ignored.  The product library reads no environment at all: it holds no PICONS_* name
+    and does not import getenv (an imported name sits in the dynamic string table, so the file's bytes show it) -- every launch decision is a
+    constant in csrc/, and two builds are compared through PICONS_LIB_NAME (capi.py)."""
     import subprocess
     import sys
     blob = open(capi.LIB_PATH, "rb").read()
-    for word in (b"ABLATE", b"PICONS_WINO_VARIANT"):
+    for word in (b"ABLATE", b"PICONS_WINO_VARIANT", b"PICONS_", b"getenv"):
         assert word not in blob, "%s found in the product library" % word.decode()
     code = "import picons_amd; from picons_amd import capi; capi.lib()"
     env = dict(os.environ, PICONS_WGRAD_ABLATE="1", PYTHONPATH=ROOT)

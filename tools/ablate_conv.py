@@ -26,7 +26,7 @@ SHAPES = [  # name, N, thw, Ci, Co, k
     ("1x1 480->304 @28x28 (stacked)", 16, (1, 28, 28), 480, 304, (1, 1, 1)),
 ]
 only = os.environ.get("ABLATE_ONLY")
-mode = os.environ.get("PICONS_CONV_ABLATE", "0") + "/var" + os.environ.get("PICONS_CONV_VARIANT", "-")
+mode = os.environ.get("PICONS_CONV_ABLATE", "0")
 R = int(os.environ.get("ABLATE_REPS", "5"))
 for name, N, thw, Ci, Co, k in SHAPES:
     if only and only not in name:

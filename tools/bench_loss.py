@@ -16,4 +16,4 @@ for gv in (False, True):
     t0 = time.perf_counter()
     for _ in range(50): ops.run_ops(arr)
     torch.cuda.synchronize()
-    print("NC=%s gv=%s loss list: %.1f us" % (os.environ.get("PICONS_LOSS_NC", "1"), gv, (time.perf_counter() - t0) / 50 * 1e6), eng.read_scalars())
+    print("gv=%s loss list: %.1f us" % (gv, (time.perf_counter() - t0) / 50 * 1e6), eng.read_scalars())

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """The two row-spectral PrimaryCaps GEMMs on the bf16-split kernel at the bench size (N = 16 clip-passes, 41 frequency groups):
 forward 832 -> 544 over 320 rows per group, input gradient 544 -> 832 over 448 rows per group.  Prints ms per launch and a checksum;
-run once per tile choice (PICONS_X6_TALL=0/1, PICONS_X6_MFAST=0/1) and compare.  `--save f` / `--check f`: store / compare the outputs."""
+run once per build of the library (PICONS_LIB_NAME) and compare.  `--save f` / `--check f`: store / compare the outputs."""
 import os
 import sys
 
