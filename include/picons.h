@@ -55,13 +55,18 @@ typedef void* pc_stream;            /* hipStream_t */
                                      * results; BatchNorm partial rows then number pc_wino_bnpart_rows(d) for THIS flag setting */
 #define PC_F_X6      128            /* the launch multiplies on the bf16 matrix cores: fp32 operands as exact sums of three bf16 values, six
                                      * products, fp32 accumulate (pc_conv_fwd_x6; the caller holds the weights as bf16 planes) */
+#define PC_F_BKMAJOR 512            /* with PC_F_X6: the weight planes are K-major, [Ci][KT*KH*KW][ldw] with the OUTPUT channel contiguous (Co <= ldw,
+                                     * Co % 8 == 0; group g at + g * wgstride) -- the forward planes of a layer, read as they are by its input
+                                     * gradient, so no transposed copy is made.  Same tile, split, work counts and variant string as without
+                                     * the flag, bit-identical results; built for the 64 x 128, 128 x 64 and 64 x 64 tiles only (PC_E_ARG otherwise) */
 
 /* ABI version of this header: bumped whenever a struct in it grows or an op's operands change (101: pc_wino_desc.m, PC_OP_BN_FIN_APPLY,
  * pc_wgrad_desc.ws_slices, pc_transpose_job.nslices / slice_stride, pc_wgrad_slices; 102: the workspace operands of PC_OP_TAIL6_WGRAD_MAP / PC_OP_TAIL6_BIAS_SUMS /
- * PC_OP_TAIL_GRADS; 103: the variant reporters pc_conv_variant / pc_wino_variant / pc_wgrad_variant).  Descriptors must be zero-initialised by the caller:
+ * PC_OP_TAIL_GRADS; 103: the variant reporters pc_conv_variant / pc_wino_variant / pc_wgrad_variant;
+ * 104: PC_F_BKMAJOR, pc_wino_weights_multi / PC_OP_WINO_WEIGHTS_MULTI).  Descriptors must be zero-initialised by the caller:
  * fields added later read as "old behaviour" when 0.  pc_version() returns the value the library was built with; the Python host
  * (capi.lib()) refuses a library whose version differs from the header it mirrors. */
-#define PC_VERSION 103
+#define PC_VERSION 104
 int         pc_version(void);
 const char* pc_last_error(void);
 
@@ -175,6 +180,14 @@ int pc_wino_conv(const pc_wino_desc* d, const float* in, const float* U, const f
 /* transform-domain weights of the m = 4 form (same addressing of w as pc_wino_weights) */
 int64_t pc_wino4_u_floats(int O, int I, int KT);
 int pc_wino4_weights(const float* w, int64_t sO, int64_t sT, int64_t sI, int O, int I, int KT, int flip, float* U, pc_stream s);
+/* many weight transforms of either form in ONE launch (the per-step transforms of the layers whose prep runs on one lane); `jobs` is HOST memory.
+ * Each job is one pc_wino_weights (m = 2 or 0) / pc_wino4_weights (m = 4) call: same arithmetic, bit-identical U. */
+typedef struct pc_wino_weights_job {
+    uint64_t w, U;                  /* device pointers */
+    int64_t  sO, sT, sI;
+    int32_t  O, I, KT, flip, m, reserved;
+} pc_wino_weights_job;
+int pc_wino_weights_multi(const pc_wino_weights_job* jobs, int njobs, pc_stream s);
 int pc_wino_bnpart_rows(const pc_wino_desc* d);
 /* host-only work accounting (see pc_conv_work): out[0] issued, out[1] executed multiply-accumulates, out[2] blocks */
 int pc_wino_work(const pc_wino_desc* d, double* out);
@@ -570,6 +583,7 @@ enum {
     PC_OP_WSPEC_MASTER_PLANES,      /* i = Acnt, a0, Atot, B, KY, KX, U, Ur; l[0] = plane stride; p = w, tw, out_f planes, out_t planes */
     PC_OP_BN_FIN_APPLY,             /* i = npg, groups, C, ldz, ldy, relu; l = count per group, rows; f = eps, momentum; p = part, gamma, beta, running_mean, running_var, stat, z, y */
     PC_OP_WGRAD_FOLD,               /* i[0] = nslices; l[0] = image floats; p = ws: pc_wgrad_fold */
+    PC_OP_WINO_WEIGHTS_MULTI,       /* p[0] = HOST pointer to pc_wino_weights_job[i[0]] (kept alive by the owner of the list) */
     PC_OP__COUNT
 };
 #define PC_MAX_LANES 8

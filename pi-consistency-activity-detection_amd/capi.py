@@ -61,7 +61,7 @@ OP_DTYPE = np.dtype([("kind", np.int32), ("i", np.int32, 48), ("f", np.float32, 
  OP_ACT_BWD, OP_TO_NDHWC, OP_TO_NCDHW, OP_TRANSPOSE, OP_FILL, OP_AXPY, OP_EM_FWD, OP_EM_BWD, OP_CMASK_FWD, OP_CMASK_BWD,
  OP_TAPSUM_FWD, OP_TAPSUM_BWD, OP_LOSS, OP_SPREAD, OP_ADAM, OP_TAIL_COMBINE, OP_TAIL_COLSUM, OP_TAIL_GRADS, OP_COL2IM,
  OP_AXIS, OP_WSPEC_FWD, OP_WSPEC_BWD, OP_WSPEC_MASTER_FWD, OP_WSPEC_MASTER_BWD, OP_TAIL6_WEIGHTS, OP_TAIL6_GATHER, OP_TAIL6_SCATTER, OP_TAIL6_WGRAD_MAP, OP_TAIL6_BIAS_SUMS,
- OP_TRANSPOSE_MULTI, OP_FORK, OP_JOIN, OP_WGRAD_MULTI, OP_WINO_CONV, OP_WINO_WEIGHTS, OP_CONV_X6, OP_SPLIT_PLANES, OP_SPLIT_PLANES_MULTI, OP_WSPEC_MASTER_PLANES, OP_BN_FIN_APPLY, OP_WGRAD_FOLD) = range(1, 51)
+ OP_TRANSPOSE_MULTI, OP_FORK, OP_JOIN, OP_WGRAD_MULTI, OP_WINO_CONV, OP_WINO_WEIGHTS, OP_CONV_X6, OP_SPLIT_PLANES, OP_SPLIT_PLANES_MULTI, OP_WSPEC_MASTER_PLANES, OP_BN_FIN_APPLY, OP_WGRAD_FOLD, OP_WINO_WEIGHTS_MULTI) = range(1, 52)
 MAX_LANES = 8
 
 # numpy mirror of struct pc_wgrad_job (pc_wgrad_desc = 42 int32, then D, S, g)
@@ -75,11 +75,16 @@ TJOB_DTYPE = np.dtype([("src", np.uint64), ("dst", np.uint64), ("sbs", np.int64)
 # numpy mirror of struct pc_split_job
 SJOB_DTYPE = np.dtype([("src", np.uint64), ("planes", np.uint64), ("n", np.int64), ("pstride", np.int64)], align=False)
 
+# numpy mirror of struct pc_wino_weights_job
+WWJOB_DTYPE = np.dtype([("w", np.uint64), ("U", np.uint64), ("sO", np.int64), ("sT", np.int64), ("sI", np.int64), ("O", np.int32), ("I", np.int32),
+                        ("KT", np.int32), ("flip", np.int32), ("m", np.int32), ("reserved", np.int32)], align=False)
+
 ACT_NONE, ACT_RELU, ACT_SIGMOID = 0, 1, 2
 F_ACCUM, F_BIAS, F_CSCALE, F_BNPART, F_NFAST, F_TOUT, F_CI3, F_X6, F_STRIPS = 1, 2, 4, 8, 16, 32, 64, 128, 256
+F_BKMAJOR = 512             # with F_X6: K-major weight planes [Ci][taps][ldw] (a layer's forward planes read by its input gradient)
 WG_CS3, WG_X6 = 1, 2
 
-ABI_VERSION = 103          # PC_VERSION of include/picons.h
+ABI_VERSION = 104          # PC_VERSION of include/picons.h
 
 _SIGS = {
     "pc_version": (i32, []),
@@ -105,6 +110,7 @@ _SIGS = {
     "pc_wgrad_work": (i32, [C.POINTER(WgradDesc), i32, i32, C.POINTER(C.c_double)]),
     "pc_wino_u_floats": (i64, [i32, i32, i32]),
     "pc_wino_weights": (i32, [vp, i64, i64, i64, i32, i32, i32, i32, vp, vp]),
+    "pc_wino_weights_multi": (i32, [vp, i32, vp]),
     "pc_wino_conv": (i32, [C.POINTER(WinoDesc), vp, vp, vp, vp, vp, vp]),
     "pc_wino4_u_floats": (i64, [i32, i32, i32]),
     "pc_wino4_weights": (i32, [vp, i64, i64, i64, i32, i32, i32, i32, vp, vp]),
@@ -201,7 +207,7 @@ def lib():
             raise RuntimeError("libpicons.so is ABI version %d, this package mirrors include/picons.h version %d: rebuild it "
                                "(`make -C pi-consistency-activity-detection_amd/csrc`)" % (L.pc_version(), ABI_VERSION))
         assert C.sizeof(ConvDesc) == 48 * 4 and OP_DTYPE.itemsize == 4 + 192 + 32 + 4 + 96 + 32
-        assert C.sizeof(WgradDesc) == 168 and WJOB_DTYPE.itemsize == 192
+        assert C.sizeof(WgradDesc) == 168 and WJOB_DTYPE.itemsize == 192 and WWJOB_DTYPE.itemsize == 64
         _lib = L
     return _lib
 
@@ -216,6 +222,11 @@ def variant(name, desc, *args):
     buf = C.create_string_buffer(160)
     check(getattr(lib(), name)(desc, *args, buf, 160))
     return buf.value.decode()
+
+
+def variant_ok(name, desc, *args):
+    """True if the library would take the launch at all (the reporter runs the launch's own descriptor checks; host-only)."""
+    return getattr(lib(), name)(desc, *args, C.create_string_buffer(160), 160) == 0
 
 
 def call(name, *args):

@@ -32,6 +32,7 @@ namespace {
 
 typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
 typedef __attribute__((ext_vector_type(4))) uint32_t u32x4;
+typedef __attribute__((ext_vector_type(4))) short v4s16;
 
 __device__ __forceinline__ void split2(float x0, float x1, uint32_t& h, uint32_t& m, uint32_t& l) { x6_split2(x0, x1, h, m, l); }
 
@@ -79,7 +80,15 @@ struct ConvX6 { ConvK k; const uint16_t* wp; long long wpstride; int full, rem, 
 
 #define PC_MFX6(X, Y, Cc) Cc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, X), __builtin_bit_cast(bf16x8, Y), Cc, 0, 0, 0)
 
-template <int BM, int BN, int WM, int WN>
+// KM (PC_F_BKMAJOR): the weight planes are K-major, [g][Ci][taps][ldw] with the OUTPUT channel contiguous -- the forward planes of a layer read
+// by its input gradient, so no transposed copy has to be made.  The B tile of a chunk is then [plane][32 k][BN] bf16 (the same number of
+// 1 KiB DMA pieces, rows of 2 BN contiguous bytes), and a fragment is two ds_read_b64_tr_b16 per plane instead of one ds_read_b128: the
+// hardware transposes a block of 4 k x 16 columns per 16-lane group, lane i receives column i with k ascending in its four elements, so
+// element e of a lane's fragment is k = 8 (lane / 32) + e as in the A fragment.  16-byte slots are XOR-swizzled so that the four rows of
+// a block (64 bytes each) fall on four different quarters of the 64 banks: by (k & 3) << 2 on 256-byte rows, (k >> 1 & 1) << 2 on 128-byte
+// rows.  The swizzle depends on k mod 4 only, so both reads of a fragment and both k16 steps of a chunk share one address register.
+// Everything else -- walk, tap box, A split, products and their order, pipeline, tail split, epilogues -- is the same code.
+template <int BM, int BN, int WM, int WN, bool KM = false>
 __global__ __launch_bounds__(64 * WM * WN, 1) void conv_x6_kernel(const ConvX6 px) {
     const ConvK& p = px.k;
     constexpr int NW = WM * WN, NT = 64 * NW;
@@ -95,7 +104,10 @@ __global__ __launch_bounds__(64 * WM * WN, 1) void conv_x6_kernel(const ConvX6 p
     static_assert(BM * BN * 4 / EH <= OPBYTES, "output tile fits the operand buffers");
     extern __shared__ __attribute__((aligned(16))) uint8_t smem8[];
     uint8_t* As0 = smem8;                              // [2][BM][32] fp32
-    uint8_t* Bs0 = smem8 + 2 * ABYTES;                 // [2][3][BN][32] bf16
+    uint8_t* Bs0 = smem8 + 2 * ABYTES;                 // [2][3][BN][32] bf16 (KM: [2][3][32][BN])
+    constexpr int RB = 2 * BN;                         // KM: bytes of one k row of a plane tile
+    static_assert(!KM || BN == 64 || BN == 128, "K-major B tiles: 128- or 256-byte rows");
+    auto km_swz = [](int k) { return BN == 128 ? (k & 3) << 2 : ((k >> 1) & 1) << 2; };
     int* rinfo = (int*)(smem8 + OPBYTES);              // [BM][4] n,t0,h0,w0
     int* rout = rinfo + BM * 4;                        // [BM] output position index or -1
     unsigned* tile_or = (unsigned*)(rout + BM);
@@ -166,9 +178,15 @@ __global__ __launch_bounds__(64 * WM * WN, 1) void conv_x6_kernel(const ConvX6 p
 #pragma unroll
     for (int j = 0; j < BR; ++j) {
         const int pc = wave + NW * j, pl = pc / (BN / 16), q = pc % (BN / 16);
-        const int row = q * 16 + (lane >> 2), co = n0 + row;
-        const int sl = (lane & 3) ^ ((row >> 2) & 3);
-        bdma[j] = (pc < BPIECES && co < p.Co) ? (unsigned)(((size_t)pl * px.wpstride + (size_t)co * p.wtaps * p.ldw + sl * 8) * 2) : DMA_OOB;
+        if constexpr (KM) {
+            // piece pc covers k rows (1024 / RB) q .. of plane pl, 16-byte slot lane % (BN / 8) (source swizzled by km_swz(k)); Co % 8 == 0
+            const int k = q * (1024 / RB) + lane / (BN / 8), co = n0 + ((lane % (BN / 8)) ^ km_swz(k)) * 8;
+            bdma[j] = (pc < BPIECES && co < p.Co) ? (unsigned)(((size_t)pl * px.wpstride + (size_t)k * p.wtaps * p.ldw + co) * 2) : DMA_OOB;
+        } else {
+            const int row = q * 16 + (lane >> 2), co = n0 + row;
+            const int sl = (lane & 3) ^ ((row >> 2) & 3);
+            bdma[j] = (pc < BPIECES && co < p.Co) ? (unsigned)(((size_t)pl * px.wpstride + (size_t)co * p.wtaps * p.ldw + sl * 8) * 2) : DMA_OOB;
+        }
     }
     {
         unsigned mo = 0;
@@ -209,7 +227,7 @@ __global__ __launch_bounds__(64 * WM * WN, 1) void conv_x6_kernel(const ConvX6 p
     };
     auto fetchB = [&](int buf) {
         const int wtap = ((p.wk0[0] + wb.a * p.wkstep[0]) * p.KH + p.wk0[1] + wb.b * p.wkstep[1]) * p.KW + p.wk0[2] + wb.c * p.wkstep[2];
-        const dma_rsrc_t rb = dma_rsrc_h(wbase + (long long)wtap * p.ldw + wb.ci);
+        const dma_rsrc_t rb = dma_rsrc_h(wbase + (KM ? ((long long)wb.ci * p.wtaps + wtap) * p.ldw : (long long)wtap * p.ldw + wb.ci));
 #pragma unroll
         for (int j = 0; j < BR; ++j)
             if (BPIECES % NW == 0 || wave + NW * j < BPIECES) glds16h(rb, bdma[j], Bs0 + buf * BBYTES + (wave + NW * j) * 1024);
@@ -239,8 +257,15 @@ __global__ __launch_bounds__(64 * WM * WN, 1) void conv_x6_kernel(const ConvX6 p
     }
 #pragma unroll
     for (int j = 0; j < TN; ++j) {
-        const int r = wn * (BN / WN) + (lane & 31) + j * 32;
-        bbas[j] = (unsigned)(2 * ABYTES) + (unsigned)(r * 64) + (unsigned)((kh ^ ((r >> 2) & 3)) << 4);
+        if constexpr (KM) {
+            // lane 4 q + pp of 16-lane group gq names row q, columns 4 pp .. 4 pp + 3 of its block: k = 8 (gq / 2) + q, columns 16 (gq % 2) ..
+            const int gq = lane >> 4, q = (lane >> 2) & 3, pp = lane & 3;
+            const int k = 8 * (gq >> 1) + q, ch = (wn * (BN / WN) + j * 32 + 16 * (gq & 1)) / 8 + (pp >> 1);
+            bbas[j] = (unsigned)(2 * ABYTES) + (unsigned)(k * RB) + (unsigned)((ch ^ km_swz(k)) << 4) + (unsigned)((pp & 1) << 3);
+        } else {
+            const int r = wn * (BN / WN) + (lane & 31) + j * 32;
+            bbas[j] = (unsigned)(2 * ABYTES) + (unsigned)(r * 64) + (unsigned)((kh ^ ((r >> 2) & 3)) << 4);
+        }
     }
     // Registers: A planes in two sets (the split of step t + 1 writes one while the MFMAs of step t read the other); B planes of column
     // tiles 0 .. TN - 2 in ONE set -- the planes of step t + 1 are read into a tile's registers right behind its last MFMA of step t --
@@ -251,7 +276,16 @@ __global__ __launch_bounds__(64 * WM * WN, 1) void conv_x6_kernel(const ConvX6 p
         raw[half] = *(const f32x4*)(smem8 + ((abase ^ (unsigned)(s * 64) ^ (unsigned)(half * 16)) + (unsigned)(buf * ABYTES)));
     };
     auto ldB = [&](int j, int pl, int s, int buf) {            // step s: plane slot kh + 2 s -> byte offset ^ 32
-        return *(const u32x4*)(smem8 + ((bbas[j] ^ (unsigned)(s * 32)) + (unsigned)(buf * BBYTES + pl * BPLANE)));
+        if constexpr (KM) {                                     // step s: 16 rows on; second read: 4 rows on (EXEC is full: every branch around this is wave-uniform)
+            typedef __attribute__((address_space(3))) v4s16* lp_t;
+            const unsigned a = bbas[j] + (unsigned)(buf * BBYTES + pl * BPLANE + s * 16 * RB);
+            const uint2 lo = __builtin_bit_cast(uint2, __builtin_amdgcn_ds_read_tr16_b64_v4i16((lp_t)(smem8 + a)));
+            const uint2 hi = __builtin_bit_cast(uint2, __builtin_amdgcn_ds_read_tr16_b64_v4i16((lp_t)(smem8 + a + 4 * RB)));
+            u32x4 r;
+            r[0] = lo.x; r[1] = lo.y; r[2] = hi.x; r[3] = hi.y;
+            return r;
+        } else
+            return *(const u32x4*)(smem8 + ((bbas[j] ^ (unsigned)(s * 32)) + (unsigned)(buf * BBYTES + pl * BPLANE)));
     };
     auto unit = [&](int q, int set) {
         float x0 = raw[q >> 1][(q & 1) * 2], x1 = raw[q >> 1][(q & 1) * 2 + 1];
@@ -420,11 +454,11 @@ inline bool x6_mfast(int mtiles_g, int K, int bn) {
     return mtiles_g <= 8 && mtiles_g > 1 && (long long)K * bn * 6 >= (2ll << 20);
 }
 
-template <int BM, int BN, int WM, int WN>
+template <int BM, int BN, int WM, int WN, bool KM = false>
 int launch_x6(const ConvX6& kx, hipStream_t s) {
     constexpr int OPBYTES = 2 * (BM * BK * 4 + 3 * BN * BK * 2);
     const size_t lds = (size_t)OPBYTES + (size_t)(BM * 5 + 4) * sizeof(int);
-    PC_SET_LDS_ONCE((conv_x6_kernel<BM, BN, WM, WN>), lds, "conv_x6_kernel");
+    PC_SET_LDS_ONCE((conv_x6_kernel<BM, BN, WM, WN, KM>), lds, "conv_x6_kernel");
     ConvX6 p = kx;
     p.k.mtiles_g = cdiv(p.k.Mg, BM);
     p.k.ntiles = cdiv(p.k.Co, BN);
@@ -432,8 +466,8 @@ int launch_x6(const ConvX6& kx, hipStream_t s) {
     if (p.ksplit <= 1 || p.rem <= 0 || !p.ws) { p.full = tiles; p.rem = 0; p.ksplit = 1; }
     p.mfast = x6_mfast(p.k.mtiles_g, p.k.K, BN);
     const dim3 grid(p.full + p.rem * p.ksplit), block(64 * WM * WN);
-    if (pc_tl_ev_start) hipExtLaunchKernelGGL((conv_x6_kernel<BM, BN, WM, WN>), grid, block, lds, s, pc_tl_ev_start, pc_tl_ev_stop, 0, p);
-    else hipLaunchKernelGGL((conv_x6_kernel<BM, BN, WM, WN>), grid, block, lds, s, p);
+    if (pc_tl_ev_start) hipExtLaunchKernelGGL((conv_x6_kernel<BM, BN, WM, WN, KM>), grid, block, lds, s, pc_tl_ev_start, pc_tl_ev_stop, 0, p);
+    else hipLaunchKernelGGL((conv_x6_kernel<BM, BN, WM, WN, KM>), grid, block, lds, s, p);
     PC_CHECK_LAUNCH("conv_x6_kernel");
     return PC_OK;
 }
@@ -460,6 +494,15 @@ inline X6Split x6_split(const pc_conv_desc* d, int groups, const X6Tile& t) {
     r.full = r.tiles - rem; r.rem = rem; r.ksplit = ks;
     r.ws_floats = (long long)rem * ks * t.bm * t.bn + ((rem + 3) / 4) * 4;        // the slices, then one counter per split tile
     return r;
+}
+
+// PC_F_BKMAJOR (K-major weight planes): instantiated for the tiles the spectral PrimaryCaps input gradient takes at 2 .. 8 clips (64 x 128 on
+// odd clip counts and at 8, 128 x 64 on 2, 4, 6) and for 64 x 64, the tile of a launch that fills no round of resident blocks
+inline bool x6_bkmajor_tile(const X6Tile& t) { return (t.bm == 64 && t.bn == 128) || (t.bm == 128 && t.bn == 64) || (t.bm == 64 && t.bn == 64); }
+inline int x6_bkmajor_check(const pc_conv_desc* d, const X6Tile& t, const char* who) {
+    PC_CHECK_ARG(d->Co % 8 == 0 && d->ldw >= d->Co, "%s: PC_F_BKMAJOR needs Co %% 8 == 0 and ldw >= Co (Co=%d ldw=%d)", who, d->Co, d->ldw);
+    PC_CHECK_ARG(x6_bkmajor_tile(t), "%s: PC_F_BKMAJOR is not built for the %d x %d tile this descriptor takes (64 x 128, 128 x 64, 64 x 64 are)", who, t.bm, t.bn);
+    return PC_OK;
 }
 
 // the tail split runs only when the caller brings a workspace (one too small for it is refused, never a silent unsplit launch)
@@ -561,6 +604,7 @@ int pc_x6_variant(const pc_conv_desc* d, int64_t ws_floats, char* buf, int cap) 
     PC_CHECK_ARG(pc_x6_eligible(d), "pc_conv_variant: the descriptor does not take the bf16-split kernel (Ci=%d ldi=%d ldw=%d flags=%d)", d->Ci, d->ldi, d->ldw, d->flags);
     const int groups = d->groups > 0 ? d->groups : 1;
     const X6Tile c = pc_x6_tile(d, groups);
+    if (d->flags & PC_F_BKMAJOR) { const int rc = x6_bkmajor_check(d, c, "pc_conv_variant"); if (rc != PC_OK) return rc; }
     const X6Split sp = x6_split(d, groups, c);
     const bool split = x6_splits(sp, ws_floats > 0);
     PC_CHECK_ARG(!split || ws_floats >= sp.ws_floats, "pc_conv_variant: the workspace holds %lld floats, this launch needs %lld (pc_conv_x6_ws_floats)",
@@ -592,6 +636,9 @@ extern "C" int pc_conv_fwd_x6_ws(const pc_conv_desc* d, const float* in, const u
                  "pc_conv_fwd_x6: channel-major output (PC_F_TOUT) is for plain launches only");
     PC_CHECK_ARG(((uintptr_t)in % 16 == 0) && ((uintptr_t)wplanes % 16 == 0) && plane_stride % 8 == 0 && d->wgstride % 8 == 0,
                  "pc_conv_fwd_x6: in / wplanes must be 16-byte aligned, plane and group strides multiples of 8 elements");
+    const bool km = (d->flags & PC_F_BKMAJOR) != 0;
+    const X6Tile c = pc_x6_tile(d, groups);
+    if (km) { const int rc = x6_bkmajor_check(d, c, "pc_conv_fwd_x6"); if (rc != PC_OK) return rc; }
     ConvX6 kx;
     ConvK& k = kx.k;
     kx.wp = wplanes; kx.wpstride = plane_stride;
@@ -611,11 +658,10 @@ extern "C" int pc_conv_fwd_x6_ws(const pc_conv_desc* d, const float* in, const u
     {   // 32-bit lane offsets from a wave-uniform base (as conv_gemm_glds_kernel)
         const long long halo = ((long long)(k.ioff0[0] < 0 ? -k.ioff0[0] : 0) * k.Hi + (k.ioff0[1] < 0 ? -k.ioff0[1] : 0)) * k.Wi + (k.ioff0[2] < 0 ? -k.ioff0[2] : 0);
         const long long in_bytes = ((long long)k.N * k.Ti * k.Hi * k.Wi + 2 * halo) * k.ldi * 4;
-        const long long w_bytes = (2 * plane_stride + (long long)k.Co * k.wtaps * k.ldw) * 2;
+        const long long w_bytes = (2 * plane_stride + (long long)(km ? k.Ci : k.Co) * k.wtaps * k.ldw) * 2;
         PC_CHECK_ARG(in_bytes < DMA_MAX_BYTES && w_bytes < DMA_MAX_BYTES,
                      "pc_conv_fwd_x6: input (%lld B) or weight planes (%lld B per group) exceed the 4 GiB the LDS-DMA gather addresses", in_bytes, w_bytes);
     }
-    const X6Tile c = pc_x6_tile(d, groups);
     const X6Split sp = x6_split(d, groups, c);
     kx.full = sp.tiles; kx.rem = 0; kx.ksplit = 1; kx.ws = nullptr; kx.ctr = nullptr;
     if (x6_splits(sp, ws != nullptr)) {
@@ -623,6 +669,11 @@ extern "C" int pc_conv_fwd_x6_ws(const pc_conv_desc* d, const float* in, const u
                      (long long)ws_floats, (long long)sp.ws_floats);
         kx.full = sp.full; kx.rem = sp.rem; kx.ksplit = sp.ksplit; kx.ws = ws;
         kx.ctr = (unsigned*)(ws + (long long)sp.rem * sp.ksplit * c.bm * c.bn);        // zero before the first use; every launch leaves them zero
+    }
+    if (km) {
+        if (c.bm == 64 && c.bn == 128) return launch_x6<64, 128, 2, 2, true>(kx, (hipStream_t)s);
+        if (c.bm == 128) return launch_x6<128, 64, 4, 1, true>(kx, (hipStream_t)s);
+        return launch_x6<64, 64, 2, 2, true>(kx, (hipStream_t)s);
     }
     if (c.bm == 256) return launch_x6<256, 128, 8, 1>(kx, (hipStream_t)s);
     if (c.bm == 128 && c.bn == 64) return launch_x6<128, 64, 4, 1>(kx, (hipStream_t)s);

@@ -9,6 +9,7 @@
 //   Y = A^T [ sum_ci sum_kt (G g_kt G^T) .* (B^T d_kt B) ] A       per 2x2 output tile, d = 4x4 input patch at (2i-1, 2j-1)
 //   B^T = [1 0 -1 0; 0 1 1 0; 0 -1 1 0; 0 1 0 -1],  G = [1 0 0; .5 .5 .5; .5 -.5 .5; 0 0 1],  A^T = [1 1 1 0; 0 1 -1 -1]
 #include "common.h"
+#include "wino_wt.h"
 #include <stdlib.h>
 #include <type_traits>
 
@@ -48,42 +49,12 @@ constexpr int WC = 64;            // output channels per block
 constexpr int WK = 8;             // input channels per K chunk
 constexpr int PLANE = 16 * 2 * 64 * 4;     // floats of one LDS operand image: [xi*4+nu][k half][row 64][4]
 
-// ---- weight transform: U[kt][ct][c8][xi*4+nu][kh][co 64][4] = (G g G^T)[xi][nu] of g = w[o][kt][.][.][i], read through strides so
-// the master OIDHW tensor (forward) and its transpose with mirrored taps (input gradient) need no intermediate layout.
+// ---- weight transform (wino_wt.h): one thread per (tap frame, output channel, input channel)
 __global__ void wino_weights_kernel(const float* __restrict__ w, long long sO, long long sT, long long sI, int O, int I, int KT, int flip,
                                     float* __restrict__ U, int nct, int nc8) {
     const long long e = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-    const long long total = (long long)KT * nct * 64 * I;
-    if (e >= total) return;
-    const int i = (int)(e % I);
-    long long r = e / I;
-    const int o = (int)(r % (nct * 64));
-    const int kt = (int)(r / (nct * 64));
-    float g[3][3];
-#pragma unroll
-    for (int a = 0; a < 3; ++a)
-#pragma unroll
-        for (int b = 0; b < 3; ++b) {
-            const int ks = flip ? KT - 1 - kt : kt, as = flip ? 2 - a : a, bs = flip ? 2 - b : b;
-            g[a][b] = o < O ? w[(long long)o * sO + (long long)((ks * 3 + as) * 3 + bs) * sT + (long long)i * sI] : 0.f;
-        }
-    float t[4][3];          // G g
-#pragma unroll
-    for (int b = 0; b < 3; ++b) {
-        t[0][b] = g[0][b];
-        t[1][b] = 0.5f * (g[0][b] + g[1][b] + g[2][b]);
-        t[2][b] = 0.5f * (g[0][b] - g[1][b] + g[2][b]);
-        t[3][b] = g[2][b];
-    }
-    float* dst = U + ((((long long)kt * nct + o / 64) * nc8 + i / 8) * 16) * (2 * 64 * 4) + ((long long)((i & 7) >> 2) * 64 + (o & 63)) * 4 + (i & 3);
-#pragma unroll
-    for (int x = 0; x < 4; ++x) {
-        const float u0 = t[x][0], u1 = 0.5f * (t[x][0] + t[x][1] + t[x][2]), u2 = 0.5f * (t[x][0] - t[x][1] + t[x][2]), u3 = t[x][2];
-        dst[(x * 4 + 0) * (2 * 64 * 4)] = u0;
-        dst[(x * 4 + 1) * (2 * 64 * 4)] = u1;
-        dst[(x * 4 + 2) * (2 * 64 * 4)] = u2;
-        dst[(x * 4 + 3) * (2 * 64 * 4)] = u3;
-    }
+    if (e >= (long long)KT * nct * 64 * I) return;
+    wino2_weights_elem(e, w, sO, sT, sI, O, I, KT, flip, U, nct, nc8);
 }
 
 // ---- the fused convolution.  Block = 64 tiles (a BTH x BTW rectangle of 2x2-output tiles of one (n, t) plane) x 64 output channels,

@@ -13,6 +13,7 @@
 //   B^T = [a2b2 0 -(a2+b2) 0 1 0; 0 -+ab2 -b2 +-a 1 0 (p = +-a); 0 -+a2b -a2 +-b 1 0 (p = +-b); 0 a2b2 0 -(a2+b2) 0 1]
 //   G   = [1/(a2b2) 0 0; (1 +-a a2) / (2a2(a2-b2)); (1 +-b b2) / (2b2(b2-a2)); 0 0 1]          A^T columns = (1 p p2 p3), last (0 0 0 1)
 #include "common.h"
+#include "wino_wt.h"
 #include <stdlib.h>
 #include <type_traits>
 
@@ -65,11 +66,8 @@ constexpr int RPIECES = 12;       // 1 KiB LDS-DMA pieces of one raw patch image
 constexpr int RPLANE = RPIECES * 256;
 
 // ---- weight transform: U[kt][ct][c4][P / 2][k half][co 64][P % 2][2] = (G g G^T)[xi][nu] of g = w[o][kt][.][.][i], read through strides (see wino.hip)
-__global__ void wino4_weights_kernel(const float* __restrict__ w, long long sO, long long sT, long long sI, int O, int I, int KT, int flip,
-                                     float* __restrict__ U, int nct, int nc4) {
-    const long long e = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-    const long long total = (long long)KT * nct * 64 * I;
-    if (e >= total) return;
+__device__ __forceinline__ void wino4_weights_elem(long long e, const float* __restrict__ w, long long sO, long long sT, long long sI, int O, int I, int KT, int flip,
+                                                   float* __restrict__ U, int nct, int nc4) {
     const int i = (int)(e % I);
     long long r = e / I;
     const int o = (int)(r % (nct * 64));
@@ -113,6 +111,28 @@ __global__ void wino4_weights_kernel(const float* __restrict__ w, long long sO, 
             dst[(P >> 1) * (2 * 64 * 4) + (P & 1) * 2] = (float)u[nu];
         }
     }
+}
+
+__global__ void wino4_weights_kernel(const float* __restrict__ w, long long sO, long long sT, long long sI, int O, int I, int KT, int flip,
+                                     float* __restrict__ U, int nct, int nc4) {
+    const long long e = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (e >= (long long)KT * nct * 64 * I) return;
+    wino4_weights_elem(e, w, sO, sT, sI, O, I, KT, flip, U, nct, nc4);
+}
+
+// Many weight-transform jobs of either form in one launch (the per-step transforms of every Winograd layer on one prep lane: 26 dependent
+// launches of 4 - 16 us otherwise); the jobs travel by value in the kernel arguments, a block belongs to one job (as split_planes_multi_kernel)
+constexpr int WW_JOBS = 32;
+struct WinoWJobK { const float* w; float* U; long long sO, sT, sI; int O, I, KT, flip, m, nct, ncc; };
+struct WinoWPack { WinoWJobK j[WW_JOBS]; int first[WW_JOBS + 1]; int n; };
+__global__ __launch_bounds__(256) void wino_weights_multi_kernel(const WinoWPack pk) {
+    int k = 0;
+    while (k + 1 < pk.n && (int)blockIdx.x >= pk.first[k + 1]) ++k;
+    const WinoWJobK& J = pk.j[k];
+    const long long e = (long long)((int)blockIdx.x - pk.first[k]) * 256 + threadIdx.x;
+    if (e >= (long long)J.KT * J.nct * 64 * J.I) return;
+    if (J.m == 4) wino4_weights_elem(e, J.w, J.sO, J.sT, J.sI, J.O, J.I, J.KT, J.flip, J.U, J.nct, J.ncc);
+    else wino2_weights_elem(e, J.w, J.sO, J.sT, J.sI, J.O, J.I, J.KT, J.flip, J.U, J.nct, J.ncc);
 }
 
 // ---- the fused convolution.  Block = 32 tiles (a BTH x BTW rectangle of 4x4-output tiles of one (n, t) plane) x 64 output channels; four
@@ -606,6 +626,31 @@ extern "C" int pc_wino4_weights(const float* w, int64_t sO, int64_t sT, int64_t 
     const long long total = (long long)KT * nct * 64 * I;
     hipLaunchKernelGGL(wino4_weights_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)s, w, (long long)sO, (long long)sT, (long long)sI, O, I, KT, flip, U, nct, nc4);
     PC_CHECK_LAUNCH("wino4_weights_kernel");
+    return PC_OK;
+}
+
+extern "C" int pc_wino_weights_multi(const pc_wino_weights_job* jobs, int njobs, pc_stream s) {
+    PC_CHECK_ARG(jobs && njobs >= 1, "pc_wino_weights_multi: bad args");
+    for (int j0 = 0; j0 < njobs; j0 += WW_JOBS) {
+        WinoWPack pk;
+        pk.n = njobs - j0 < WW_JOBS ? njobs - j0 : WW_JOBS;
+        long long blocks = 0;
+        for (int q = 0; q < pk.n; ++q) {
+            const pc_wino_weights_job& a = jobs[j0 + q];
+            PC_CHECK_ARG(a.w && a.U && a.O >= 1 && a.I >= 8 && a.I % 8 == 0 && (a.KT == 1 || a.KT == 3) && (a.m == 0 || a.m == 2 || a.m == 4) && (a.flip == 0 || a.flip == 1),
+                         "pc_wino_weights_multi: bad job %d (O=%d I=%d KT=%d m=%d flip=%d)", j0 + q, a.O, a.I, a.KT, a.m, a.flip);
+            WinoWJobK& J = pk.j[q];
+            J.w = (const float*)(uintptr_t)a.w; J.U = (float*)(uintptr_t)a.U; J.sO = a.sO; J.sT = a.sT; J.sI = a.sI;
+            J.O = a.O; J.I = a.I; J.KT = a.KT; J.flip = a.flip; J.m = a.m == 4 ? 4 : 2;
+            J.nct = cdiv(a.O, 64); J.ncc = J.m == 4 ? a.I / XK : a.I / 8;        // channel chunks of U: 4 per chunk in F(4x4), 8 in F(2x2)
+            pk.first[q] = (int)blocks;
+            blocks += ((long long)a.KT * J.nct * 64 * a.I + 255) / 256;
+            PC_CHECK_ARG(blocks < (1ll << 31), "pc_wino_weights_multi: too many elements");
+        }
+        pk.first[pk.n] = (int)blocks;
+        hipLaunchKernelGGL(wino_weights_multi_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)s, pk);
+        PC_CHECK_LAUNCH("wino_weights_multi_kernel");
+    }
     return PC_OK;
 }
 

@@ -93,6 +93,14 @@ def wino_weights(w, O, I, KT=3, flip=False, strides=None, out=None, m=2):
     return U
 
 
+def wino_weights_multi(jobs):
+    """pc_wino_weights_multi: jobs = [(w, U, (sO, sT, sI), O, I, KT, flip, m)] with device tensors w, U -- every job in ONE launch."""
+    tab = np.zeros(len(jobs), dtype=capi.WWJOB_DTYPE)
+    for q, (w, U, st, O, I, KT, flip, m) in enumerate(jobs):
+        tab[q] = (w.data_ptr(), U.data_ptr(), st[0], st[1], st[2], O, I, KT, int(flip), m, 0)
+    capi.call("pc_wino_weights_multi", C.c_void_p(tab.ctypes.data), len(jobs), stream())
+
+
 def wino_conv(d, x, U, out, bias=None, bnpart=None):
     capi.call("pc_wino_conv", C.byref(d), ptr(x), ptr(U), ptr(bias), ptr(out), ptr(bnpart), stream())
     return out

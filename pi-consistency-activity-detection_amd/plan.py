@@ -1082,6 +1082,7 @@ class Plan:
         npose = spec.IN_CAPS * spec.POSE
         caps_in = self.tensor(N, (1, s20, s20), npose + spec.IN_CAPS, "caps_in")
         spectral_pc = self.spectral_pc and xd.thw[0] == 1
+        pc_dgrad_wv = False
         Cpc = npose + spec.IN_CAPS
         pc_names = [("primary_caps.pose.weight", 0, npose), ("primary_caps.a.weight", npose, spec.IN_CAPS)]
         if spectral_pc:
@@ -1094,12 +1095,20 @@ class Plan:
             nW = SL.G * SL.w_g
             x6_pc = self.x6 and sw.get("PICONS_SPLIT_SPECTRAL", "1") != "0" and all(capi.lib().pc_conv_x6_ok(_cdesc(dict(D.trim_conv(dd), flags=dd["flags"] | capi.F_X6))) for dd in [SL.conv()] + SL.dgrad())
             if x6_pc:
-                # the 2 x 167 M-element weight planes leave the producer as bf16 terms (6 B per element): no fp32 copy exists, the
+                # the 167 M-element weight planes leave the producer as bf16 terms (6 B per element): no fp32 copy exists, the
                 # "fp32" references below are virtual addresses that only locate a group inside the planes
-                wpc = dict(wv=("V", 0), wvt=("V", 4 * nW))
-                pf, pt = self.alloc((3 * nW + 1) // 2), self.alloc((3 * nW + 1) // 2)
+                # The input gradient reads the forward planes as they are (capi.F_BKMAJOR: its B tile is fetched K-major and transposed by
+                # the LDS read), so the transposed layout -- half of the prep's bytes, a second pass over the master weight and 1 GB of
+                # arena -- is not made.  PICONS_PC_DGRAD_WV=0, or a clip count whose tile the flagged kernel is not built for: both layouts.
+                pc_dgrad_wv = sw.get("PICONS_PC_DGRAD_WV", "1") != "0" and all(
+                    capi.variant_ok("pc_conv_variant", _cdesc(dict(D.trim_conv(dd), flags=dd["flags"] | capi.F_X6)), 0)
+                    for dd in SL.dgrad(fwd_planes=True))
+                wpc = dict(wv=("V", 0), wvt=("V", 0 if pc_dgrad_wv else 4 * nW))
+                pf = self.alloc((3 * nW + 1) // 2)
+                pt = None if pc_dgrad_wv else self.alloc((3 * nW + 1) // 2)
                 self.wbufs.append(dict(ref=wpc["wv"], n=nW, lst=None, lane=None, planes=pf))
-                self.wbufs.append(dict(ref=wpc["wvt"], n=nW, lst=None, lane=None, planes=pt))
+                if pt is not None:
+                    self.wbufs.append(dict(ref=wpc["wvt"], n=nW, lst=None, lane=None, planes=pt))
                 for nm, a0, cnt in pc_names:
                     self.emit(capi.OP_WSPEC_MASTER_PLANES, i=[cnt, a0, Cpc, xd.C, KP, KP, SL.nu, SL.Ur], l=[nW], p=[self.P(nm), sm["tw"], pf, pt],
                               lst=self.prep_target, lane=pl)
@@ -1181,7 +1190,7 @@ class Plan:
             if spectral_pc:
                 dxpl = self.alloc(SL.G * SL.x_g)
                 self.alg_dgrad(SL.flops())
-                for dd in SL.dgrad():
+                for dd in SL.dgrad(fwd_planes=pc_dgrad_wv):
                     self.conv_op(dd, dtpl, wpc["wvt"], dxpl, alg=0)
                 self.emit(capi.OP_AXIS, i=D.flatten(SL.planes_to_dx(dx.ld, acc), capi.AXIS_FIELDS), p=[dxpl, sm["Ft"], None, dx.ref])
             elif xd.thw[0] == 1 and caps_in.thw[1] + KP - 1 == xd.thw[1]:
@@ -1582,8 +1591,9 @@ class Plan:
 
     def _merge_prep_transposes(self, lst, bases, keep):
         """The weight re-layouts that read master parameters are independent of each other: all of them on one lane
-        become ONE launch (pc_transpose_multi, jobs passed by value) instead of ~80 seven-microsecond launches."""
-        res, pending, splits = [], {}, {}
+        become ONE launch (pc_transpose_multi, jobs passed by value) instead of ~80 seven-microsecond launches.  The same for the Winograd
+        weight transforms (pc_wino_weights_multi: 26 launches of 4 - 16 us, each behind the last on its lane)."""
+        res, pending, splits, winos = [], {}, {}, {}
 
         def flush():
             for lane in sorted(pending):
@@ -1592,6 +1602,13 @@ class Plan:
                 keep.append(tab)
                 res.append((capi.OP_TRANSPOSE_MULTI, [len(jobs)], [], [("HOST", tab.ctypes.data)], [], lane))
             pending.clear()
+            for lane in sorted(winos):
+                tab = np.zeros(len(winos[lane]), dtype=capi.WWJOB_DTYPE)
+                for q, (_k, i, _f, p, l, _lane) in enumerate(winos[lane]):
+                    tab[q] = (bases[p[0][0]] + p[0][1], bases[p[1][0]] + p[1][1], l[0], l[1], l[2], i[0], i[1], i[2], i[3], i[4], 0)
+                keep.append(tab)
+                res.append((capi.OP_WINO_WEIGHTS_MULTI, [len(tab)], [], [("HOST", tab.ctypes.data)], [], lane))
+            winos.clear()
             for lane in sorted(splits):          # the bf16 planes of the buffers those transposes filled: one launch per lane, behind them
                 res.append((capi.OP_SPLIT_PLANES_MULTI, [len(splits[lane])], [], [("SJOBS", splits[lane])], [], lane))
             splits.clear()
@@ -1600,6 +1617,8 @@ class Plan:
                 splits.setdefault(op[5], []).append((op[3][0], op[3][1], op[4][0], op[4][1]))
             elif op[0] == capi.OP_TRANSPOSE and op[3][0][0] == "P":
                 pending.setdefault(op[5], []).append(op)
+            elif op[0] == capi.OP_WINO_WEIGHTS and op[3][0][0] == "P":
+                winos.setdefault(op[5], []).append(op)
             elif op[0] in (capi.OP_FILL, capi.OP_FORK, capi.OP_WSPEC_MASTER_FWD, capi.OP_WSPEC_MASTER_PLANES, capi.OP_WINO_WEIGHTS):
                 res.append(op)           # fills precede the transposes into their buffer; the fork opens the region; the
                                          # master-layout weight planes touch nothing the transposes do

@@ -118,7 +118,8 @@ def axis(R, I, O, C, in_sr, in_hi, in_lo, in_split, out_sr, out_hi, out_lo, out_
 class Layout:
     """Extents and descriptors of one spectral PrimaryCaps instance: x [N][H][W][Ci] (row stride ldx) ->
     y [N][OH][OW][Co] (row stride ldy), kernel KY x KX, W = P.  Groups g = 3*u + j; operand planes X [g][n][iy][Ci],
-    result planes T [g][n][oy][Co], weight planes [g][Co][KY][Ci] (forward) / [g][Ci][KY][Co] (dgrad)."""
+    result planes T [g][n][oy][Co], weight planes [g][Co][KY][Ci] (forward; also read by the dgrad of the bf16-split kernel,
+    dgrad(fwd_planes=True)) / [g][Ci][KY][Co] (dgrad otherwise)."""
 
     def __init__(self, N, H, W, Ci, ldx, Co, ldy, KY, KX):
         self.N, self.H, self.W, self.Ci, self.ldx, self.Co, self.ldy, self.KY, self.KX = N, H, W, Ci, ldx, Co, ldy, KY, KX
@@ -151,11 +152,14 @@ class Layout:
         d["wgstride"] = self.w_g
         return d
 
-    def dgrad(self):
+    def dgrad(self, fwd_planes=False):
         # sample-fastest row order inside each group: a 64-row tile is 4 rows of y for all samples, so the taps that only
-        # reach the zero padding of the 'full' correlation (H rows gathered from OH real ones) are skipped per tile
+        # reach the zero padding of the 'full' correlation (H rows gathered from OH real ones) are skipped per tile.
+        # fwd_planes: the launch reads the FORWARD weight planes [g][Co][ky][Ci] as they are (bf16-split kernel only, capi.F_BKMAJOR:
+        # rows = its contraction channel, Ci contiguous) instead of a transposed copy [g][Ci][ky][Co]
         out = D.transposed_classes(self.G * self.N, (1, self.OH, 1), self.Co, self.Co, (1, self.H, 1), self.Ci, self.Ci,
-                                   (1, self.KY, 1), (1, 1, 1), (0, 0, 0), groups=self.G, ldw=self.Co, flags=capi.F_NFAST)
+                                   (1, self.KY, 1), (1, 1, 1), (0, 0, 0), groups=self.G, ldw=self.Ci if fwd_planes else self.Co,
+                                   flags=capi.F_NFAST | (capi.F_BKMAJOR if fwd_planes else 0))
         for d in out:
             d["wgstride"] = self.w_g
         return out
