@@ -63,10 +63,10 @@ typedef void* pc_stream;            /* hipStream_t */
 /* ABI version of this header: bumped whenever a struct in it grows or an op's operands change (101: pc_wino_desc.m, PC_OP_BN_FIN_APPLY,
  * pc_wgrad_desc.ws_slices, pc_transpose_job.nslices / slice_stride, pc_wgrad_slices; 102: the workspace operands of PC_OP_TAIL6_WGRAD_MAP / PC_OP_TAIL6_BIAS_SUMS /
  * PC_OP_TAIL_GRADS; 103: the variant reporters pc_conv_variant / pc_wino_variant / pc_wgrad_variant;
- * 104: PC_F_BKMAJOR, pc_wino_weights_multi / PC_OP_WINO_WEIGHTS_MULTI).  Descriptors must be zero-initialised by the caller:
+ * 104: PC_F_BKMAJOR, pc_wino_weights_multi / PC_OP_WINO_WEIGHTS_MULTI; 105: pc_val_metrics / PC_OP_VAL_METRICS).  Descriptors must be zero-initialised by the caller:
  * fields added later read as "old behaviour" when 0.  pc_version() returns the value the library was built with; the Python host
  * (capi.lib()) refuses a library whose version differs from the header it mirrors. */
-#define PC_VERSION 104
+#define PC_VERSION 105
 int         pc_version(void);
 const char* pc_last_error(void);
 
@@ -351,6 +351,23 @@ int pc_col2im(const float* cols, int N, int Ho, int Wo, int KH, int KW, int C, f
 int pc_seg_frame_counts(const float* logits, const float* gt, int64_t nframes, int64_t pix, int32_t* counts, pc_stream s);
 int pc_map_accumulate(const int32_t* counts, int64_t nframes, int label, int ncls, int32_t* frame_hits, int32_t* video_hits,
                       int32_t* n_frames, int32_t* n_vids, pc_stream s);
+/* Validation pass (main_ucf101.py:33-47 val_model_interface and the loop body of validate :241-264) on one batch: `output` [B][pix]
+ * logits and `loc_msk` [B][pix] truth (fp32, values in {0, 1}; pix = 8*H*W, a multiple of 4, both 16-byte aligned),
+ * `predicted_action` [B][C], `action` [B] (int32 class ids).  One record of pc_val_record_words(B) = 10 + 3*B 32-bit words:
+ *   float  [0] total = loc + cls   [1] loc = bce + dice   [2] cls   [3] abs_cls   (SpreadLoss over all B rows, utils/losses.py:14-37, margin 0.2)
+ *          [4] bce = mean of max(x,0) - x*y + log1p(exp(-|x|))   [5] dice = 1 - (2*sum(s*y) + 1) / (sum(s) + sum(y) + 1), s = sigmoid(x)
+ *          [6] sum of inter/union over the clips with gt > 0   [7] their number
+ *   int32  [8] n_correct: rows whose arg-max (first maximum) equals action   [9] B
+ *          [10 + 3*b ..] per clip: inter = #(x > 0 and y != 0), union = #(x > 0 or y != 0), gt = #(y != 0) -- the sums IOU2 takes
+ *          (utils/metrics.py:171-193) for the mask `output > 0` (strict, validate :255; NOT the sigmoid(x) >= 0.5 of pc_seg_frame_counts).
+ * Per-element terms are fp32, sums double; block partials go to `ws` (pc_val_metrics_ws_floats(B, pix) floats, 16-byte aligned, contents
+ * irrelevant before the call) and are added in block order: no floating-point atomics, the record is bit-identical from run to run.  A row
+ * whose action is outside [0, C) makes cls / abs_cls / total NaN and is not counted as correct.  The two size functions are host-only and
+ * return -1 for a B or pix the call would refuse. */
+int     pc_val_record_words(int B);
+int64_t pc_val_metrics_ws_floats(int B, int64_t pix);
+int     pc_val_metrics(const float* output, const float* loc_msk, const float* predicted_action, const int32_t* action, int B, int64_t pix,
+                       int C, int32_t* record, float* ws, pc_stream s);
 /* ------------------------------------------------------------------------------------------
  * Input pipeline (datasets/ucf_dataloader.py:146-173 and the box rasterisation of load_video :204-221): from the decoded
  * uint8 frames `video` [F][H][W][3] in HBM, the 8 frames `span8` (host array), the S x S crop at (h0, w0): data =
@@ -584,6 +601,7 @@ enum {
     PC_OP_BN_FIN_APPLY,             /* i = npg, groups, C, ldz, ldy, relu; l = count per group, rows; f = eps, momentum; p = part, gamma, beta, running_mean, running_var, stat, z, y */
     PC_OP_WGRAD_FOLD,               /* i[0] = nslices; l[0] = image floats; p = ws: pc_wgrad_fold */
     PC_OP_WINO_WEIGHTS_MULTI,       /* p[0] = HOST pointer to pc_wino_weights_job[i[0]] (kept alive by the owner of the list) */
+    PC_OP_VAL_METRICS,              /* i = B, C; l[0] = pix; p = output, loc_msk, predicted_action, action, record, ws: pc_val_metrics */
     PC_OP__COUNT
 };
 #define PC_MAX_LANES 8

@@ -61,7 +61,7 @@ OP_DTYPE = np.dtype([("kind", np.int32), ("i", np.int32, 48), ("f", np.float32, 
  OP_ACT_BWD, OP_TO_NDHWC, OP_TO_NCDHW, OP_TRANSPOSE, OP_FILL, OP_AXPY, OP_EM_FWD, OP_EM_BWD, OP_CMASK_FWD, OP_CMASK_BWD,
  OP_TAPSUM_FWD, OP_TAPSUM_BWD, OP_LOSS, OP_SPREAD, OP_ADAM, OP_TAIL_COMBINE, OP_TAIL_COLSUM, OP_TAIL_GRADS, OP_COL2IM,
  OP_AXIS, OP_WSPEC_FWD, OP_WSPEC_BWD, OP_WSPEC_MASTER_FWD, OP_WSPEC_MASTER_BWD, OP_TAIL6_WEIGHTS, OP_TAIL6_GATHER, OP_TAIL6_SCATTER, OP_TAIL6_WGRAD_MAP, OP_TAIL6_BIAS_SUMS,
- OP_TRANSPOSE_MULTI, OP_FORK, OP_JOIN, OP_WGRAD_MULTI, OP_WINO_CONV, OP_WINO_WEIGHTS, OP_CONV_X6, OP_SPLIT_PLANES, OP_SPLIT_PLANES_MULTI, OP_WSPEC_MASTER_PLANES, OP_BN_FIN_APPLY, OP_WGRAD_FOLD, OP_WINO_WEIGHTS_MULTI) = range(1, 52)
+ OP_TRANSPOSE_MULTI, OP_FORK, OP_JOIN, OP_WGRAD_MULTI, OP_WINO_CONV, OP_WINO_WEIGHTS, OP_CONV_X6, OP_SPLIT_PLANES, OP_SPLIT_PLANES_MULTI, OP_WSPEC_MASTER_PLANES, OP_BN_FIN_APPLY, OP_WGRAD_FOLD, OP_WINO_WEIGHTS_MULTI, OP_VAL_METRICS) = range(1, 53)
 MAX_LANES = 8
 
 # numpy mirror of struct pc_wgrad_job (pc_wgrad_desc = 42 int32, then D, S, g)
@@ -84,7 +84,7 @@ F_ACCUM, F_BIAS, F_CSCALE, F_BNPART, F_NFAST, F_TOUT, F_CI3, F_X6, F_STRIPS = 1,
 F_BKMAJOR = 512             # with F_X6: K-major weight planes [Ci][taps][ldw] (a layer's forward planes read by its input gradient)
 WG_CS3, WG_X6 = 1, 2
 
-ABI_VERSION = 104          # PC_VERSION of include/picons.h
+ABI_VERSION = 105          # PC_VERSION of include/picons.h
 
 _SIGS = {
     "pc_version": (i32, []),
@@ -136,6 +136,9 @@ _SIGS = {
     "pc_col2im": (i32, [vp, i32, i32, i32, i32, i32, i32, vp, i32, i32, vp]),
     "pc_seg_frame_counts": (i32, [vp, vp, i64, i64, vp, vp]),
     "pc_map_accumulate": (i32, [vp, i64, i32, i32, vp, vp, vp, vp, vp]),
+    "pc_val_record_words": (i32, [i32]),
+    "pc_val_metrics_ws_floats": (i64, [i32, i64]),
+    "pc_val_metrics": (i32, [vp, vp, vp, vp, i32, i64, i32, vp, vp, vp]),
     "pc_clip_from_u8": (i32, [vp, i32, i32, i32, C.POINTER(C.c_int32), i32, i32, i32, vp, i32, vp, vp, vp, vp]),
     "pc_clip_from_u8_ndhwc4": (i32, [vp, i32, i32, i32, C.POINTER(C.c_int32), i32, i32, i32, vp, i32, vp, vp, vp, vp]),
     "pc_clip_from_u8_masks": (i32, [vp, i32, i32, i32, C.POINTER(C.c_int32), i32, i32, i32, vp, C.POINTER(C.c_int32), vp, vp, vp, vp, vp]),

@@ -171,6 +171,9 @@ static int run_one(const pc_op& op, pc_stream s) {
             return pc_wino_weights(P(const float*, 0), op.l[0], op.l[1], op.l[2], op.i[0], op.i[1], op.i[2], op.i[3], P(float*, 1), s);
         case PC_OP_WINO_WEIGHTS_MULTI:
             return pc_wino_weights_multi(P(const pc_wino_weights_job*, 0), op.i[0], s);
+        case PC_OP_VAL_METRICS:
+            return pc_val_metrics(P(const float*, 0), P(const float*, 1), P(const float*, 2), P(const int32_t*, 3), op.i[0], op.l[0], op.i[1], P(int32_t*, 4),
+                                  P(float*, 5), s);
         default:
             pc_set_error("pc_run_ops: unknown op kind %d", op.kind);
             return PC_E_ARG;

@@ -36,7 +36,7 @@ from utils.losses import SpreadLoss, DiceLoss, weighted_mse_loss  # noqa: E402
 from utils.metrics import get_accuracy, IOU2  # noqa: E402
 from utils.helpers import measure_pixelwise_var_v2, measure_pixelwise_gradient  # noqa: E402
 from utils import ramp_ups  # noqa: E402
-from picons_amd import dist as pdist, step as pstep, synthetic  # noqa: E402
+from picons_amd import dist as pdist, step as pstep, synthetic, valstep as pval  # noqa: E402
 
 NUM_CLASSES = 24
 DATASET = "ucf101"
@@ -234,8 +234,16 @@ def train(args, model, labeled_train_loader, unlabeled_train_loader, optimizer, 
     return float(np.array(total_loss).mean())
 
 
-def validate(model, val_data_loader, epoch):
-    """main_ucf101.py:226-278."""
+def validate(model, val_data_loader, epoch, engine=None):
+    """main_ucf101.py:226-278.  engine (picons_amd.valstep.ValEngine): the pass runs on the device -- forward, losses, IoU sums and accuracy
+    per batch with no host round trip, one read-back at the end."""
+    if engine is not None:
+        engine.begin()
+        for minibatch in val_data_loader:
+            engine.val_step(minibatch)
+        s = pval.summarize(engine.results(), epoch)
+        print(s['line'])
+        return s['total']
     model.eval()
     model.training = False
     total_loss, accuracy, total_IOU, validiou = [], [], 0, 0
@@ -344,7 +352,7 @@ def run(args):
     optimizer = optim.Adam(model.parameters(), lr=args.lr, weight_decay=0, eps=1e-6)
     scheduler = optim.lr_scheduler.ReduceLROnPlateau(optimizer, 'min', min_lr=1e-7, patience=5, factor=0.1)
     ramp_wt = ramp_ups.exp_rampup(args.epochs)
-    engine = reducer = None
+    engine = reducer = val_engine = None
     if world > 1 and not fused:
         # the nn.Module path has no gradient exchange: N ranks would train N independent models and rank 0's would be saved
         raise RuntimeError("WORLD_SIZE > 1 needs the fused step (PICONS_FUSED=1): the autograd path does no gradient all-reduce")
@@ -353,6 +361,7 @@ def run(args):
         engine = pstep.StepEngine(args, bs=2 * (args.bs // 2), hw=hw, num_classes=NUM_CLASSES, jhmdb=(DATASET == "jhmdb"), state=model.state_dict(),
                                   device="cuda:%d" % local)
         reducer = engine.make_reducer() if world > 1 else None
+        val_engine = engine.val_engine(args.bs)           # validates the step engine's own weights (validation batches hold args.bs clips)
     save_path = os.path.join('train_log_wts', args.exp_id)
     model_save_dir = os.path.join(save_path, time.strftime('%m-%d-%H-%M'))
     os.makedirs(model_save_dir, exist_ok=True)
@@ -361,8 +370,8 @@ def run(args):
     for e in range(1, args.epochs + 1):
         train_loss = train(args, model, labeled_loader, unlabeled_loader, optimizer, e, save_path, None, ramp_wt, engine, reducer)
         if engine is not None:
-            model.load_state_dict(engine.state_dict())
-        val_loss = validate(model, val_loader, e)
+            model.load_state_dict(engine.state_dict())           # the checkpoints below are written from `model`
+        val_loss = validate(model, val_loader, e, val_engine)
         # data parallel: every rank must take the same scheduler / checkpoint decisions, so they are taken on the mean of the
         # per-rank losses (each rank saw its own shard); otherwise ReduceLROnPlateau fires on one rank and the replicas
         # train at different learning rates from then on

@@ -476,6 +476,47 @@ def map_accumulate(counts, label, frame_hits, video_hits, n_frames, n_vids):
               ptr(n_frames), ptr(n_vids), stream())
 
 
+VAL_SCALARS = ("total", "loc", "cls", "abs_cls", "bce", "dice", "iou_sum", "iou_clips")     # words 0..7 of a pc_val_metrics record (float32)
+VAL_HEAD = 10                                                                                # then n_correct, B (int32), then [B][3] counts
+
+
+def val_record_words(B):
+    return int(capi.lib().pc_val_record_words(int(B)))
+
+
+def val_metrics_ws_floats(B, pix):
+    return int(capi.lib().pc_val_metrics_ws_floats(int(B), int(pix)))
+
+
+def val_metrics(output, loc_msk, predicted_action, action, record=None, ws=None):
+    """pc_val_metrics: output / loc_msk contiguous float32 device tensors (B, ..., H, W) of equal size, predicted_action (B, C) float32,
+    action (B,) int32 -> int32 record of val_record_words(B) words (words 0..7 are float32 bit patterns: decode_val_record)."""
+    for t in (output, loc_msk, predicted_action):
+        if t.dtype != torch.float32 or not t.is_contiguous():
+            raise ValueError("val_metrics: contiguous float32 tensors")
+    if action.dtype != torch.int32 or not action.is_contiguous():
+        raise ValueError("val_metrics: action must be contiguous int32")
+    B, C_ = predicted_action.shape
+    if output.shape[0] != B or loc_msk.numel() != output.numel() or action.numel() != B:
+        raise ValueError("val_metrics: %s logits, %s truth, %s scores, %s actions" % (tuple(output.shape), tuple(loc_msk.shape), (B, C_), tuple(action.shape)))
+    pix = output.numel() // B
+    if record is None:
+        record = torch.empty(max(val_record_words(B), 1), dtype=torch.int32, device=output.device)
+    if ws is None:
+        ws = torch.empty(max(val_metrics_ws_floats(B, pix), 4), dtype=torch.float32, device=output.device)
+    capi.call("pc_val_metrics", ptr(output), ptr(loc_msk), ptr(predicted_action), ptr(action), B, pix, C_, ptr(record), ptr(ws), stream())
+    return record
+
+
+def decode_val_record(rec):
+    """One record (host int32 array, numpy or torch) -> dict: the eight float scalars by name, n_correct, B, counts int32 [B][3]."""
+    r = np.ascontiguousarray(rec.cpu().numpy() if torch.is_tensor(rec) else rec, dtype=np.int32)
+    B = int(r[9])
+    out = {k: float(v) for k, v in zip(VAL_SCALARS, r[:8].view(np.float32))}
+    out.update(n_correct=int(r[8]), B=B, counts=r[VAL_HEAD:VAL_HEAD + 3 * B].reshape(B, 3).copy())
+    return out
+
+
 def clip_from_u8(video, span, h0, w0, rects, S=224, out=None, ndhwc4=False):
     """video: uint8 device tensor [F,H,W,3]; span: 8 frame ids; rects: int32 device tensor [8,R,4] (x0,x1,y0,y1) or None.
     -> data, aug [3,8,S,S] float32, mask [8,S,S] float32 (pc_clip_from_u8).  out: (data, aug, mask) contiguous float32 device tensors of those

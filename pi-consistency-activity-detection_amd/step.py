@@ -496,6 +496,12 @@ class StepEngine:
         pred = self.aview(p.pred, 2 * n * self.C).view(2 * n, self.C)
         return out[:n], out[n:], pred[:n]
 
+    def val_engine(self, bs=None, capacity=64):
+        """-> valstep.ValEngine over THIS engine's parameter and running-statistics buffers (no copy: a validation pass sees what the last
+        train step left) and behind its lanes; arenas, record table and staging are the ValEngine's own.  bs: the largest validation batch."""
+        from .valstep import ValEngine
+        return ValEngine(self.bs if bs is None else bs, capacity=capacity, engine=self)
+
     def make_reducer(self, group=None, target_floats=3_000_000, force=False, check=True):
         """check: refuse to train if the ranks do not hold identical parameters (dist.check_replicas_agree: one 3-number all-reduce)."""
         from . import dist as pdist
