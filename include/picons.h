@@ -63,10 +63,11 @@ typedef void* pc_stream;            /* hipStream_t */
 /* ABI version of this header: bumped whenever a struct in it grows or an op's operands change (101: pc_wino_desc.m, PC_OP_BN_FIN_APPLY,
  * pc_wgrad_desc.ws_slices, pc_transpose_job.nslices / slice_stride, pc_wgrad_slices; 102: the workspace operands of PC_OP_TAIL6_WGRAD_MAP / PC_OP_TAIL6_BIAS_SUMS /
  * PC_OP_TAIL_GRADS; 103: the variant reporters pc_conv_variant / pc_wino_variant / pc_wgrad_variant;
- * 104: PC_F_BKMAJOR, pc_wino_weights_multi / PC_OP_WINO_WEIGHTS_MULTI; 105: pc_val_metrics / PC_OP_VAL_METRICS).  Descriptors must be zero-initialised by the caller:
+ * 104: PC_F_BKMAJOR, pc_wino_weights_multi / PC_OP_WINO_WEIGHTS_MULTI; 105: pc_val_metrics / PC_OP_VAL_METRICS;
+ * 106: pc_truth_frame_flags / pc_eval_clips_from_u8 / pc_video_vote).  Descriptors must be zero-initialised by the caller:
  * fields added later read as "old behaviour" when 0.  pc_version() returns the value the library was built with; the Python host
  * (capi.lib()) refuses a library whose version differs from the header it mirrors. */
-#define PC_VERSION 105
+#define PC_VERSION 106
 int         pc_version(void);
 const char* pc_last_error(void);
 
@@ -387,6 +388,21 @@ int pc_clip_from_u8_masks(const uint8_t* video, int F, int H, int W, const int32
  * needs no layout conversion at all (StepEngine.sample_stager); mask as pc_clip_from_u8.  data / aug 16-byte aligned. */
 int pc_clip_from_u8_ndhwc4(const uint8_t* video, int F, int H, int W, const int32_t* span8, int h0, int w0, int S,
                            const int32_t* rects, int R, float* data, float* aug, float* mask, pc_stream s);
+/* Evaluation input (evaluate_ucf101.py:79-101, :139-146) from one decoded video in HBM: `video` uint8 [F][H][W][3], `truth` uint8 [F][H][W], the
+ * S x S crop at (h0, w0) (the eval loader's centre crop, datasets/ucf_dataloader_eval.py:100-106).
+ * pc_truth_frame_flags: flags[f] (int32) = number of non-zero truth pixels of frame f inside the crop; one block per frame, a plain store (no
+ * atomics, `flags` need not be zeroed).  A clip is kept if one of its in-range frames has a non-zero flag (:95-96).
+ * pc_eval_clips_from_u8: `starts` is a HOST array of n first-frame indices (1 <= n <= 32, each >= 0); frame k of clip c is starts[c] + k * f_skip.
+ * data [n][8][S][S][4] float32 = (r, g, b, 0) with every channel (float)((double)u8 / 255.0) -- the NDHWC tensor the network's first conv reads
+ * (PC_F_CI3), as pc_clip_from_u8_ndhwc4 writes it; gt [n][8][S][S] float32 = the truth VALUE (not binarised), frame-major as pc_seg_frame_counts
+ * takes it.  A frame index >= F gives zeros in both and reads nothing (:89-91).  data / gt 16-byte aligned.
+ * pc_video_vote: pred [n][C] float32; the n rows are added in row order in fp32 and divided by (float)n (numpy's mean over axis 0 of a C-contiguous
+ * float32 array), and *n_correct += 1 if the first maximum is `label` (a NaN mean counts as the maximum, as in np.argmax).
+ * All three refuse bad arguments with PC_E_ARG before any HIP call. */
+int pc_truth_frame_flags(const uint8_t* truth, int F, int H, int W, int h0, int w0, int S, int32_t* flags, pc_stream s);
+int pc_eval_clips_from_u8(const uint8_t* video, const uint8_t* truth, int F, int H, int W, int h0, int w0, int S,
+                          const int32_t* starts, int n, int f_skip, float* data, float* gt, pc_stream s);
+int pc_video_vote(const float* pred, int n, int C, int label, int32_t* n_correct, pc_stream s);
 /* cv2.resize on uint8 images [n][H][W][C] -> [n][Ho][Wo][C] (C <= 4), the calls of the reference's loaders:
  * datasets/jhmdb_dataloader.py:252 (frames, INTER_AREA 320x240 -> 256x256), :267,:281 (puppet masks, INTER_NEAREST),
  * :192,:208 and ucf_dataloader.py:165,171 (224 crop -> frame size, INTER_LINEAR; the identity at 224).  OpenCV's 8-bit

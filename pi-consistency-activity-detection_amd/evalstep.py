@@ -1,0 +1,327 @@
+"""The f-mAP / v-mAP evaluation on one MI355X from DECODED uint8 video: the reference's evaluate_ucf101.py:73-186 (evaluate_jhmdb.py: the
+same loop, 21 classes) with the video uploaded as the decoder left it (uint8 frames, uint8 truth: 1/24 of the float64 the reference's loader
+yields), the clips cut on the device straight into the tensor the stem reads (pc_eval_clips_from_u8, csrc/evalclips.hip), the eval forward
+replayed from ONE op plan of `bs` clips whose weight layouts are made once per pass, and the per-frame counts, the per-class tables and the
+class vote accumulated on the device (pc_seg_frame_counts, pc_map_accumulate, pc_video_vote).  One device-to-host copy per pass (`results`).
+
+The only host wait per video is for its F per-frame truth counts (pc_truth_frame_flags on the copy stream): they decide on the host which
+clips exist (`clip_starts`), as `np.sum(clips[-1][1]) == 0` does in the reference.  The compute stream is never waited for.
+"""
+from types import SimpleNamespace
+
+import numpy as np
+import torch
+
+from . import capi, evalmetrics, ops, spec
+from .plan import Plan
+from .valstep import PlanEngine
+
+MAX_LAUNCH_CLIPS = 32          # clips of one pc_eval_clips_from_u8 launch
+
+
+# ---------------------------------------------------------------------- pure host functions (tests/test_evalstep_cpu.py)
+def centre_crop(H, W, hw):
+    """datasets/ucf_dataloader_eval.py:100-103: (h0, w0) of the hw x hw centre crop, int(margin / 2)."""
+    return int((H - hw) / 2), int((W - hw) / 2)
+
+
+def clip_starts(F, flags, f_skip=2):
+    """First frames of the clips evaluate_ucf101.py:79-97 keeps, in its order: i + j for i = 0, 8 * f_skip, ..., j = 0..f_skip-1; frame k of a
+    clip is start + k * f_skip; a clip is kept if one of its frames below F has a non-zero flag (flags[f]: truth pixels of frame f)."""
+    flags = np.asarray(flags).reshape(-1)
+    out = []
+    for i in range(0, F, 8 * f_skip):
+        for j in range(f_skip):
+            if any(flags[f] != 0 for f in range(i + j, min(i + j + 8 * f_skip, F), f_skip)):
+                out.append(i + j)
+    return out
+
+
+def ring_place(pos, rows, capacity, bs):
+    """Where a video of `rows` clip rows goes in a ring of `capacity` rows whose next free row is `pos`: contiguous, from row 0 if it would
+    run over the end.  -> (first row, next free row).  A video may take at most capacity - bs rows."""
+    if rows < 1:
+        raise ValueError("a video of %d clips takes no rows" % rows)
+    if rows > capacity - bs:
+        raise ValueError("a video of %d clips needs more than capacity - bs = %d - %d rows of the tables" % (rows, capacity, bs))
+    row0 = pos if pos + rows <= capacity else 0
+    return row0, row0 + rows
+
+
+def vote(pred):
+    """np.argmax(np.mean(pred, axis=0)) as pc_video_vote computes it: the rows added in order in float32, one division, the first maximum."""
+    p = np.asarray(pred, np.float32)
+    s = p[0].copy()
+    for r in p[1:]:
+        s = (s + r).astype(np.float32)
+    m = (s / np.float32(p.shape[0])).astype(np.float32)
+    best = 0
+    for j in range(1, m.size):
+        if (np.isnan(m[j]) and not np.isnan(m[best])) or m[j] > m[best]:
+            best = j
+    return best
+
+
+def _as_u8(a, what):
+    """numpy / host tensor / device tensor -> torch uint8 tensor (no copy), or ValueError."""
+    t = a if torch.is_tensor(a) else (torch.from_numpy(a) if isinstance(a, np.ndarray) else None)
+    if t is None or t.dtype != torch.uint8:
+        raise ValueError("%s: uint8 frames as numpy array or torch tensor, got %s" % (what, getattr(a, "dtype", type(a))))
+    return t
+
+
+class EvalEngine(PlanEngine):
+    """Evaluates the weights in the flat buffers P, R: a StepEngine's own (StepEngine.eval_engine: no copy, behind its lanes) or, built from a
+    state dict, buffers of its own (load_state per checkpoint).
+
+    begin() once per pass, add_video(frames_u8, truth_u8, label) per video, results() at the end -- or evaluate(videos).  pack=False: batches
+    of up to `bs` clips of ONE video, as the reference forms them; pack=True: clips of consecutive videos share full batches.  A batch of
+    m < bs clips runs on the same plan: in eval mode a clip's outputs do not depend on its neighbours, the stale slots cost time only."""
+
+    def __init__(self, bs=14, hw=224, num_classes=24, device="cuda:0", state=None, engine=None, capacity=256, seed=47, f_skip=2, pack=False, on_batch=None):
+        if not torch.cuda.is_available():
+            raise RuntimeError("EvalEngine needs a GPU: the hot path is HIP-only (no CPU fallback)")
+        if bs < 1 or capacity <= bs:
+            raise ValueError("bs must be at least 1 and capacity larger than bs")
+        capi.lib()
+        lay = self._bind(bs, hw, num_classes, device, state, seed, engine)
+        self.capacity, self.f_skip, self.pack, self.on_batch = capacity, f_skip, bool(pack), on_batch
+        c = self.c = self._build(bs, lay)
+        p = c.plan
+        c.ops["fwd"][p.op_to_ndhwc[0]]["i"][1] = 0                      # N = 0, for good: pc_eval_clips_from_u8 writes the stem's tensor itself
+        self._view(c, p.in_cls, bs).fill_(500.0)                        # the reference's empty_action (:121-122) as the module's eval slot leaves it
+        self._view(c, p.in_labeled, bs, torch.int32).fill_(500)
+        self.img = self._view(c, p.img.ref, bs * self.per * 4)          # [bs][8][hw][hw][4]
+        self.img.zero_()                                                # slots no batch has filled yet hold numbers, not whatever the allocator left
+        self.gt = torch.zeros(bs * self.per, device=self.dev)           # [bs][8][hw][hw], the truth of the batch in flight
+        self.out = self._view(c, p.out.ref, bs * self.per)
+        self.pred = self._view(c, p.pred, bs * self.C).view(bs, self.C)
+        self.counts = torch.zeros(capacity * spec.FRAMES, 3, dtype=torch.int32, device=self.dev)
+        self.scores = torch.zeros(capacity, self.C, device=self.dev)
+        # the accumulators of evaluate_ucf101.py:66-72 in ONE int32 buffer, so that a pass ends with one device-to-host copy
+        C_, T = self.C, evalmetrics.N_THR
+        self.tables = torch.zeros(2 * C_ * T + 2 * C_ + 1, dtype=torch.int32, device=self.dev)
+        self.acc = self._accumulator(self.tables)
+        self.copy_stream = torch.cuda.Stream(device=self.dev)
+        self.pin = None                      # page-locked staging of one video (frames, then truth); free again when its flags have arrived
+        self.pin_flags = self.dev_flags = None
+        self.pool = []                       # device buffers of videos: dict(buf, free: event after the last launch that read it, or None if in use)
+        self.gen = self.gen_done = 0
+        self.m = 0                           # clips of the last batch
+        self._reset()
+
+    def _plan(self, n):
+        p = Plan(self.C, self.hw, n=n, groups=1, training=False)
+        p.build_forward()
+        return p
+
+    def _accumulator(self, flat):
+        C_, T = self.C, evalmetrics.N_THR
+        a = evalmetrics.MapAccumulator.__new__(evalmetrics.MapAccumulator)
+        a.n_classes = C_
+        a.frame_hits, a.video_hits = flat[:C_ * T].view(C_, T), flat[C_ * T:2 * C_ * T].view(C_, T)
+        a.n_frames, a.n_vids, a.n_correct = flat[2 * C_ * T:2 * C_ * T + C_], flat[2 * C_ * T + C_:2 * C_ * T + 2 * C_], flat[2 * C_ * T + 2 * C_:]
+        return a
+
+    def _reset(self):
+        self.pos = 0                         # next free row of the ring
+        self.batch = []                      # segments of the batch being filled: (video record, first clip, count)
+        self.fill = 0
+        self.live = []                       # videos with clips not yet run, in arrival order
+        self.n_videos = self.n_skipped = self.n_clips = 0
+
+    # ------------------------------------------------------------------ the pass
+    def begin(self, pack=None):
+        """Start a pass (pack: how batches are formed from here on): zero tables, an empty ring, and the weight layouts (the `prep` and
+        `prep_late` lists) due again in front of the first batch -- the weights do not change during a pass.  Behind a StepEngine, the pass
+        waits for its lanes."""
+        for v in self.live:
+            self._release(v)
+        self._reset()
+        if pack is not None:
+            self.pack = bool(pack)
+        self.gen += 1
+        self.tables.zero_()
+        if self.side:
+            ops.streams_fanin(torch.cuda.current_stream(self.dev), self.side)
+
+    def check_video(self, frames, truth, label):
+        """Refuse (ValueError) a video the engine cannot take, before anything is enqueued or changed.  -> (frames, truth [F,H,W], label)."""
+        v, t = _as_u8(frames, "frames"), _as_u8(truth, "truth")
+        if v.dim() != 4 or v.shape[3] != 3 or v.shape[0] < 1:
+            raise ValueError("frames: shape %s, expected (F, H, W, 3)" % (tuple(v.shape),))
+        F, H, W = (int(s) for s in v.shape[:3])
+        if H < self.hw or W < self.hw:
+            raise ValueError("frames of %d x %d are smaller than the %d x %d crop" % (H, W, self.hw, self.hw))
+        if t.dim() == 4 and t.shape[3] == 1:
+            t = t.reshape(t.shape[:3])
+        if t.dim() != 3 or tuple(t.shape) != (F, H, W):
+            raise ValueError("truth: shape %s, expected (%d, %d, %d) or (%d, %d, %d, 1)" % (tuple(truth.shape), F, H, W, F, H, W))
+        try:
+            lab = int(label)
+        except (TypeError, ValueError):
+            raise ValueError("label: %r is not a class id" % (label,)) from None
+        if lab != label or not 0 <= lab < self.C:
+            raise ValueError("label: %r outside [0, %d)" % (label, self.C))
+        return v, t, lab
+
+    def _acquire(self, nbytes):
+        """A device buffer of at least nbytes that no launch still to run reads -- the copy stream waits (on the device) for the launches that did."""
+        best = None
+        for e in self.pool:
+            if e["free"] is not None and e["buf"].numel() >= nbytes and (best is None or e["buf"].numel() < best["buf"].numel()):
+                best = e
+        if best is None:
+            main = torch.cuda.current_stream(self.dev)
+            for i, e in enumerate(self.pool):
+                if e["free"] is not None:                # a free one that is too small makes room for the new one
+                    e["buf"].record_stream(main)
+                    del self.pool[i]                     # (by position: comparing the entries would compare their tensors)
+                    break
+            with torch.cuda.stream(self.copy_stream):
+                best = dict(buf=torch.empty((nbytes + (1 << 20) - 1) >> 20 << 20, dtype=torch.uint8, device=self.dev), free=None)
+            self.pool.append(best)
+        else:
+            self.copy_stream.wait_event(best["free"])
+        best["free"] = None
+        return best
+
+    def _release(self, v):
+        """The last launch that reads the video has been enqueued on the compute stream: its buffer is free once that launch has run."""
+        if v.entry is not None:
+            ev = torch.cuda.Event()
+            ev.record(torch.cuda.current_stream(self.dev))
+            v.entry["free"] = ev
+            v.entry = None
+        v.video = v.truth = None             # a caller's device tensors: stream order on the compute stream keeps them until here
+
+    def _upload(self, v, t):
+        """-> (video, truth, entry) on the device, the upload (if any) enqueued on the copy stream."""
+        if v.is_cuda or t.is_cuda:
+            if not (v.is_cuda and t.is_cuda):
+                v, t = v.to(self.dev), t.to(self.dev)
+            self.copy_stream.wait_stream(torch.cuda.current_stream(self.dev))        # whatever produced them
+            return v.contiguous(), t.contiguous(), None
+        nv, nt = v.numel(), t.numel()
+        o_t = (nv + 255) // 256 * 256
+        if self.pin is None or self.pin.numel() < o_t + nt:
+            self.pin = torch.empty(o_t + nt, dtype=torch.uint8).pin_memory()
+        self.pin[:nv].view(v.shape).copy_(v)
+        self.pin[o_t:o_t + nt].view(t.shape).copy_(t)
+        e = self._acquire(o_t + nt)
+        with torch.cuda.stream(self.copy_stream):
+            e["buf"][:o_t + nt].copy_(self.pin[:o_t + nt], non_blocking=True)
+        return e["buf"][:nv].view(v.shape), e["buf"][o_t:o_t + nt].view(t.shape), e
+
+    def add_video(self, frames_u8, truth_u8, label):
+        """One video: frames [F,H,W,3] uint8, truth [F,H,W] or [F,H,W,1] uint8 (numpy, host tensor or device tensor), class id.  Uploaded through
+        page-locked memory on the copy stream; its kept clips join the batches.  -> the number of clips (0: "Video has no bounding boxes",
+        evaluate_ucf101.py:99-101, the video is skipped)."""
+        v, t, lab = self.check_video(frames_u8, truth_u8, label)
+        F, H, W = (int(s) for s in v.shape[:3])
+        h0, w0 = centre_crop(H, W, self.hw)
+        if self.dev_flags is None or self.dev_flags.numel() < F:
+            with torch.cuda.stream(self.copy_stream):                # allocated where it is used: every frame's flag is a plain store, no fill
+                self.dev_flags = torch.empty(max(F, 256), dtype=torch.int32, device=self.dev)
+            self.pin_flags = torch.zeros(max(F, 256), dtype=torch.int32).pin_memory()
+        dv, dt, entry = self._upload(v, t)
+        rec = SimpleNamespace(video=dv, truth=dt, entry=entry, F=F, H=H, W=W, h0=h0, w0=w0, label=lab, ready=torch.cuda.Event(), waited=False)
+        with torch.cuda.stream(self.copy_stream):
+            ops.truth_frame_flags(dt, h0, w0, self.hw, self.dev_flags)
+            self.pin_flags[:F].copy_(self.dev_flags[:F], non_blocking=True)
+            rec.ready.record(self.copy_stream)
+        rec.ready.synchronize()              # the one host wait of the video: F integers, on the copy stream
+        rec.starts = clip_starts(F, self.pin_flags[:F].numpy(), self.f_skip)
+        rec.rows, rec.done = len(rec.starts), 0
+        if not rec.starts:
+            self._release(rec)
+            self.n_skipped += 1
+            return 0
+        try:
+            row0, pos = ring_place(self.pos, rec.rows, self.capacity, self.bs)
+        except ValueError:
+            self._release(rec)
+            raise
+        if any(row0 < o.row0 + o.rows and o.row0 < row0 + rec.rows for o in self.live):
+            self.flush()                     # rows of a video whose clips still wait for a full batch: run them first (pack=True, a small ring)
+        rec.row0, self.pos = row0, pos
+        self.live.append(rec)
+        self.n_videos += 1
+        self.n_clips += rec.rows
+        if self.pack:
+            first = 0
+            while first < rec.rows:
+                take = min(rec.rows - first, self.bs - self.fill)
+                self.batch.append((rec, first, take))
+                self.fill += take
+                first += take
+                if self.fill == self.bs:
+                    self._run_batch()
+        else:
+            for i in range(0, rec.rows, self.bs):
+                self.batch.append((rec, i, min(self.bs, rec.rows - i)))
+                self._run_batch()
+        return rec.rows
+
+    def flush(self):
+        """Run the clips that wait for a full batch (pack=True) as a short one."""
+        self._run_batch()
+
+    def _run_batch(self):
+        if not self.batch:
+            return
+        c, hw, per = self.c, self.hw, self.per
+        main = torch.cuda.current_stream(self.dev)
+        slot = 0
+        for rec, first, n in self.batch:                                       # one clip-making launch per video segment (32 clips at most each)
+            if not rec.waited:
+                main.wait_event(rec.ready)
+                rec.waited = True
+            for q in range(0, n, MAX_LAUNCH_CLIPS):
+                k = min(MAX_LAUNCH_CLIPS, n - q)
+                o = slot + q
+                ops.eval_clips_from_u8(rec.video, rec.truth, rec.h0, rec.w0, hw, rec.starts[first + q:first + q + k], self.f_skip,
+                                       out=(self.img[o * per * 4:(o + k) * per * 4], self.gt[o * per:(o + k) * per]))
+            if first + n == rec.rows:
+                self._release(rec)
+            slot += n
+        m = self.m = slot
+        if self.gen_done != self.gen:                                          # first batch of the pass: the weight layouts
+            ops.run_ops(c.ops["prep"])
+            ops.run_ops(c.ops["prep_late"])
+            self.gen_done = self.gen
+        ops.run_ops(c.ops["fwd"])
+        slot = 0
+        T = spec.FRAMES
+        for rec, first, n in self.batch:
+            r = rec.row0 + first
+            capi.call("pc_seg_frame_counts", ops.ptr(self.out[slot * per:]), ops.ptr(self.gt[slot * per:]), T * n, hw * hw,
+                      ops.ptr(self.counts[r * T:]), ops.stream())
+            self.scores[r:r + n].copy_(self.pred[slot:slot + n])
+            slot += n
+        if self.on_batch is not None:
+            self.on_batch(m, *self.outputs())
+        for rec, first, n in self.batch:
+            rec.done += n
+            if rec.done == rec.rows:                                           # the video's last clip has run: its rows into the tables
+                a = self.acc
+                ops.map_accumulate(self.counts[rec.row0 * T:(rec.row0 + rec.rows) * T], rec.label, a.frame_hits, a.video_hits, a.n_frames, a.n_vids)
+                ops.video_vote(self.scores[rec.row0:rec.row0 + rec.rows], rec.label, a.n_correct)
+                self.live = [o for o in self.live if o is not rec]
+        self.batch, self.fill = [], 0
+
+    def results(self):
+        """The pass's one device-to-host copy -> the dict of evalmetrics.MapAccumulator.result()."""
+        self.flush()
+        return self._accumulator(self.tables.cpu()).result()
+
+    def outputs(self):
+        """(output (m,1,8,H,W) logits, predicted_action (m,C)) of the last batch: views of the plan's arena."""
+        return self.out[:self.m * self.per].view(self.m, 1, spec.FRAMES, self.hw, self.hw), self.pred[:self.m]
+
+    def evaluate(self, videos, pack=False):
+        """One pass over an iterable of (frames_u8, truth_u8, label) -> results()."""
+        self.begin(pack)
+        for frames, truth, label in videos:
+            self.add_video(frames, truth, label)
+        return self.results()

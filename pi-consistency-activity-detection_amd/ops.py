@@ -555,6 +555,55 @@ def clip_from_u8_masks(video, span, h0, w0, maskframes, valid, S=224):
     return data, aug, mask, mask_cls
 
 
+def _u8_video(video, truth, who):
+    if video.dtype != torch.uint8 or video.dim() != 4 or video.shape[3] != 3 or not video.is_contiguous():
+        raise ValueError("%s: contiguous uint8 [F,H,W,3] frames" % who)
+    if truth.dtype != torch.uint8 or not truth.is_contiguous() or truth.numel() != video.numel() // 3 or tuple(truth.shape[:3]) != tuple(video.shape[:3]):
+        raise ValueError("%s: truth must be contiguous uint8 [F,H,W] of the video's size" % who)
+    return (int(v) for v in video.shape[:3])
+
+
+def truth_frame_flags(truth, h0, w0, S, flags=None):
+    """pc_truth_frame_flags: truth uint8 device [F,H,W] -> int32 [F], the non-zero truth pixels of each frame inside the S x S crop at (h0, w0).
+    flags: an int32 device tensor of at least F elements to write into."""
+    if truth.dtype != torch.uint8 or truth.dim() != 3 or not truth.is_contiguous():
+        raise ValueError("truth_frame_flags: contiguous uint8 [F,H,W] truth")
+    F, H, W = (int(v) for v in truth.shape)
+    if flags is None:
+        flags = torch.empty(F, dtype=torch.int32, device=truth.device)
+    elif flags.dtype != torch.int32 or not flags.is_contiguous() or flags.numel() < F:
+        raise ValueError("truth_frame_flags: flags must be contiguous int32 with at least %d elements" % F)
+    capi.call("pc_truth_frame_flags", ptr(truth), F, H, W, int(h0), int(w0), int(S), ptr(flags), stream())
+    return flags[:F]
+
+
+def eval_clips_from_u8(video, truth, h0, w0, S, starts, f_skip=2, out=None):
+    """pc_eval_clips_from_u8: video uint8 device [F,H,W,3], truth uint8 device [F,H,W]; starts: 1..32 first-frame indices (host).
+    -> data [n,8,S,S,4] float32 (r, g, b, 0), gt [n,8,S,S] float32 (the truth values; zero frames past the end).  out: (data, gt) contiguous
+    float32 device tensors with room for n clips -- a batch's place in the plan's clip tensor -- instead of fresh ones."""
+    F, H, W = _u8_video(video, truth, "eval_clips_from_u8")
+    n = len(starts)
+    if out is None:
+        data = torch.empty(n, 8, S, S, 4, device=video.device); gt = torch.empty(n, 8, S, S, device=video.device)
+    else:
+        data, gt = out
+        for t, n_ in ((data, 32 * S * S), (gt, 8 * S * S)):
+            if t.dtype != torch.float32 or not t.is_contiguous() or t.numel() < n * n_ or t.device != video.device:
+                raise ValueError("eval_clips_from_u8: out tensors must be contiguous float32 device tensors of at least n*8*S*S*4 / n*8*S*S elements")
+    st = (C.c_int32 * max(n, 1))(*[int(v) for v in starts])
+    capi.call("pc_eval_clips_from_u8", ptr(video), ptr(truth), F, H, W, int(h0), int(w0), int(S), st, n, int(f_skip), ptr(data), ptr(gt), stream())
+    return data, gt
+
+
+def video_vote(pred, label, n_correct):
+    """pc_video_vote: n_correct (int32 device, 1 element) += argmax(mean(pred, axis=0)) == label; pred contiguous float32 device [n,C]."""
+    if pred.dtype != torch.float32 or pred.dim() != 2 or not pred.is_contiguous():
+        raise ValueError("video_vote: contiguous float32 [n,C] scores")
+    if n_correct.dtype != torch.int32 or n_correct.numel() < 1:
+        raise ValueError("video_vote: n_correct must be an int32 device tensor")
+    capi.call("pc_video_vote", ptr(pred), int(pred.shape[0]), int(pred.shape[1]), int(label), ptr(n_correct), stream())
+
+
 _RESIZE_TABS = {}
 
 

@@ -502,6 +502,12 @@ class StepEngine:
         from .valstep import ValEngine
         return ValEngine(self.bs if bs is None else bs, capacity=capacity, engine=self)
 
+    def eval_engine(self, bs=14, capacity=256, **kw):
+        """-> evalstep.EvalEngine over THIS engine's parameter and running-statistics buffers (no copy: an evaluation pass sees what the last
+        train step left) and behind its lanes; arena, tables and staging are the EvalEngine's own.  bs: clips per batch (the reference's 14)."""
+        from .evalstep import EvalEngine
+        return EvalEngine(bs, capacity=capacity, engine=self, **kw)
+
     def make_reducer(self, group=None, target_floats=3_000_000, force=False, check=True):
         """check: refuse to train if the ranks do not hold identical parameters (dist.check_replicas_agree: one 3-number all-reduce)."""
         from . import dist as pdist

@@ -177,6 +177,35 @@ def make_eval_videos(n, seed=1234, num_classes=24, hw=224):
     return out
 
 
+def make_eval_videos_u8(n, seed=1234, num_classes=24, hw=224, frames_hw=None):
+    """Synthetic evaluation set in the form the eval loaders' `load_video` returns (datasets/ucf_dataloader_eval.py, before the centre crop and the
+    division by 255): (frames uint8 [F,H,W,3], truth uint8 [F,H,W,1] in {0,1}, label), F = 8..40, frames larger than the hw x hw crop (default
+    hw + 16 by hw + 32), one moving box per video over a sub-range of its frames.  The box of video 1 (if n > 1) lies wholly OUTSIDE the centre crop:
+    the evaluation skips that video ("Video has no bounding boxes")."""
+    rng = np.random.default_rng(seed)
+    H, W = frames_hw if frames_hw is not None else (hw + 16, hw + 32)
+    h0, w0 = int((H - hw) / 2), int((W - hw) / 2)
+    if H <= hw or W <= hw or min(h0, w0) < 2:
+        raise ValueError("make_eval_videos_u8: frames of %d x %d leave no margin of 2 around the %d crop" % (H, W, hw))
+    out = []
+    for vi in range(n):
+        F = int(rng.integers(8, 41))
+        truth = np.zeros((F, H, W, 1), np.uint8)
+        f0 = int(rng.integers(0, max(1, F - 6))); f1 = int(rng.integers(f0 + 3, F + 1))
+        h, w = int(rng.integers(hw // 6, hw // 2)), int(rng.integers(hw // 6, hw // 2))
+        y, x = int(rng.integers(0, H - h)), int(rng.integers(0, W - w))
+        frames = rng.integers(0, 256, (F, H, W, 3), dtype=np.uint8)
+        if vi == 1:
+            truth[f0:f1, :h0, :w0, 0] = 1                      # the corner the crop leaves out
+        else:
+            for f in range(f0, f1):
+                yy, xx = min(H - h, y + (f - f0)), min(W - w, x + 2 * (f - f0))
+                truth[f, yy:yy + h, xx:xx + w, 0] = 1
+            truth[f0, h0 + hw // 2, w0 + hw // 2, 0] = 1       # whatever the draw: truth inside the crop
+        out.append((frames, truth, vi % num_classes))
+    return out
+
+
 def make_decoded_video(seed, labeled=True, num_classes=24, frames_hw=(240, 320)):
     """One synthetic decoded training video in the form datasets/ucf_dataloader.py `load_video` consumes after `vread`:
     (uint8 frames [F,H,W,3], annotations [(start, end, label, [[x,y,w,h] per frame], [annotated frame ids], labeled_vid)])."""

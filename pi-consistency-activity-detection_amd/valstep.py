@@ -19,7 +19,65 @@ from .plan import Plan
 KEYS = ("data", "action", "loc_msk")
 
 
-class ValEngine:
+class PlanEngine:
+    """What the engines that replay an eval plan share (ValEngine here, evalstep.EvalEngine): the flat parameter / running-statistics buffers
+    P, R -- a StepEngine's own (no copy) or, built from a state dict, buffers of their own -- a plan resolved over an arena, and views into it.
+    A subclass provides _plan(n)."""
+
+    def _bind(self, bs, hw, num_classes, device, state, seed, engine):
+        """Device, sizes, P / R and the lanes to fan in; -> the primary plan (not yet resolved)."""
+        self.engine = engine
+        if engine is not None:
+            self.dev, self.hw, self.C = engine.dev, engine.hw, engine.C
+            self.P, self.R = engine.P, engine.R
+            self.side = list(engine.side) + ([engine.main] if engine.main is not None else [])
+        else:
+            self.dev, self.hw, self.C = torch.device(device), hw, num_classes
+            self.side = []
+        torch.cuda.set_device(self.dev)
+        self.bs = bs
+        self.per = spec.FRAMES * self.hw * self.hw                 # pixels of one clip's mask
+        lay = self._plan(bs)
+        self.pshape, self.poff, self.roff = lay.pshape, lay.poff, lay.roff
+        if engine is None:
+            self.P = torch.zeros(lay.nparams, device=self.dev)
+            self.R = torch.zeros(lay.nrunning, device=self.dev)
+            self.load_state(state if state is not None else synthetic.init_state(seed, num_classes))
+        elif (lay.nparams, lay.nrunning, lay.poff, lay.roff) != (engine.plan.nparams, engine.plan.nrunning, engine.plan.poff, engine.plan.roff):
+            raise RuntimeError("the eval plan lays out the parameters differently from the engine's plan")
+        return lay
+
+    def _build(self, n, p=None):
+        p = p or self._plan(n)
+        arena = torch.empty(p.arena_bytes + 256, device=self.dev, dtype=torch.uint8)
+        base = (arena.data_ptr() + 255) // 256 * 256
+        c = SimpleNamespace(plan=p, n=n, arena=arena, a0=base - arena.data_ptr(), gen=-1)
+        c.ops = p.resolve(dict(A=base, P=self.P.data_ptr(), G=0, M=0, V=0, R=self.R.data_ptr()))
+        if len(p.op_to_ndhwc) != 1:
+            raise RuntimeError("an eval plan converts one clip tensor, this one %d" % len(p.op_to_ndhwc))
+        view = lambda ref, nf, dt=torch.float32: self._view(c, ref, nf, dt)
+        p.upload_consts(view)
+        return c
+
+    @staticmethod
+    def _view(c, ref, nfloats, dtype=torch.float32):
+        o = c.a0 + ref[1]
+        return c.arena[o:o + 4 * nfloats].view(dtype)
+
+    def load_state(self, state):
+        """Reference-layout state_dict (numpy or torch values) into the engine's OWN buffers."""
+        if self.engine is not None:
+            raise RuntimeError("this %s reads its StepEngine's buffers: load the state there" % type(self).__name__)
+        T = lambda v: (v.detach() if torch.is_tensor(v) else torch.as_tensor(np.asarray(v))).to(self.dev, torch.float32)
+        for k, shp in self.pshape.items():
+            o = self.poff[k]
+            self.P[o:o + int(np.prod(shp))].copy_(T(state[k]).reshape(-1))
+        for k, o in self.roff.items():
+            v = T(state[k])
+            self.R[o:o + v.numel()].copy_(v)
+
+
+class ValEngine(PlanEngine):
     """Validates the weights in the flat parameter / running-statistics buffers P, R: a StepEngine's own (StepEngine.val_engine: no copy,
     validation sees what the last train step left) or, built from a state dict, buffers of its own.
 
@@ -34,25 +92,8 @@ class ValEngine:
         if bs < 1 or capacity < 1:
             raise ValueError("bs and capacity must be at least 1")
         capi.lib()
-        self.engine = engine
-        if engine is not None:
-            self.dev, self.hw, self.C = engine.dev, engine.hw, engine.C
-            self.P, self.R = engine.P, engine.R
-            self.side = list(engine.side) + ([engine.main] if engine.main is not None else [])
-        else:
-            self.dev, self.hw, self.C = torch.device(device), hw, num_classes
-            self.side = []
-        torch.cuda.set_device(self.dev)
-        self.bs, self.capacity = bs, capacity
-        self.per = spec.FRAMES * self.hw * self.hw                 # pixels of one clip's mask
-        lay = self._plan(bs)
-        self.pshape, self.poff, self.roff = lay.pshape, lay.poff, lay.roff
-        if engine is None:
-            self.P = torch.zeros(lay.nparams, device=self.dev)
-            self.R = torch.zeros(lay.nrunning, device=self.dev)
-            self.load_state(state if state is not None else synthetic.init_state(seed, num_classes))
-        elif (lay.nparams, lay.nrunning, lay.poff, lay.roff) != (engine.plan.nparams, engine.plan.nrunning, engine.plan.poff, engine.plan.roff):
-            raise RuntimeError("the eval plan lays out the parameters differently from the engine's plan")
+        lay = self._bind(bs, hw, num_classes, device, state, seed, engine)
+        self.capacity = capacity
         self.words = ops.val_record_words(bs)
         self.table = torch.zeros(capacity, self.words, dtype=torch.int32, device=self.dev)
         self.k = 0                       # filled rows of the table
@@ -87,22 +128,9 @@ class ValEngine:
         return p
 
     def _build(self, n, p=None):
-        p = p or self._plan(n)
-        arena = torch.empty(p.arena_bytes + 256, device=self.dev, dtype=torch.uint8)
-        base = (arena.data_ptr() + 255) // 256 * 256
-        c = SimpleNamespace(plan=p, n=n, arena=arena, a0=base - arena.data_ptr(), gen=-1)
-        c.ops = p.resolve(dict(A=base, P=self.P.data_ptr(), G=0, M=0, V=0, R=self.R.data_ptr()))
-        if len(p.op_to_ndhwc) != 1:
-            raise RuntimeError("an eval plan converts one clip tensor, this one %d" % len(p.op_to_ndhwc))
-        view = lambda ref, nf, dt=torch.float32: self._view(c, ref, nf, dt)
-        p.upload_consts(view)
-        view(p.in_labeled, n, torch.int32).zero_()           # val_model_interface's empty_vector
+        c = super()._build(n, p)
+        self._view(c, c.plan.in_labeled, n, torch.int32).zero_()           # val_model_interface's empty_vector
         return c
-
-    @staticmethod
-    def _view(c, ref, nfloats, dtype=torch.float32):
-        o = c.a0 + ref[1]
-        return c.arena[o:o + 4 * nfloats].view(dtype)
 
     def _activate(self, m):
         if m == self.bs:
@@ -118,18 +146,6 @@ class ValEngine:
                 self._short.move_to_end(m)
         self._cur = c
         return c
-
-    def load_state(self, state):
-        """Reference-layout state_dict (numpy or torch values) into the engine's OWN buffers."""
-        if self.engine is not None:
-            raise RuntimeError("this ValEngine reads its StepEngine's buffers: load the state there")
-        T = lambda v: (v.detach() if torch.is_tensor(v) else torch.as_tensor(np.asarray(v))).to(self.dev, torch.float32)
-        for k, shp in self.pshape.items():
-            o = self.poff[k]
-            self.P[o:o + int(np.prod(shp))].copy_(T(state[k]).reshape(-1))
-        for k, o in self.roff.items():
-            v = T(state[k])
-            self.R[o:o + v.numel()].copy_(v)
 
     # ------------------------------------------------------------------ the pass
     def begin(self):
