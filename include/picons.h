@@ -64,10 +64,11 @@ typedef void* pc_stream;            /* hipStream_t */
  * pc_wgrad_desc.ws_slices, pc_transpose_job.nslices / slice_stride, pc_wgrad_slices; 102: the workspace operands of PC_OP_TAIL6_WGRAD_MAP / PC_OP_TAIL6_BIAS_SUMS /
  * PC_OP_TAIL_GRADS; 103: the variant reporters pc_conv_variant / pc_wino_variant / pc_wgrad_variant;
  * 104: PC_F_BKMAJOR, pc_wino_weights_multi / PC_OP_WINO_WEIGHTS_MULTI; 105: pc_val_metrics / PC_OP_VAL_METRICS;
- * 106: pc_truth_frame_flags / pc_eval_clips_from_u8 / pc_video_vote).  Descriptors must be zero-initialised by the caller:
+ * 106: pc_truth_frame_flags / pc_eval_clips_from_u8 / pc_video_vote;
+ * 107: pc_clips_from_u8 / pc_detect_frames / pc_detect_frames_ws_bytes / pc_video_class).  Descriptors must be zero-initialised by the caller:
  * fields added later read as "old behaviour" when 0.  pc_version() returns the value the library was built with; the Python host
  * (capi.lib()) refuses a library whose version differs from the header it mirrors. */
-#define PC_VERSION 106
+#define PC_VERSION 107
 int         pc_version(void);
 const char* pc_last_error(void);
 
@@ -403,6 +404,31 @@ int pc_truth_frame_flags(const uint8_t* truth, int F, int H, int W, int h0, int 
 int pc_eval_clips_from_u8(const uint8_t* video, const uint8_t* truth, int F, int H, int W, int h0, int w0, int S,
                           const int32_t* starts, int n, int f_skip, float* data, float* gt, pc_stream s);
 int pc_video_vote(const float* pred, int n, int C, int label, int32_t* n_correct, pc_stream s);
+/* Detection output (csrc/detect.hip; picons_amd/detect.py): unlabelled video in, per-frame masks, boxes and scores and the video's class out.
+ * pc_clips_from_u8: pc_eval_clips_from_u8 without the truth side -- the same kernel, the truth a compile-time switch -- writing `data` with the
+ * same bits; same refusals.
+ * pc_detect_frames: `logits` float32 [n][8][S][S], the eval forward's output for n <= 32 clips of ONE video (16-byte aligned, S % 4 == 0), and
+ * the starts / f_skip / F / H / W / h0 / w0 / S the clips were cut with.  Frame k of clip c is video frame f = starts[c] + k * f_skip; for
+ * f >= F nothing is read and nothing written.  For f < F the launch writes the WHOLE frame mask[f] of `mask` uint8 [F][H][W] (video frame
+ * order, full-frame coordinates): 1 where the pixel lies inside the crop and fp32 sigmoid(x) >= 0.5 -- pc_seg_frame_counts' predicate, one
+ * device function for both; NaN is background -- and 0 everywhere else, the margin around the crop included: no fill in front of the launch,
+ * and a frame the launch does not address is not touched.  `mask` may be null: records only.  rec int32 [F][8], one record per frame:
+ *   [0] count of positive pixels   [1..4] x0, y0, x1, y1, the half-open box of the positive pixels in full-frame coordinates (mask[f, y0:y1,
+ *   x0:x1] holds all of them), all zero when count == 0   [5] the bits of the float32 frame score: the mean of the fp32 1 / (1 + expf(-x))
+ *   over the positive pixels, summed in double in a fixed order, divided once in double and rounded once; 0.0f when count == 0
+ *   [6] row0 + c, the clip row the frame came from   [7] 0
+ * No atomics: every block leaves a partial in `ws` (pc_detect_frames_ws_bytes(n, S) bytes, 8-byte aligned, contents irrelevant before the
+ * call; host-only, -1 for an n or S the call would refuse) and a second small launch adds them in block order, so a record is bit-identical
+ * from run to run.  The starts of one launch must address distinct frames.
+ * pc_video_class: scores float32 [n][C] -> out float32 [C + 2]: the mean class scores with pc_video_vote's arithmetic (rows added in row
+ * order in fp32, one division by (float)n), then the arg-max as a float (the first maximum; a NaN beats every number), then the mean at it.
+ * All refuse bad arguments with PC_E_ARG before any HIP call, allocate nothing and enqueue on `s` only. */
+int     pc_clips_from_u8(const uint8_t* video, int F, int H, int W, int h0, int w0, int S, const int32_t* starts, int n, int f_skip,
+                         float* data, pc_stream s);
+int64_t pc_detect_frames_ws_bytes(int n, int S);
+int     pc_detect_frames(const float* logits, int F, int H, int W, int h0, int w0, int S, const int32_t* starts, int n, int f_skip,
+                         int row0, uint8_t* mask, int32_t* rec, void* ws, pc_stream s);
+int     pc_video_class(const float* scores, int n, int C, float* out, pc_stream s);
 /* cv2.resize on uint8 images [n][H][W][C] -> [n][Ho][Wo][C] (C <= 4), the calls of the reference's loaders:
  * datasets/jhmdb_dataloader.py:252 (frames, INTER_AREA 320x240 -> 256x256), :267,:281 (puppet masks, INTER_NEAREST),
  * :192,:208 and ucf_dataloader.py:165,171 (224 crop -> frame size, INTER_LINEAR; the identity at 224).  OpenCV's 8-bit

@@ -84,7 +84,7 @@ F_ACCUM, F_BIAS, F_CSCALE, F_BNPART, F_NFAST, F_TOUT, F_CI3, F_X6, F_STRIPS = 1,
 F_BKMAJOR = 512             # with F_X6: K-major weight planes [Ci][taps][ldw] (a layer's forward planes read by its input gradient)
 WG_CS3, WG_X6 = 1, 2
 
-ABI_VERSION = 106          # PC_VERSION of include/picons.h
+ABI_VERSION = 107          # PC_VERSION of include/picons.h
 
 _SIGS = {
     "pc_version": (i32, []),
@@ -145,6 +145,10 @@ _SIGS = {
     "pc_truth_frame_flags": (i32, [vp, i32, i32, i32, i32, i32, i32, vp, vp]),
     "pc_eval_clips_from_u8": (i32, [vp, vp, i32, i32, i32, i32, i32, i32, C.POINTER(C.c_int32), i32, i32, vp, vp, vp]),
     "pc_video_vote": (i32, [vp, i32, i32, i32, vp, vp]),
+    "pc_clips_from_u8": (i32, [vp, i32, i32, i32, i32, i32, i32, C.POINTER(C.c_int32), i32, i32, vp, vp]),
+    "pc_detect_frames_ws_bytes": (i64, [i32, i32]),
+    "pc_detect_frames": (i32, [vp, i32, i32, i32, i32, i32, i32, C.POINTER(C.c_int32), i32, i32, i32, vp, vp, vp, vp]),
+    "pc_video_class": (i32, [vp, i32, i32, vp, vp]),
     "pc_resize_tables": (i64, [i32, i32, i32, i32, i32, vp, i64]),
     "pc_resize_u8": (i32, [vp, i32, i32, i32, i32, i32, i32, vp, i32, vp, vp]),
     "pc_fill": (i32, [vp, i64, f32, vp]),

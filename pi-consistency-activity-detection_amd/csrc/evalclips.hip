@@ -4,8 +4,10 @@
 //   pc_truth_frame_flags   per frame, the number of non-zero truth pixels inside the crop: decides which clips are kept (:95-96)
 //   pc_eval_clips_from_u8  up to 32 clips of one video straight into the NDHWC tensor the stem reads and the frame-major truth
 //                          pc_seg_frame_counts takes; HBM-bound, 4 bytes read and 20 written per pixel
+//   pc_clips_from_u8       the same kernel without the truth side (unlabelled video: picons_amd/detect.py)
 //   pc_video_vote          argmax(mean(predictions, axis=0)) == label, rows added in order in fp32 as numpy adds them
 #include "common.h"
+#include "evalpred.h"
 
 namespace {
 
@@ -38,6 +40,8 @@ struct EvalClipsK {
 // blockIdx.y = clip * 8 + frame of the clip, blockIdx.x strides over the frame's S*S pixels: one thread per pixel writes one whole float4
 // (a wave: 1 KiB contiguous) and one truth float (256 B contiguous).  The source bytes of a cropped RGB row start at any byte address, so
 // they are read as bytes; consecutive lanes read consecutive 3-byte pixels of one row.
+// TRUTH = false (pc_clips_from_u8): the same body without the truth side; p.truth and p.gt are never touched.
+template <bool TRUTH>
 __global__ __launch_bounds__(256) void eval_clips_from_u8_kernel(const EvalClipsK p) {
     __shared__ float lut[256];
     lut[threadIdx.x] = (float)((double)threadIdx.x / 255.0);        // img / 255. in float64, then the float32 cast: once per block
@@ -46,49 +50,30 @@ __global__ __launch_bounds__(256) void eval_clips_from_u8_kernel(const EvalClips
     const int64_t f = (int64_t)p.starts[c] + (int64_t)k * p.f_skip;
     const int total = p.S * p.S;
     float4* data = p.data + (size_t)blockIdx.y * total;
-    float* gt = p.gt + (size_t)blockIdx.y * total;
+    float* gt = TRUTH ? p.gt + (size_t)blockIdx.y * total : nullptr;
     if (f >= p.F) {                                                  // a frame past the end: zeros, nothing read (evaluate_ucf101.py:89-91)
         for (int idx = blockIdx.x * 256 + threadIdx.x; idx < total; idx += gridDim.x * 256) {
             data[idx] = make_float4(0.f, 0.f, 0.f, 0.f);
-            gt[idx] = 0.f;
+            if (TRUTH) gt[idx] = 0.f;
         }
         return;
     }
     const uint8_t* vf = p.video + (((size_t)f * p.H + p.h0) * p.W + p.w0) * 3;
-    const uint8_t* tf = p.truth + ((size_t)f * p.H + p.h0) * p.W + p.w0;
+    const uint8_t* tf = TRUTH ? p.truth + ((size_t)f * p.H + p.h0) * p.W + p.w0 : nullptr;
     for (int idx = blockIdx.x * 256 + threadIdx.x; idx < total; idx += gridDim.x * 256) {
         const int y = idx / p.S, x = idx - y * p.S;
         const uint8_t* px = vf + ((size_t)y * p.W + x) * 3;
         data[idx] = make_float4(lut[px[0]], lut[px[1]], lut[px[2]], 0.f);
-        gt[idx] = (float)tf[(size_t)y * p.W + x];                    // the value itself: the reference counts pred + gt == 2
+        if (TRUTH) gt[idx] = (float)tf[(size_t)y * p.W + x];         // the value itself: the reference counts pred + gt == 2
     }
-}
-
-__device__ __forceinline__ bool vote_better(float a, int ia, float b, int ib) {     // np.argmax: the first maximum; a NaN beats every number
-    const bool na = a != a, nb = b != b;
-    if (na != nb) return na;
-    if (!na && a != b) return a > b;
-    return ia < ib;
 }
 
 __global__ __launch_bounds__(256) void video_vote_kernel(const float* __restrict__ pred, int n, int C, int label, int32_t* n_correct) {
     __shared__ float bv[256];
     __shared__ int bi[256];
-    float best = 0.f; int besti = 0x7fffffff;
-    for (int j = threadIdx.x; j < C; j += 256) {
-        float s = pred[j];
-        for (int r = 1; r < n; ++r) s = __fadd_rn(s, pred[(size_t)r * C + j]);
-        const float m = __fdiv_rn(s, (float)n);
-        if (besti == 0x7fffffff || vote_better(m, j, best, besti)) { best = m; besti = j; }
-    }
-    bv[threadIdx.x] = best; bi[threadIdx.x] = besti;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        const int live = C < 256 ? C : 256;
-        for (int t = 1; t < live; ++t)
-            if (vote_better(bv[t], bi[t], best, besti)) { best = bv[t]; besti = bi[t]; }
-        if (besti == label) *n_correct += 1;
-    }
+    float best; int besti;
+    vote_mean_argmax(pred, n, C, nullptr, bv, bi, best, besti);     // evalpred.h: the reduction pc_video_class shares
+    if (threadIdx.x == 0 && besti == label) *n_correct += 1;
 }
 
 }  // namespace
@@ -102,26 +87,38 @@ extern "C" int pc_truth_frame_flags(const uint8_t* truth, int F, int H, int W, i
     return PC_OK;
 }
 
-extern "C" int pc_eval_clips_from_u8(const uint8_t* video, const uint8_t* truth, int F, int H, int W, int h0, int w0, int S,
-                                     const int32_t* starts, int n, int f_skip, float* data, float* gt, pc_stream s) {
-    PC_CHECK_ARG(video && truth && starts && data && gt, "pc_eval_clips_from_u8: null pointer");
+// The checks and the launch pc_eval_clips_from_u8 (TRUTH) and pc_clips_from_u8 share; `who` names the entry in the messages.
+template <bool TRUTH>
+static int clips_from_u8(const char* who, const uint8_t* video, const uint8_t* truth, int F, int H, int W, int h0, int w0, int S,
+                         const int32_t* starts, int n, int f_skip, float* data, float* gt, pc_stream s) {
+    PC_CHECK_ARG(video && starts && data && (!TRUTH || (truth && gt)), "%s: null pointer", who);
     PC_CHECK_ARG(F >= 1 && H >= 1 && W >= 1 && S >= 1 && S <= 32768 && h0 >= 0 && w0 >= 0 && (int64_t)h0 + S <= H && (int64_t)w0 + S <= W,
-                 "pc_eval_clips_from_u8: %d frames, crop %d+%d x %d+%d outside %d x %d", F, h0, S, w0, S, H, W);
-    PC_CHECK_ARG(n >= 1 && n <= MAX_CLIPS, "pc_eval_clips_from_u8: n = %d clips outside 1..%d", n, MAX_CLIPS);
-    PC_CHECK_ARG(f_skip >= 1, "pc_eval_clips_from_u8: f_skip = %d", f_skip);
-    PC_CHECK_ARG(((uintptr_t)data % 16 == 0) && ((uintptr_t)gt % 16 == 0), "pc_eval_clips_from_u8: data / gt must be 16-byte aligned");
+                 "%s: %d frames, crop %d+%d x %d+%d outside %d x %d", who, F, h0, S, w0, S, H, W);
+    PC_CHECK_ARG(n >= 1 && n <= MAX_CLIPS, "%s: n = %d clips outside 1..%d", who, n, MAX_CLIPS);
+    PC_CHECK_ARG(f_skip >= 1, "%s: f_skip = %d", who, f_skip);
+    PC_CHECK_ARG(((uintptr_t)data % 16 == 0) && (!TRUTH || (uintptr_t)gt % 16 == 0), "%s: data / gt must be 16-byte aligned", who);
     EvalClipsK k;
     k.video = video; k.truth = truth; k.F = F; k.H = H; k.W = W; k.h0 = h0; k.w0 = w0; k.S = S; k.f_skip = f_skip;
     k.data = (float4*)data; k.gt = gt;
     for (int c = 0; c < MAX_CLIPS; ++c) {
-        if (c < n) PC_CHECK_ARG(starts[c] >= 0, "pc_eval_clips_from_u8: start %d of clip %d is negative", starts[c], c);
+        if (c < n) PC_CHECK_ARG(starts[c] >= 0, "%s: start %d of clip %d is negative", who, starts[c], c);
         k.starts[c] = c < n ? starts[c] : 0;
     }
     int gx = cdiv((int64_t)S * S, 1024);                             // ~4 pixels per thread
     if (gx > 1024) gx = 1024;
-    hipLaunchKernelGGL(eval_clips_from_u8_kernel, dim3((unsigned)gx, (unsigned)(n * 8)), dim3(256), 0, (hipStream_t)s, k);
-    PC_CHECK_LAUNCH("eval_clips_from_u8");
+    hipLaunchKernelGGL(eval_clips_from_u8_kernel<TRUTH>, dim3((unsigned)gx, (unsigned)(n * 8)), dim3(256), 0, (hipStream_t)s, k);
+    PC_CHECK_LAUNCH(who);
     return PC_OK;
+}
+
+extern "C" int pc_eval_clips_from_u8(const uint8_t* video, const uint8_t* truth, int F, int H, int W, int h0, int w0, int S,
+                                     const int32_t* starts, int n, int f_skip, float* data, float* gt, pc_stream s) {
+    return clips_from_u8<true>("pc_eval_clips_from_u8", video, truth, F, H, W, h0, w0, S, starts, n, f_skip, data, gt, s);
+}
+
+extern "C" int pc_clips_from_u8(const uint8_t* video, int F, int H, int W, int h0, int w0, int S, const int32_t* starts, int n, int f_skip,
+                                float* data, pc_stream s) {
+    return clips_from_u8<false>("pc_clips_from_u8", video, nullptr, F, H, W, h0, w0, S, starts, n, f_skip, data, nullptr, s);
 }
 
 extern "C" int pc_video_vote(const float* pred, int n, int C, int label, int32_t* n_correct, pc_stream s) {

@@ -2,6 +2,7 @@
 // against the truth and the per-class f-mAP / v-mAP hit tables the reference accumulates on the host in numpy
 // (/root/reference/evaluate_ucf101.py:142-183).  HBM-bound: every logit and every truth pixel is read once.
 #include "common.h"
+#include "evalpred.h"
 
 namespace {
 
@@ -18,10 +19,7 @@ __global__ __launch_bounds__(256) void seg_frame_counts_kernel(const float* __re
         const f32x4 x = lp[i], g = gp[i];
 #pragma unroll
         for (int e = 0; e < 4; ++e) {
-            // sigmoid(x) >= 0.5 in fp32: certainly true for x >= 0 (exp(-x) <= 1 => 1 + e <= 2, division is monotone) and
-            // certainly false below -1e-6 (1 + e >= 2.000001 > 2); only in between does the rounding of exp / the sum decide
-            const float xe = x[e];
-            const bool on = xe >= 0.f ? true : (xe < -1e-6f ? false : (1.0f / (1.0f + expf(-xe))) >= 0.5f);
+            const bool on = seg_positive(x[e]);                      // evalpred.h: the predicate pc_detect_frames shares
             const float v = (on ? 1.0f : 0.0f) + g[e];
             inter += v == 2.0f;
             uni += v != 0.0f;

@@ -1,0 +1,168 @@
+"""Detection output on one MI355X: where the action is in a video and which action it is, from DECODED uint8 video without truth.  The
+inference side of evalstep.EvalEngine -- the same upload pool, clip kernel (pc_clips_from_u8: the truth side compiled out), single eval plan
+whose weight layouts are made once per pass, and class-score ring -- ending not in hit tables but in detections: behind each batch one
+pc_detect_frames per video segment undoes the clip interleave (frame k of a clip is start + k * f_skip) straight into the video's uint8 masks
+in frame order and full-frame coordinates and leaves one record per frame (pixel count, box, score); behind a video's last clip
+pc_video_class votes its class, and one asynchronous copy takes records and class vector into page-locked memory.  No truth, no flag
+kernel, and the compute stream is never waited for per video (the host only waits for the upload of two videos ago to have left its
+page-locked slot): `results()` is the one host wait of a pass.  The masks stay on the device.
+
+The mask predicate is the evaluator's own (fp32 sigmoid(x) >= 0.5, one device function for both kernels), so a detection and the f-mAP /
+v-mAP that scores it cannot disagree on a pixel.  The model localises one actor per clip, as the reference's does: a tube is a run of
+detected frames, its class and class score are the video's.
+"""
+from types import SimpleNamespace
+
+import numpy as np
+import torch
+
+from . import ops
+from .evalstep import ClipEngine, _as_u8, centre_crop, clip_starts, ring_place
+
+PIN_CHUNK_WORDS = 1 << 18          # page-locked staging of the records, 1 MiB at a time
+
+
+# ---------------------------------------------------------------------- pure host functions (tests/test_detect_cpu.py)
+def link_tubes(counts, boxes, frame_scores, min_pixels=1, max_gap=0):
+    """Per-frame records -> action tubes.  A tube is a maximal run of frames with count >= min_pixels; two runs merge when at most max_gap
+    frames lie between them (those frames keep their box as it is: empty, for a frame without a positive pixel).
+    -> [(t0, t1, boxes[t0:t1 + 1], score)], t1 inclusive, score the float64 mean of the frame scores of the tube's DETECTED frames."""
+    counts = np.asarray(counts).reshape(-1)
+    boxes = np.asarray(boxes).reshape(-1, 4)
+    scores = np.asarray(frame_scores, np.float64).reshape(-1)
+    if not (counts.size == boxes.shape[0] == scores.size):
+        raise ValueError("link_tubes: %d counts, %d boxes, %d scores" % (counts.size, boxes.shape[0], scores.size))
+    if min_pixels < 1 or max_gap < 0:
+        raise ValueError("link_tubes: min_pixels >= 1 and max_gap >= 0, got %r and %r" % (min_pixels, max_gap))
+    on = counts >= min_pixels
+    runs = []
+    for t in np.flatnonzero(on).tolist():
+        if runs and t - runs[-1][1] - 1 <= max_gap:
+            runs[-1][1] = t
+        else:
+            runs.append([t, t])
+    return [(t0, t1, boxes[t0:t1 + 1].copy(), float(scores[t0:t1 + 1][on[t0:t1 + 1]].mean())) for t0, t1 in runs]
+
+
+class Detection:
+    """One video's detections.  label / class_score / class_scores [C]: the arg-max of the mean class scores of its clips, that mean, all means;
+    counts [F] positive pixels, boxes [F, 4] = x0, y0, x1, y1 (half-open, full-frame coordinates, zeros for an empty frame) and frame_scores [F]
+    (mean sigmoid over the positive pixels) per frame; masks: device uint8 [F, H, W] or None."""
+
+    def __init__(self, label, class_score, class_scores, counts, boxes, frame_scores, masks):
+        self.label, self.class_score, self.class_scores = label, class_score, class_scores
+        self.counts, self.boxes, self.frame_scores, self.masks = counts, boxes, frame_scores, masks
+
+    def tubes(self, min_pixels=1, max_gap=0):
+        return link_tubes(self.counts, self.boxes, self.frame_scores, min_pixels, max_gap)
+
+
+class DetectEngine(ClipEngine):
+    """Detects with the weights in the flat buffers P, R: a StepEngine's own (StepEngine.detect_engine: no copy, behind its lanes) or, built
+    from a state dict, buffers of its own (load_state per checkpoint).
+
+    begin() once per pass, add_video(frames_u8) per video, results() at the end -- or detect(frames_u8).  pack as in EvalEngine.
+    masks=False: records only (the kernel gets a null mask)."""
+
+    def __init__(self, bs=14, hw=224, num_classes=24, device="cuda:0", state=None, engine=None, capacity=256, seed=47, f_skip=2, pack=False,
+                 masks=True, on_batch=None):
+        hw = engine.hw if engine is not None else hw
+        if hw % 4:
+            raise ValueError("DetectEngine: hw = %d must be a multiple of 4 (pc_detect_frames reads the logit rows 16 bytes at a time)" % hw)
+        self._setup(bs, hw, num_classes, device, state, engine, capacity, seed, f_skip, pack, on_batch)
+        self.masks = bool(masks)
+        self.ws = torch.empty(ops.detect_frames_ws_bytes(min(bs, 32), self.hw), dtype=torch.uint8, device=self.dev)
+        self.pins = []                       # page-locked chunks the records of a pass are copied into
+        # upload staging: two page-locked slots, so that the host fills one while the copy stream still reads the other (EvalEngine has one:
+        # it waits for every video's flags).  A slot is filled again once the upload of two videos ago has left it.
+        self.up_pin, self.up_done, self.up_slot = [None, None], [None, None], 0
+        self._clear()
+
+    def _clear(self):
+        self.videos = []                     # the pass's videos in arrival order
+        self.pin_i = self.pin_off = 0
+
+    def _stage(self, words):
+        """`words` int32 of page-locked memory, this pass's own until the next begin()."""
+        while self.pin_i < len(self.pins) and self.pin_off + words > self.pins[self.pin_i].numel():
+            self.pin_i, self.pin_off = self.pin_i + 1, 0
+        if self.pin_i == len(self.pins):
+            self.pins.append(torch.empty(max(words, PIN_CHUNK_WORDS), dtype=torch.int32).pin_memory())
+        o = self.pin_off
+        self.pin_off += words
+        return self.pins[self.pin_i][o:o + words]
+
+    # ------------------------------------------------------------------ the pass
+    def check_video(self, frames):
+        """Refuse (ValueError) a video the engine cannot take, before anything is enqueued or changed.  -> (frames, clip starts, row0, next row)."""
+        v = _as_u8(frames, "frames")
+        if v.dim() != 4 or v.shape[3] != 3 or v.shape[0] < 1:
+            raise ValueError("frames: shape %s, expected (F, H, W, 3)" % (tuple(v.shape),))
+        F, H, W = (int(s) for s in v.shape[:3])
+        if H < self.hw or W < self.hw:
+            raise ValueError("frames of %d x %d are smaller than the %d x %d crop" % (H, W, self.hw, self.hw))
+        starts = clip_starts(F, np.ones(F, np.int32), self.f_skip)        # every clip with a real frame: each frame belongs to exactly one
+        row0, pos = ring_place(self.pos, len(starts), self.capacity, self.bs)
+        return v, starts, row0, pos
+
+    def add_video(self, frames_u8):
+        """One video: frames [F,H,W,3] uint8 (numpy, host tensor or device tensor).  Uploaded through page-locked memory on the copy stream; its
+        clips join the batches.  -> the index of the video in results()."""
+        v, starts, row0, pos = self.check_video(frames_u8)
+        F, H, W = (int(s) for s in v.shape[:3])
+        h0, w0 = centre_crop(H, W, self.hw)
+        slot = self.up_slot
+        self.up_slot ^= 1
+        if self.up_done[slot] is not None:
+            self.up_done[slot].synchronize()                          # an upload on the copy stream, two videos back: never the compute stream
+        self.pin = self.up_pin[slot]
+        dv, _none, entry = self._upload(v)
+        self.up_pin[slot] = self.pin                                  # (grown, if the video was larger than the slot)
+        rec = SimpleNamespace(video=dv, truth=None, entry=entry, F=F, H=H, W=W, h0=h0, w0=w0, ready=torch.cuda.Event(), waited=False,
+                              starts=starts, rows=len(starts), done=0)
+        rec.ready.record(self.copy_stream)
+        self.up_done[slot] = rec.ready
+        # records [F][8] and the class vector [C + 2] side by side: one copy to the host takes both.  Every frame below F belongs to one clip,
+        # so every mask byte and every record is written by a launch: nothing is filled.
+        rec.dev = torch.empty(F * ops.DETECT_REC_WORDS + self.C + 2, dtype=torch.int32, device=self.dev)
+        rec.mask = torch.empty(F, H, W, dtype=torch.uint8, device=self.dev) if self.masks else None
+        rec.pin = None
+        self.videos.append(rec)
+        self._join(rec, row0, pos)
+        return len(self.videos) - 1
+
+    def _cut(self, rec, first, k, slot):
+        per = self.per
+        ops.clips_from_u8(rec.video, rec.h0, rec.w0, self.hw, rec.starts[first:first + k], self.f_skip, out=self.img[slot * per * 4:(slot + k) * per * 4])
+
+    def _collect(self, rec, first, n, slot):
+        per, hw, W8 = self.per, self.hw, ops.DETECT_REC_WORDS
+        for q in range(0, n, 32):
+            k = min(32, n - q)
+            ops.detect_frames(self.out[(slot + q) * per:(slot + q + k) * per].view(k, 8, hw, hw), rec.starts[first + q:first + q + k], rec.F, rec.H, rec.W,
+                              rec.h0, rec.w0, self.f_skip, row0=rec.row0 + first + q, mask=rec.mask, rec=rec.dev[:rec.F * W8].view(rec.F, W8), ws=self.ws,
+                              want_mask=False)
+
+    def _finish(self, rec):
+        """The video's class from its score rows; records and class vector on their way to the host."""
+        ops.video_class(self.scores[rec.row0:rec.row0 + rec.rows], out=rec.dev[rec.F * ops.DETECT_REC_WORDS:].view(torch.float32))
+        rec.pin = self._stage(rec.dev.numel())
+        rec.pin.copy_(rec.dev, non_blocking=True)
+
+    def results(self):
+        """The pass's one host wait -> [Detection], one per video in arrival order."""
+        self.flush()
+        torch.cuda.current_stream(self.dev).synchronize()
+        out = []
+        for rec in self.videos:
+            words = rec.pin.numpy()
+            counts, boxes, fscores, _rows = ops.decode_detect_records(words[:rec.F * ops.DETECT_REC_WORDS])
+            cls = words[rec.F * ops.DETECT_REC_WORDS:].copy().view(np.float32)
+            out.append(Detection(int(cls[self.C]), float(cls[self.C + 1]), cls[:self.C].copy(), counts, boxes, fscores, rec.mask))
+        return out
+
+    def detect(self, frames_u8):
+        """One video on its own: begin(), add_video, results()[0]."""
+        self.begin()
+        self.add_video(frames_u8)
+        return self.results()[0]

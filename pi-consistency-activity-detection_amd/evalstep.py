@@ -4,6 +4,9 @@ yields), the clips cut on the device straight into the tensor the stem reads (pc
 replayed from ONE op plan of `bs` clips whose weight layouts are made once per pass, and the per-frame counts, the per-class tables and the
 class vote accumulated on the device (pc_seg_frame_counts, pc_map_accumulate, pc_video_vote).  One device-to-host copy per pass (`results`).
 
+ClipEngine holds what EvalEngine shares with detect.DetectEngine (the inference side: unlabelled video in, masks, boxes and tubes out): the
+plan, the upload pool, batch forming, the class-score ring and the batch itself.
+
 The only host wait per video is for its F per-frame truth counts (pc_truth_frame_flags on the copy stream): they decide on the host which
 clips exist (`clip_starts`), as `np.sum(clips[-1][1]) == 0` does in the reference.  The compute stream is never waited for.
 """
@@ -70,17 +73,15 @@ def _as_u8(a, what):
     return t
 
 
-class EvalEngine(PlanEngine):
-    """Evaluates the weights in the flat buffers P, R: a StepEngine's own (StepEngine.eval_engine: no copy, behind its lanes) or, built from a
-    state dict, buffers of its own (load_state per checkpoint).
+class ClipEngine(PlanEngine):
+    """What the engines that run decoded uint8 video through the eval plan share (EvalEngine here, detect.DetectEngine): one plan of `bs` clips
+    whose first conv reads the clip tensor as the clip kernel writes it, the upload pool behind a copy stream, batch forming (pack on / off),
+    the ring of class-score rows, and the batch itself (_run_batch) with three steps left to the subclass: _cut (the clip-making launch),
+    _collect (what is read off a video segment's logits) and _finish (a video's last clip has run)."""
 
-    begin() once per pass, add_video(frames_u8, truth_u8, label) per video, results() at the end -- or evaluate(videos).  pack=False: batches
-    of up to `bs` clips of ONE video, as the reference forms them; pack=True: clips of consecutive videos share full batches.  A batch of
-    m < bs clips runs on the same plan: in eval mode a clip's outputs do not depend on its neighbours, the stale slots cost time only."""
-
-    def __init__(self, bs=14, hw=224, num_classes=24, device="cuda:0", state=None, engine=None, capacity=256, seed=47, f_skip=2, pack=False, on_batch=None):
+    def _setup(self, bs, hw, num_classes, device, state, engine, capacity, seed, f_skip, pack, on_batch):
         if not torch.cuda.is_available():
-            raise RuntimeError("EvalEngine needs a GPU: the hot path is HIP-only (no CPU fallback)")
+            raise RuntimeError("%s needs a GPU: the hot path is HIP-only (no CPU fallback)" % type(self).__name__)
         if bs < 1 or capacity <= bs:
             raise ValueError("bs must be at least 1 and capacity larger than bs")
         capi.lib()
@@ -88,23 +89,16 @@ class EvalEngine(PlanEngine):
         self.capacity, self.f_skip, self.pack, self.on_batch = capacity, f_skip, bool(pack), on_batch
         c = self.c = self._build(bs, lay)
         p = c.plan
-        c.ops["fwd"][p.op_to_ndhwc[0]]["i"][1] = 0                      # N = 0, for good: pc_eval_clips_from_u8 writes the stem's tensor itself
+        c.ops["fwd"][p.op_to_ndhwc[0]]["i"][1] = 0                      # N = 0, for good: the clip kernel writes the stem's tensor itself
         self._view(c, p.in_cls, bs).fill_(500.0)                        # the reference's empty_action (:121-122) as the module's eval slot leaves it
         self._view(c, p.in_labeled, bs, torch.int32).fill_(500)
         self.img = self._view(c, p.img.ref, bs * self.per * 4)          # [bs][8][hw][hw][4]
         self.img.zero_()                                                # slots no batch has filled yet hold numbers, not whatever the allocator left
-        self.gt = torch.zeros(bs * self.per, device=self.dev)           # [bs][8][hw][hw], the truth of the batch in flight
         self.out = self._view(c, p.out.ref, bs * self.per)
         self.pred = self._view(c, p.pred, bs * self.C).view(bs, self.C)
-        self.counts = torch.zeros(capacity * spec.FRAMES, 3, dtype=torch.int32, device=self.dev)
         self.scores = torch.zeros(capacity, self.C, device=self.dev)
-        # the accumulators of evaluate_ucf101.py:66-72 in ONE int32 buffer, so that a pass ends with one device-to-host copy
-        C_, T = self.C, evalmetrics.N_THR
-        self.tables = torch.zeros(2 * C_ * T + 2 * C_ + 1, dtype=torch.int32, device=self.dev)
-        self.acc = self._accumulator(self.tables)
         self.copy_stream = torch.cuda.Stream(device=self.dev)
-        self.pin = None                      # page-locked staging of one video (frames, then truth); free again when its flags have arrived
-        self.pin_flags = self.dev_flags = None
+        self.pin = None                      # page-locked staging of one video (frames, then truth); free again when its upload has run
         self.pool = []                       # device buffers of videos: dict(buf, free: event after the last launch that read it, or None if in use)
         self.gen = self.gen_done = 0
         self.m = 0                           # clips of the last batch
@@ -115,14 +109,6 @@ class EvalEngine(PlanEngine):
         p.build_forward()
         return p
 
-    def _accumulator(self, flat):
-        C_, T = self.C, evalmetrics.N_THR
-        a = evalmetrics.MapAccumulator.__new__(evalmetrics.MapAccumulator)
-        a.n_classes = C_
-        a.frame_hits, a.video_hits = flat[:C_ * T].view(C_, T), flat[C_ * T:2 * C_ * T].view(C_, T)
-        a.n_frames, a.n_vids, a.n_correct = flat[2 * C_ * T:2 * C_ * T + C_], flat[2 * C_ * T + C_:2 * C_ * T + 2 * C_], flat[2 * C_ * T + 2 * C_:]
-        return a
-
     def _reset(self):
         self.pos = 0                         # next free row of the ring
         self.batch = []                      # segments of the batch being filled: (video record, first clip, count)
@@ -132,38 +118,18 @@ class EvalEngine(PlanEngine):
 
     # ------------------------------------------------------------------ the pass
     def begin(self, pack=None):
-        """Start a pass (pack: how batches are formed from here on): zero tables, an empty ring, and the weight layouts (the `prep` and
-        `prep_late` lists) due again in front of the first batch -- the weights do not change during a pass.  Behind a StepEngine, the pass
-        waits for its lanes."""
+        """Start a pass (pack: how batches are formed from here on): the subclass's results cleared (_clear), an empty ring, and the weight
+        layouts (the `prep` and `prep_late` lists) due again in front of the first batch -- the weights do not change during a pass.  Behind a
+        StepEngine, the pass waits for its lanes."""
         for v in self.live:
             self._release(v)
         self._reset()
         if pack is not None:
             self.pack = bool(pack)
         self.gen += 1
-        self.tables.zero_()
+        self._clear()
         if self.side:
             ops.streams_fanin(torch.cuda.current_stream(self.dev), self.side)
-
-    def check_video(self, frames, truth, label):
-        """Refuse (ValueError) a video the engine cannot take, before anything is enqueued or changed.  -> (frames, truth [F,H,W], label)."""
-        v, t = _as_u8(frames, "frames"), _as_u8(truth, "truth")
-        if v.dim() != 4 or v.shape[3] != 3 or v.shape[0] < 1:
-            raise ValueError("frames: shape %s, expected (F, H, W, 3)" % (tuple(v.shape),))
-        F, H, W = (int(s) for s in v.shape[:3])
-        if H < self.hw or W < self.hw:
-            raise ValueError("frames of %d x %d are smaller than the %d x %d crop" % (H, W, self.hw, self.hw))
-        if t.dim() == 4 and t.shape[3] == 1:
-            t = t.reshape(t.shape[:3])
-        if t.dim() != 3 or tuple(t.shape) != (F, H, W):
-            raise ValueError("truth: shape %s, expected (%d, %d, %d) or (%d, %d, %d, 1)" % (tuple(truth.shape), F, H, W, F, H, W))
-        try:
-            lab = int(label)
-        except (TypeError, ValueError):
-            raise ValueError("label: %r is not a class id" % (label,)) from None
-        if lab != label or not 0 <= lab < self.C:
-            raise ValueError("label: %r outside [0, %d)" % (label, self.C))
-        return v, t, lab
 
     def _acquire(self, nbytes):
         """A device buffer of at least nbytes that no launch still to run reads -- the copy stream waits (on the device) for the launches that did."""
@@ -195,23 +161,158 @@ class EvalEngine(PlanEngine):
             v.entry = None
         v.video = v.truth = None             # a caller's device tensors: stream order on the compute stream keeps them until here
 
-    def _upload(self, v, t):
-        """-> (video, truth, entry) on the device, the upload (if any) enqueued on the copy stream."""
-        if v.is_cuda or t.is_cuda:
-            if not (v.is_cuda and t.is_cuda):
+    def _upload(self, v, t=None):
+        """-> (video, truth or None, entry) on the device, the upload (if any) enqueued on the copy stream."""
+        if v.is_cuda or (t is not None and t.is_cuda):
+            if t is None:
+                v = v.to(self.dev)
+            elif not (v.is_cuda and t.is_cuda):
                 v, t = v.to(self.dev), t.to(self.dev)
             self.copy_stream.wait_stream(torch.cuda.current_stream(self.dev))        # whatever produced them
-            return v.contiguous(), t.contiguous(), None
-        nv, nt = v.numel(), t.numel()
+            return v.contiguous(), (None if t is None else t.contiguous()), None
+        nv, nt = v.numel(), (0 if t is None else t.numel())
         o_t = (nv + 255) // 256 * 256
         if self.pin is None or self.pin.numel() < o_t + nt:
             self.pin = torch.empty(o_t + nt, dtype=torch.uint8).pin_memory()
         self.pin[:nv].view(v.shape).copy_(v)
-        self.pin[o_t:o_t + nt].view(t.shape).copy_(t)
+        if t is not None:
+            self.pin[o_t:o_t + nt].view(t.shape).copy_(t)
         e = self._acquire(o_t + nt)
         with torch.cuda.stream(self.copy_stream):
             e["buf"][:o_t + nt].copy_(self.pin[:o_t + nt], non_blocking=True)
-        return e["buf"][:nv].view(v.shape), e["buf"][o_t:o_t + nt].view(t.shape), e
+        return e["buf"][:nv].view(v.shape), (None if t is None else e["buf"][o_t:o_t + nt].view(t.shape)), e
+
+    def _join(self, rec, row0, pos):
+        """A video with rec.rows clips takes the rows ring_place gave it, and its clips join the batches."""
+        if any(row0 < o.row0 + o.rows and o.row0 < row0 + rec.rows for o in self.live):
+            self.flush()                     # rows of a video whose clips still wait for a full batch: run them first (pack=True, a small ring)
+        rec.row0, self.pos = row0, pos
+        self.live.append(rec)
+        self.n_videos += 1
+        self.n_clips += rec.rows
+        if self.pack:
+            first = 0
+            while first < rec.rows:
+                take = min(rec.rows - first, self.bs - self.fill)
+                self.batch.append((rec, first, take))
+                self.fill += take
+                first += take
+                if self.fill == self.bs:
+                    self._run_batch()
+        else:
+            for i in range(0, rec.rows, self.bs):
+                self.batch.append((rec, i, min(self.bs, rec.rows - i)))
+                self._run_batch()
+
+    def flush(self):
+        """Run the clips that wait for a full batch (pack=True) as a short one."""
+        self._run_batch()
+
+    def _run_batch(self):
+        if not self.batch:
+            return
+        c = self.c
+        main = torch.cuda.current_stream(self.dev)
+        slot = 0
+        for rec, first, n in self.batch:                                       # one clip-making launch per video segment (32 clips at most each)
+            if not rec.waited:
+                main.wait_event(rec.ready)
+                rec.waited = True
+            for q in range(0, n, MAX_LAUNCH_CLIPS):
+                self._cut(rec, first + q, min(MAX_LAUNCH_CLIPS, n - q), slot + q)
+            if first + n == rec.rows:
+                self._release(rec)
+            slot += n
+        self.m = slot
+        if self.gen_done != self.gen:                                          # first batch of the pass: the weight layouts
+            ops.run_ops(c.ops["prep"])
+            ops.run_ops(c.ops["prep_late"])
+            self.gen_done = self.gen
+        ops.run_ops(c.ops["fwd"])
+        slot = 0
+        for rec, first, n in self.batch:
+            self._collect(rec, first, n, slot)
+            r = rec.row0 + first
+            self.scores[r:r + n].copy_(self.pred[slot:slot + n])
+            slot += n
+        if self.on_batch is not None:
+            self.on_batch(self.m, *self.outputs())
+        for rec, first, n in self.batch:
+            rec.done += n
+            if rec.done == rec.rows:                                           # the video's last clip has run
+                self._finish(rec)
+                self.live = [o for o in self.live if o is not rec]
+        self.batch, self.fill = [], 0
+
+    def outputs(self):
+        """(output (m,1,8,H,W) logits, predicted_action (m,C)) of the last batch: views of the plan's arena."""
+        return self.out[:self.m * self.per].view(self.m, 1, spec.FRAMES, self.hw, self.hw), self.pred[:self.m]
+
+
+class EvalEngine(ClipEngine):
+    """Evaluates the weights in the flat buffers P, R: a StepEngine's own (StepEngine.eval_engine: no copy, behind its lanes) or, built from a
+    state dict, buffers of its own (load_state per checkpoint).
+
+    begin() once per pass, add_video(frames_u8, truth_u8, label) per video, results() at the end -- or evaluate(videos).  pack=False: batches
+    of up to `bs` clips of ONE video, as the reference forms them; pack=True: clips of consecutive videos share full batches.  A batch of
+    m < bs clips runs on the same plan: in eval mode a clip's outputs do not depend on its neighbours, the stale slots cost time only."""
+
+    def __init__(self, bs=14, hw=224, num_classes=24, device="cuda:0", state=None, engine=None, capacity=256, seed=47, f_skip=2, pack=False, on_batch=None):
+        self._setup(bs, hw, num_classes, device, state, engine, capacity, seed, f_skip, pack, on_batch)
+        self.gt = torch.zeros(bs * self.per, device=self.dev)           # [bs][8][hw][hw], the truth of the batch in flight
+        self.counts = torch.zeros(capacity * spec.FRAMES, 3, dtype=torch.int32, device=self.dev)
+        # the accumulators of evaluate_ucf101.py:66-72 in ONE int32 buffer, so that a pass ends with one device-to-host copy
+        C_, T = self.C, evalmetrics.N_THR
+        self.tables = torch.zeros(2 * C_ * T + 2 * C_ + 1, dtype=torch.int32, device=self.dev)
+        self.acc = self._accumulator(self.tables)
+        self.pin_flags = self.dev_flags = None
+
+    def _accumulator(self, flat):
+        C_, T = self.C, evalmetrics.N_THR
+        a = evalmetrics.MapAccumulator.__new__(evalmetrics.MapAccumulator)
+        a.n_classes = C_
+        a.frame_hits, a.video_hits = flat[:C_ * T].view(C_, T), flat[C_ * T:2 * C_ * T].view(C_, T)
+        a.n_frames, a.n_vids, a.n_correct = flat[2 * C_ * T:2 * C_ * T + C_], flat[2 * C_ * T + C_:2 * C_ * T + 2 * C_], flat[2 * C_ * T + 2 * C_:]
+        return a
+
+    def _clear(self):
+        self.tables.zero_()
+
+    def _cut(self, rec, first, k, slot):
+        per = self.per
+        ops.eval_clips_from_u8(rec.video, rec.truth, rec.h0, rec.w0, self.hw, rec.starts[first:first + k], self.f_skip,
+                               out=(self.img[slot * per * 4:(slot + k) * per * 4], self.gt[slot * per:(slot + k) * per]))
+
+    def _collect(self, rec, first, n, slot):
+        T, per = spec.FRAMES, self.per
+        capi.call("pc_seg_frame_counts", ops.ptr(self.out[slot * per:]), ops.ptr(self.gt[slot * per:]), T * n, self.hw * self.hw,
+                  ops.ptr(self.counts[(rec.row0 + first) * T:]), ops.stream())
+
+    def _finish(self, rec):
+        """The video's rows into the tables."""
+        a, T = self.acc, spec.FRAMES
+        ops.map_accumulate(self.counts[rec.row0 * T:(rec.row0 + rec.rows) * T], rec.label, a.frame_hits, a.video_hits, a.n_frames, a.n_vids)
+        ops.video_vote(self.scores[rec.row0:rec.row0 + rec.rows], rec.label, a.n_correct)
+
+    def check_video(self, frames, truth, label):
+        """Refuse (ValueError) a video the engine cannot take, before anything is enqueued or changed.  -> (frames, truth [F,H,W], label)."""
+        v, t = _as_u8(frames, "frames"), _as_u8(truth, "truth")
+        if v.dim() != 4 or v.shape[3] != 3 or v.shape[0] < 1:
+            raise ValueError("frames: shape %s, expected (F, H, W, 3)" % (tuple(v.shape),))
+        F, H, W = (int(s) for s in v.shape[:3])
+        if H < self.hw or W < self.hw:
+            raise ValueError("frames of %d x %d are smaller than the %d x %d crop" % (H, W, self.hw, self.hw))
+        if t.dim() == 4 and t.shape[3] == 1:
+            t = t.reshape(t.shape[:3])
+        if t.dim() != 3 or tuple(t.shape) != (F, H, W):
+            raise ValueError("truth: shape %s, expected (%d, %d, %d) or (%d, %d, %d, 1)" % (tuple(truth.shape), F, H, W, F, H, W))
+        try:
+            lab = int(label)
+        except (TypeError, ValueError):
+            raise ValueError("label: %r is not a class id" % (label,)) from None
+        if lab != label or not 0 <= lab < self.C:
+            raise ValueError("label: %r outside [0, %d)" % (label, self.C))
+        return v, t, lab
 
     def add_video(self, frames_u8, truth_u8, label):
         """One video: frames [F,H,W,3] uint8, truth [F,H,W] or [F,H,W,1] uint8 (numpy, host tensor or device tensor), class id.  Uploaded through
@@ -242,82 +343,13 @@ class EvalEngine(PlanEngine):
         except ValueError:
             self._release(rec)
             raise
-        if any(row0 < o.row0 + o.rows and o.row0 < row0 + rec.rows for o in self.live):
-            self.flush()                     # rows of a video whose clips still wait for a full batch: run them first (pack=True, a small ring)
-        rec.row0, self.pos = row0, pos
-        self.live.append(rec)
-        self.n_videos += 1
-        self.n_clips += rec.rows
-        if self.pack:
-            first = 0
-            while first < rec.rows:
-                take = min(rec.rows - first, self.bs - self.fill)
-                self.batch.append((rec, first, take))
-                self.fill += take
-                first += take
-                if self.fill == self.bs:
-                    self._run_batch()
-        else:
-            for i in range(0, rec.rows, self.bs):
-                self.batch.append((rec, i, min(self.bs, rec.rows - i)))
-                self._run_batch()
+        self._join(rec, row0, pos)
         return rec.rows
-
-    def flush(self):
-        """Run the clips that wait for a full batch (pack=True) as a short one."""
-        self._run_batch()
-
-    def _run_batch(self):
-        if not self.batch:
-            return
-        c, hw, per = self.c, self.hw, self.per
-        main = torch.cuda.current_stream(self.dev)
-        slot = 0
-        for rec, first, n in self.batch:                                       # one clip-making launch per video segment (32 clips at most each)
-            if not rec.waited:
-                main.wait_event(rec.ready)
-                rec.waited = True
-            for q in range(0, n, MAX_LAUNCH_CLIPS):
-                k = min(MAX_LAUNCH_CLIPS, n - q)
-                o = slot + q
-                ops.eval_clips_from_u8(rec.video, rec.truth, rec.h0, rec.w0, hw, rec.starts[first + q:first + q + k], self.f_skip,
-                                       out=(self.img[o * per * 4:(o + k) * per * 4], self.gt[o * per:(o + k) * per]))
-            if first + n == rec.rows:
-                self._release(rec)
-            slot += n
-        m = self.m = slot
-        if self.gen_done != self.gen:                                          # first batch of the pass: the weight layouts
-            ops.run_ops(c.ops["prep"])
-            ops.run_ops(c.ops["prep_late"])
-            self.gen_done = self.gen
-        ops.run_ops(c.ops["fwd"])
-        slot = 0
-        T = spec.FRAMES
-        for rec, first, n in self.batch:
-            r = rec.row0 + first
-            capi.call("pc_seg_frame_counts", ops.ptr(self.out[slot * per:]), ops.ptr(self.gt[slot * per:]), T * n, hw * hw,
-                      ops.ptr(self.counts[r * T:]), ops.stream())
-            self.scores[r:r + n].copy_(self.pred[slot:slot + n])
-            slot += n
-        if self.on_batch is not None:
-            self.on_batch(m, *self.outputs())
-        for rec, first, n in self.batch:
-            rec.done += n
-            if rec.done == rec.rows:                                           # the video's last clip has run: its rows into the tables
-                a = self.acc
-                ops.map_accumulate(self.counts[rec.row0 * T:(rec.row0 + rec.rows) * T], rec.label, a.frame_hits, a.video_hits, a.n_frames, a.n_vids)
-                ops.video_vote(self.scores[rec.row0:rec.row0 + rec.rows], rec.label, a.n_correct)
-                self.live = [o for o in self.live if o is not rec]
-        self.batch, self.fill = [], 0
 
     def results(self):
         """The pass's one device-to-host copy -> the dict of evalmetrics.MapAccumulator.result()."""
         self.flush()
         return self._accumulator(self.tables.cpu()).result()
-
-    def outputs(self):
-        """(output (m,1,8,H,W) logits, predicted_action (m,C)) of the last batch: views of the plan's arena."""
-        return self.out[:self.m * self.per].view(self.m, 1, spec.FRAMES, self.hw, self.hw), self.pred[:self.m]
 
     def evaluate(self, videos, pack=False):
         """One pass over an iterable of (frames_u8, truth_u8, label) -> results()."""

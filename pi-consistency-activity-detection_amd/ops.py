@@ -604,6 +604,77 @@ def video_vote(pred, label, n_correct):
     capi.call("pc_video_vote", ptr(pred), int(pred.shape[0]), int(pred.shape[1]), int(label), ptr(n_correct), stream())
 
 
+def clips_from_u8(video, h0, w0, S, starts, f_skip=2, out=None):
+    """pc_clips_from_u8: eval_clips_from_u8 without truth.  video uint8 device [F,H,W,3]; starts: 1..32 first-frame indices (host).
+    -> data [n,8,S,S,4] float32 (r, g, b, 0).  out: a contiguous float32 device tensor with room for n clips to write into."""
+    if video.dtype != torch.uint8 or video.dim() != 4 or video.shape[3] != 3 or not video.is_contiguous():
+        raise ValueError("clips_from_u8: contiguous uint8 [F,H,W,3] frames")
+    F, H, W = (int(v) for v in video.shape[:3])
+    n = len(starts)
+    if out is None:
+        out = torch.empty(n, 8, S, S, 4, device=video.device)
+    elif out.dtype != torch.float32 or not out.is_contiguous() or out.numel() < n * 32 * S * S or out.device != video.device:
+        raise ValueError("clips_from_u8: out must be a contiguous float32 device tensor of at least n*8*S*S*4 elements")
+    st = (C.c_int32 * max(n, 1))(*[int(v) for v in starts])
+    capi.call("pc_clips_from_u8", ptr(video), F, H, W, int(h0), int(w0), int(S), st, n, int(f_skip), ptr(out), stream())
+    return out
+
+
+DETECT_REC_WORDS = 8        # a pc_detect_frames record: count, x0, y0, x1, y1, float32 score bits, clip row, 0
+
+
+def detect_frames_ws_bytes(n, S):
+    return int(capi.lib().pc_detect_frames_ws_bytes(int(n), int(S)))
+
+
+def detect_frames(logits, starts, F, H, W, h0, w0, f_skip=2, row0=0, mask=None, rec=None, ws=None, want_mask=True):
+    """pc_detect_frames: logits contiguous float32 device [n,8,S,S] (any shape with those elements; S from the last dim), the eval forward's
+    output for the n <= 32 clips of one video cut at `starts`.  -> (mask uint8 [F,H,W] or None, rec int32 [F,8]); given tensors are written
+    in place -- only the frames the clips address -- fresh ones are zero-filled first.  want_mask=False with mask=None: records only."""
+    if logits.dtype != torch.float32 or not logits.is_contiguous():
+        raise ValueError("detect_frames: contiguous float32 logits")
+    S, n = int(logits.shape[-1]), len(starts)
+    if int(logits.shape[-2]) != S or logits.numel() < n * 8 * S * S:
+        raise ValueError("detect_frames: logits %s do not hold %d clips of 8 x %d x %d" % (tuple(logits.shape), n, S, S))
+    dev = logits.device
+    if mask is None and want_mask:
+        mask = torch.zeros(F, H, W, dtype=torch.uint8, device=dev)
+    if mask is not None and (mask.dtype != torch.uint8 or not mask.is_contiguous() or mask.numel() != F * H * W or mask.device != dev):
+        raise ValueError("detect_frames: mask must be a contiguous uint8 device tensor [F,H,W]")
+    if rec is None:
+        rec = torch.zeros(F, DETECT_REC_WORDS, dtype=torch.int32, device=dev)
+    elif rec.dtype != torch.int32 or not rec.is_contiguous() or rec.numel() != F * DETECT_REC_WORDS or rec.device != dev:
+        raise ValueError("detect_frames: rec must be a contiguous int32 device tensor [F,8]")
+    need = detect_frames_ws_bytes(n, S)
+    if ws is None and need > 0:
+        ws = torch.empty(need, dtype=torch.uint8, device=dev)
+    elif ws is not None and (not ws.is_contiguous() or ws.numel() * ws.element_size() < need or ws.device != dev):
+        raise ValueError("detect_frames: ws must hold detect_frames_ws_bytes(n, S) = %d bytes" % need)
+    st = (C.c_int32 * max(n, 1))(*[int(v) for v in starts])
+    capi.call("pc_detect_frames", ptr(logits), int(F), int(H), int(W), int(h0), int(w0), S, st, n, int(f_skip), int(row0), ptr(mask), ptr(rec),
+              ptr(ws), stream())
+    return mask, rec
+
+
+def decode_detect_records(rec):
+    """Host int32 [F,8] records (numpy or torch) -> (counts int32 [F], boxes int32 [F,4] = x0, y0, x1, y1, frame_scores float32 [F], rows int32 [F])."""
+    r = np.ascontiguousarray(rec.cpu().numpy() if torch.is_tensor(rec) else rec, dtype=np.int32).reshape(-1, DETECT_REC_WORDS)
+    return r[:, 0].copy(), r[:, 1:5].copy(), r[:, 5].copy().view(np.float32), r[:, 6].copy()
+
+
+def video_class(scores, out=None):
+    """pc_video_class: scores contiguous float32 device [n,C] -> float32 device [C + 2]: mean class scores, arg-max (as a float), its mean."""
+    if scores.dtype != torch.float32 or scores.dim() != 2 or not scores.is_contiguous():
+        raise ValueError("video_class: contiguous float32 [n,C] scores")
+    n, C_ = (int(v) for v in scores.shape)
+    if out is None:
+        out = torch.empty(C_ + 2, device=scores.device)
+    elif out.dtype != torch.float32 or not out.is_contiguous() or out.numel() != C_ + 2 or out.device != scores.device:
+        raise ValueError("video_class: out must be a contiguous float32 device tensor of C + 2 elements")
+    capi.call("pc_video_class", ptr(scores), n, C_, ptr(out), stream())
+    return out
+
+
 _RESIZE_TABS = {}
 
 

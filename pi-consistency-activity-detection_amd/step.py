@@ -508,6 +508,12 @@ class StepEngine:
         from .evalstep import EvalEngine
         return EvalEngine(bs, capacity=capacity, engine=self, **kw)
 
+    def detect_engine(self, bs=14, capacity=256, **kw):
+        """-> detect.DetectEngine over THIS engine's parameter and running-statistics buffers (no copy: a detection pass sees what the last
+        train step left) and behind its lanes; arena, masks, records and staging are the DetectEngine's own.  bs: clips per batch."""
+        from .detect import DetectEngine
+        return DetectEngine(bs, capacity=capacity, engine=self, **kw)
+
     def make_reducer(self, group=None, target_floats=3_000_000, force=False, check=True):
         """check: refuse to train if the ranks do not hold identical parameters (dist.check_replicas_agree: one 3-number all-reduce)."""
         from . import dist as pdist

@@ -1,0 +1,75 @@
+#!/usr/bin/env python3
+"""Detections from decoded uint8 video on one MI355X (detect.DetectEngine): where the action is and which action it is.
+
+Weights: a checkpoint in the reference's key layout (--ckpt, a torch.save'd state_dict), or the synthetic initial state.  Videos: .npy files
+of uint8 frames [F,H,W,3] with frames at least hw x hw (ops.resize_u8 scales decoded frames on the device), or --synthetic N videos of
+synthetic.make_eval_videos_u8.  One pass; one .npz with, per video i: label_i, class_scores_i [C], counts_i [F], boxes_i [F,4] (x0, y0, x1, y1,
+half-open, full-frame coordinates), frame_scores_i [F], tubes_i [T,3] = (t0, t1 inclusive, score), and with --masks masks_i = np.packbits of
+the uint8 masks [F,H,W] (mask_shape_i to unpack them).
+
+    python tools/detect.py --out detections.npz [--ckpt best_model.pth] [--synthetic 4 | video.npy ...] [--masks] [--pack] [--max-gap 0] [--min-pixels 1]
+"""
+import argparse
+import os
+import sys
+
+import numpy as np
+import torch
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import picons_amd  # noqa: F401,E402
+from picons_amd import detect, synthetic  # noqa: E402
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("videos", nargs="*", help=".npy files of uint8 frames [F,H,W,3]")
+    ap.add_argument("--out", default="detections.npz")
+    ap.add_argument("--ckpt", default=None)
+    ap.add_argument("--synthetic", type=int, default=0, help="use N synthetic videos (the default, with 4, when no file is given)")
+    ap.add_argument("--classes", type=int, default=24)
+    ap.add_argument("--hw", type=int, default=224)
+    ap.add_argument("--bs", type=int, default=14)
+    ap.add_argument("--masks", action="store_true")
+    ap.add_argument("--pack", action="store_true")
+    ap.add_argument("--min-pixels", type=int, default=1)
+    ap.add_argument("--max-gap", type=int, default=0)
+    a = ap.parse_args()
+    if not torch.cuda.is_available():
+        raise SystemExit("tools/detect.py needs a GPU: the hot path is HIP-only (no CPU fallback)")
+    if a.ckpt:
+        state = torch.load(a.ckpt, map_location="cpu")
+        state = state.get("state_dict", state) if isinstance(state, dict) else state
+        state = {(k[7:] if k.startswith("module.") else k): v for k, v in state.items()}
+    else:
+        state = synthetic.init_state(47, a.classes)
+    names = list(a.videos)
+    if names:
+        videos = [np.load(n) for n in names]
+    else:
+        n = a.synthetic or 4
+        videos = [v[0] for v in synthetic.make_eval_videos_u8(n, num_classes=a.classes, hw=a.hw)]
+        names = ["synthetic_%d" % i for i in range(n)]
+    engine = detect.DetectEngine(bs=a.bs, hw=a.hw, num_classes=a.classes, state=state, pack=a.pack, masks=a.masks)
+    engine.begin()
+    for v in videos:
+        engine.add_video(v)
+    out = {"names": np.array(names)}
+    for i, (name, d) in enumerate(zip(names, engine.results())):
+        tubes = d.tubes(a.min_pixels, a.max_gap)
+        out.update({"label_%d" % i: np.int32(d.label), "class_scores_%d" % i: d.class_scores, "counts_%d" % i: d.counts, "boxes_%d" % i: d.boxes,
+                    "frame_scores_%d" % i: d.frame_scores,
+                    "tubes_%d" % i: np.array([(t0, t1, s) for t0, t1, _b, s in tubes], np.float64).reshape(-1, 3)})
+        if a.masks:
+            m = d.masks.cpu().numpy()
+            out.update({"masks_%d" % i: np.packbits(m), "mask_shape_%d" % i: np.array(m.shape, np.int64)})
+        print("%s: %d frames, class %d (%.4f), %d frames detected, %d tube(s)%s" % (
+            name, d.counts.size, d.label, d.class_score, int((d.counts >= a.min_pixels).sum()), len(tubes),
+            "".join("  [%d..%d] %.3f" % (t0, t1, s) for t0, t1, _b, s in tubes[:4])))
+    os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+    np.savez_compressed(a.out, **out)
+    print("wrote %s (%d videos, %d clips)" % (a.out, len(names), engine.n_clips))
+
+
+if __name__ == "__main__":
+    main()
