@@ -65,7 +65,8 @@ typedef void* pc_stream;            /* hipStream_t */
  * PC_OP_TAIL_GRADS; 103: the variant reporters pc_conv_variant / pc_wino_variant / pc_wgrad_variant;
  * 104: PC_F_BKMAJOR, pc_wino_weights_multi / PC_OP_WINO_WEIGHTS_MULTI; 105: pc_val_metrics / PC_OP_VAL_METRICS;
  * 106: pc_truth_frame_flags / pc_eval_clips_from_u8 / pc_video_vote;
- * 107: pc_clips_from_u8 / pc_detect_frames / pc_detect_frames_ws_bytes / pc_video_class).  Descriptors must be zero-initialised by the caller:
+ * 107: pc_clips_from_u8 / pc_detect_frames / pc_detect_frames_ws_bytes / pc_video_class; the entries pc_clips_from_u8_views / pc_detect_frames_views /
+ * pc_detect_frames_views_ws_bytes came later and move nothing: no struct grew, no op's operands changed).  Descriptors must be zero-initialised by the caller:
  * fields added later read as "old behaviour" when 0.  pc_version() returns the value the library was built with; the Python host
  * (capi.lib()) refuses a library whose version differs from the header it mirrors. */
 #define PC_VERSION 107
@@ -429,6 +430,27 @@ int64_t pc_detect_frames_ws_bytes(int n, int S);
 int     pc_detect_frames(const float* logits, int F, int H, int W, int h0, int w0, int S, const int32_t* starts, int n, int f_skip,
                          int row0, uint8_t* mask, int32_t* rec, void* ws, pc_stream s);
 int     pc_video_class(const float* scores, int n, int C, float* out, pc_stream s);
+/* Multi-view detection (picons_amd/detect.py: DetectEngine(tile=, flip=, views=)).  A view is a crop of the frame, optionally mirrored left-right:
+ * `views` is a HOST table int32 [V][3] = h0, w0, flip (1 <= V <= 32, every crop inside the frame, flip 0 or 1).  View v of clip c lies at clip
+ * slot v * view_stride + c of `data` / `logits` (view_stride >= n, in clips): the caller decides the slot layout.
+ * pc_clips_from_u8_views: pc_clips_from_u8 for all V views of the n <= 32 clips in ONE launch (grid.y = V * n * 8).  An unflipped view holds the
+ * bytes pc_clips_from_u8 writes for its crop (the same u8 / 255 table, zeros for a frame index >= F, a fourth channel of exactly 0); in a
+ * flipped view data[y][x] is the pixel at (h0 + y, w0 + S - 1 - x).  Slots between the views (view_stride > n) are not touched.
+ * pc_detect_frames_views: pc_detect_frames with the views merged per FULL-FRAME pixel in front of the predicate.  The views that cover the pixel
+ * are visited in table order (a flipped view is read at x' = S - 1 - (x - w0)): the first value is taken as it is, later ones are added with
+ * __fadd_rn, and the sum is divided once with __fdiv_rn by (float)count when count > 1 -- no zero start, so -0.0 and NaN pass through.  A pixel
+ * no view covers is background (0).  Mask, predicate (seg_positive), record layout, frame rules (f >= F neither read nor written, a frame the
+ * launch does not address untouched, a null `mask` gives records only) and the score's arithmetic (fp32 sigmoid of the MERGED logit, summed in
+ * double in a fixed order: thread, wave, block partial in `ws`, a second launch adds the partials in block order) are pc_detect_frames'; the box
+ * is in full-frame coordinates and rec[6] = row0 + c * V, the ring row of the clip's first view.  The blocks of a frame stride over its H * W
+ * pixels: pc_detect_frames_views_ws_bytes(n, H, W) = n * 8 * min(64, ceil(ceil(H * W / 4) / 1024)) * 32 bytes (host-only; -1 for n outside
+ * 1..32, H or W < 1, H * W >= 2^31).  No atomics, nothing to zero in front of the launch.  Refusals: pc_detect_frames' list (S % 4 == 0 and the
+ * alignments included), the view-table checks and view_stride < n -- PC_E_ARG before any HIP call. */
+int     pc_clips_from_u8_views(const uint8_t* video, int F, int H, int W, int S, const int32_t* views, int V, int view_stride,
+                               const int32_t* starts, int n, int f_skip, float* data, pc_stream s);
+int64_t pc_detect_frames_views_ws_bytes(int n, int H, int W);
+int     pc_detect_frames_views(const float* logits, int F, int H, int W, int S, const int32_t* views, int V, int view_stride,
+                               const int32_t* starts, int n, int f_skip, int row0, uint8_t* mask, int32_t* rec, void* ws, pc_stream s);
 /* cv2.resize on uint8 images [n][H][W][C] -> [n][Ho][Wo][C] (C <= 4), the calls of the reference's loaders:
  * datasets/jhmdb_dataloader.py:252 (frames, INTER_AREA 320x240 -> 256x256), :267,:281 (puppet masks, INTER_NEAREST),
  * :192,:208 and ucf_dataloader.py:165,171 (224 crop -> frame size, INTER_LINEAR; the identity at 224).  OpenCV's 8-bit

@@ -5,6 +5,7 @@
 //   pc_eval_clips_from_u8  up to 32 clips of one video straight into the NDHWC tensor the stem reads and the frame-major truth
 //                          pc_seg_frame_counts takes; HBM-bound, 4 bytes read and 20 written per pixel
 //   pc_clips_from_u8       the same kernel without the truth side (unlabelled video: picons_amd/detect.py)
+//   pc_clips_from_u8_views pc_clips_from_u8 for V views (crops at their own offsets, some mirrored left-right) of the clips in one launch
 //   pc_video_vote          argmax(mean(predictions, axis=0)) == label, rows added in order in fp32 as numpy adds them
 #include "common.h"
 #include "evalpred.h"
@@ -127,5 +128,79 @@ extern "C" int pc_video_vote(const float* pred, int n, int C, int label, int32_t
     PC_CHECK_ARG(label >= 0 && label < C, "pc_video_vote: label %d outside [0, %d)", label, C);
     hipLaunchKernelGGL(video_vote_kernel, dim3(1), dim3(256), 0, (hipStream_t)s, pred, n, C, label, n_correct);
     PC_CHECK_LAUNCH("video_vote");
+    return PC_OK;
+}
+
+// ---------------------------------------------------------------------- views (detect.DetectEngine, tile / flip)
+namespace {
+
+constexpr int MAX_VIEWS = 32;
+
+struct ClipViewsK {
+    const uint8_t* video;
+    int F, H, W, S, f_skip, n, view_stride;
+    int starts[MAX_CLIPS];
+    int vh0[MAX_VIEWS], vw0[MAX_VIEWS];
+    uint32_t flips;                                                  // bit v: view v is mirrored left-right
+    float4* data;
+};
+
+// pc_clips_from_u8 for V views (crops at their own offsets, some mirrored) of the n clips in one launch: blockIdx.y = (view * n + clip) * 8 +
+// frame of the clip, written at clip slot view * view_stride + clip; blockIdx.x strides over the S*S pixels, one whole float4 per thread as
+// in eval_clips_from_u8_kernel.  A mirrored view reads its row backwards: consecutive lanes, descending 3-byte pixels of one row.
+__global__ __launch_bounds__(256) void clips_from_u8_views_kernel(const ClipViewsK p) {
+    __shared__ float lut[256];
+    lut[threadIdx.x] = (float)((double)threadIdx.x / 255.0);        // the table of eval_clips_from_u8_kernel
+    __syncthreads();
+    const int v = blockIdx.y / (p.n * 8), ck = blockIdx.y - v * (p.n * 8);
+    const int c = ck >> 3, k = ck & 7;
+    const int64_t f = (int64_t)p.starts[c] + (int64_t)k * p.f_skip;
+    const int S = p.S, total = S * S;
+    float4* data = p.data + (((size_t)v * p.view_stride + c) * 8 + k) * total;
+    if (f >= p.F) {                                                  // a frame past the end: zeros, nothing read
+        for (int idx = blockIdx.x * 256 + threadIdx.x; idx < total; idx += gridDim.x * 256) data[idx] = make_float4(0.f, 0.f, 0.f, 0.f);
+        return;
+    }
+    const bool flip = (p.flips >> v) & 1u;
+    const uint8_t* vf = p.video + (((size_t)f * p.H + p.vh0[v]) * p.W + p.vw0[v]) * 3;
+    for (int idx = blockIdx.x * 256 + threadIdx.x; idx < total; idx += gridDim.x * 256) {
+        const int y = idx / S, x = idx - y * S;
+        const uint8_t* px = vf + ((size_t)y * p.W + (flip ? S - 1 - x : x)) * 3;
+        data[idx] = make_float4(lut[px[0]], lut[px[1]], lut[px[2]], 0.f);
+    }
+}
+
+}  // namespace
+
+extern "C" int pc_clips_from_u8_views(const uint8_t* video, int F, int H, int W, int S, const int32_t* views, int V, int view_stride,
+                                      const int32_t* starts, int n, int f_skip, float* data, pc_stream s) {
+    const char* who = "pc_clips_from_u8_views";
+    PC_CHECK_ARG(video && views && starts && data, "%s: null pointer", who);
+    PC_CHECK_ARG(F >= 1 && H >= 1 && W >= 1 && S >= 1 && S <= 32768 && S <= H && S <= W, "%s: %d frames, crop of %d outside %d x %d", who, F, S, H, W);
+    PC_CHECK_ARG(V >= 1 && V <= MAX_VIEWS, "%s: V = %d views outside 1..%d", who, V, MAX_VIEWS);
+    PC_CHECK_ARG(n >= 1 && n <= MAX_CLIPS, "%s: n = %d clips outside 1..%d", who, n, MAX_CLIPS);
+    PC_CHECK_ARG(view_stride >= n, "%s: view_stride = %d is below the n = %d clips of a view", who, view_stride, n);
+    PC_CHECK_ARG(f_skip >= 1, "%s: f_skip = %d", who, f_skip);
+    PC_CHECK_ARG((uintptr_t)data % 16 == 0, "%s: data must be 16-byte aligned", who);
+    ClipViewsK k;
+    k.video = video; k.F = F; k.H = H; k.W = W; k.S = S; k.f_skip = f_skip; k.n = n; k.view_stride = view_stride; k.flips = 0;
+    k.data = (float4*)data;
+    for (int v = 0; v < MAX_VIEWS; ++v) {
+        k.vh0[v] = k.vw0[v] = 0;
+        if (v >= V) continue;
+        const int h0 = views[3 * v], w0 = views[3 * v + 1], fl = views[3 * v + 2];
+        PC_CHECK_ARG(h0 >= 0 && w0 >= 0 && (int64_t)h0 + S <= H && (int64_t)w0 + S <= W, "%s: view %d, crop %d+%d x %d+%d outside %d x %d", who, v,
+                     h0, S, w0, S, H, W);
+        PC_CHECK_ARG(fl == 0 || fl == 1, "%s: view %d, flip = %d is neither 0 nor 1", who, v, fl);
+        k.vh0[v] = h0; k.vw0[v] = w0; k.flips |= (uint32_t)fl << v;
+    }
+    for (int c = 0; c < MAX_CLIPS; ++c) {
+        if (c < n) PC_CHECK_ARG(starts[c] >= 0, "%s: start %d of clip %d is negative", who, starts[c], c);
+        k.starts[c] = c < n ? starts[c] : 0;
+    }
+    int gx = cdiv((int64_t)S * S, 1024);                             // ~4 pixels per thread
+    if (gx > 1024) gx = 1024;
+    hipLaunchKernelGGL(clips_from_u8_views_kernel, dim3((unsigned)gx, (unsigned)(V * n * 8)), dim3(256), 0, (hipStream_t)s, k);
+    PC_CHECK_LAUNCH(who);
     return PC_OK;
 }

@@ -10,6 +10,12 @@ page-locked slot): `results()` is the one host wait of a pass.  The masks stay o
 The mask predicate is the evaluator's own (fp32 sigmoid(x) >= 0.5, one device function for both kernels), so a detection and the f-mAP /
 v-mAP that scores it cannot disagree on a pixel.  The model localises one actor per clip, as the reference's does: a tube is a run of
 detected frames, its class and class score are the video's.
+
+Views.  By default the network sees the centre hw x hw crop of every frame, as the reference's evaluator does.  With tile / flip / views a
+video is cut into several VIEWS (h0, w0, flip) -- crops at their own offsets, optionally mirrored left-right; the model is trained on random
+crops and its consistency loss ties the map of a clip to the map of its mirror image -- every view runs through the same plan, and
+pc_detect_frames_views merges their logits per full-frame pixel (the mean over the views that cover the pixel) in front of the threshold,
+the box and the score: one pc_clips_from_u8_views launch in front of the forward and one merge launch behind it per video segment.
 """
 from types import SimpleNamespace
 
@@ -20,6 +26,7 @@ from . import ops
 from .evalstep import ClipEngine, _as_u8, centre_crop, clip_starts, ring_place
 
 PIN_CHUNK_WORDS = 1 << 18          # page-locked staging of the records, 1 MiB at a time
+MAX_VIEWS = ops.MAX_VIEWS          # views of one video (one launch cuts, one merges, all of them)
 
 
 # ---------------------------------------------------------------------- pure host functions (tests/test_detect_cpu.py)
@@ -44,14 +51,47 @@ def link_tubes(counts, boxes, frame_scores, min_pixels=1, max_gap=0):
     return [(t0, t1, boxes[t0:t1 + 1].copy(), float(scores[t0:t1 + 1][on[t0:t1 + 1]].mean())) for t0, t1 in runs]
 
 
+def _tile_offsets(L, hw):
+    nt = -(-L // hw)
+    return [0] if nt == 1 else [(i * (L - hw)) // (nt - 1) for i in range(nt)]
+
+
+def check_views(views, H, W, hw):
+    """Views given by a caller -> [(h0, w0, flip)] as ints, or ValueError: 1..MAX_VIEWS of them, every crop inside the frame, flip 0 or 1."""
+    try:
+        out = [(int(h0), int(w0), int(fl)) for h0, w0, fl in views]
+    except (TypeError, ValueError):
+        raise ValueError("views: a list of (h0, w0, flip), got %r" % (views,)) from None
+    if not 1 <= len(out) <= MAX_VIEWS:
+        raise ValueError("%d views for frames of %d x %d: 1..%d are allowed" % (len(out), H, W, MAX_VIEWS))
+    for h0, w0, fl in out:
+        if h0 < 0 or w0 < 0 or h0 + hw > H or w0 + hw > W or fl not in (0, 1):
+            raise ValueError("view (%d, %d, %d): a %d x %d crop outside the %d x %d frame, or flip not 0 / 1" % (h0, w0, fl, hw, hw, H, W))
+    return out
+
+
+def make_views(H, W, hw, tile=False, flip=False):
+    """The views (h0, w0, flip) of an H x W frame for a network of hw x hw.  tile=False: the centre crop.  tile=True: each axis of length L
+    gets ceil(L / hw) crops at the offsets (i * (L - hw)) // (nt - 1), so that every frame pixel is covered; y-major, x-minor.  flip=True: each
+    crop is followed directly by its mirrored twin.  More than MAX_VIEWS views: ValueError."""
+    if hw < 1 or H < hw or W < hw:
+        raise ValueError("frames of %d x %d are smaller than the %d x %d crop" % (H, W, hw, hw))
+    tiles = [(h0, w0) for h0 in _tile_offsets(H, hw) for w0 in _tile_offsets(W, hw)] if tile else [centre_crop(H, W, hw)]
+    views = [(h0, w0, fl) for h0, w0 in tiles for fl in ((0, 1) if flip else (0,))]
+    if len(views) > MAX_VIEWS:
+        raise ValueError("frames of %d x %d at hw = %d need %d views, more than the %d allowed" % (H, W, hw, len(views), MAX_VIEWS))
+    return views
+
+
 class Detection:
     """One video's detections.  label / class_score / class_scores [C]: the arg-max of the mean class scores of its clips, that mean, all means;
     counts [F] positive pixels, boxes [F, 4] = x0, y0, x1, y1 (half-open, full-frame coordinates, zeros for an empty frame) and frame_scores [F]
-    (mean sigmoid over the positive pixels) per frame; masks: device uint8 [F, H, W] or None."""
+    (mean sigmoid over the positive pixels) per frame; masks: device uint8 [F, H, W] or None; views: the (h0, w0, flip) the video was seen
+    through."""
 
-    def __init__(self, label, class_score, class_scores, counts, boxes, frame_scores, masks):
+    def __init__(self, label, class_score, class_scores, counts, boxes, frame_scores, masks, views=None):
         self.label, self.class_score, self.class_scores = label, class_score, class_scores
-        self.counts, self.boxes, self.frame_scores, self.masks = counts, boxes, frame_scores, masks
+        self.counts, self.boxes, self.frame_scores, self.masks, self.views = counts, boxes, frame_scores, masks, views
 
     def tubes(self, min_pixels=1, max_gap=0):
         return link_tubes(self.counts, self.boxes, self.frame_scores, min_pixels, max_gap)
@@ -62,16 +102,25 @@ class DetectEngine(ClipEngine):
     from a state dict, buffers of its own (load_state per checkpoint).
 
     begin() once per pass, add_video(frames_u8) per video, results() at the end -- or detect(frames_u8).  pack as in EvalEngine.
-    masks=False: records only (the kernel gets a null mask)."""
+    masks=False: records only (the kernel gets a null mask).
+
+    tile / flip: make_views per video (every frame pixel covered; each crop also mirrored); views: an explicit list of (h0, w0, flip) for
+    every video.  With any of the three the engine runs V views per clip: all V share a batch, so a batch holds bs // V clips -- bs should be
+    a multiple of V, bs < V is refused -- and a video takes clips * V rows of the score ring, row0 + clip * V + view, over all of which its
+    class is voted.  A segment of n clips lies view-major in the batch (view v of its clip c at slot v * n + c of the segment's n * V slots:
+    the order on_batch / outputs() show).  Without them: the centre crop, pc_clips_from_u8 and pc_detect_frames, as before."""
 
     def __init__(self, bs=14, hw=224, num_classes=24, device="cuda:0", state=None, engine=None, capacity=256, seed=47, f_skip=2, pack=False,
-                 masks=True, on_batch=None):
+                 masks=True, on_batch=None, tile=False, flip=False, views=None):
         hw = engine.hw if engine is not None else hw
         if hw % 4:
             raise ValueError("DetectEngine: hw = %d must be a multiple of 4 (pc_detect_frames reads the logit rows 16 bytes at a time)" % hw)
         self._setup(bs, hw, num_classes, device, state, engine, capacity, seed, f_skip, pack, on_batch)
         self.masks = bool(masks)
+        self.tile, self.flip, self.view_list = bool(tile), bool(flip), (None if views is None else list(views))
+        self.multi = self.tile or self.flip or views is not None
         self.ws = torch.empty(ops.detect_frames_ws_bytes(min(bs, 32), self.hw), dtype=torch.uint8, device=self.dev)
+        self.ws_views = None                 # the merge's partials: sized for the first video's frame, grown only for a larger one
         self.pins = []                       # page-locked chunks the records of a pass are copied into
         # upload staging: two page-locked slots, so that the host fills one while the copy stream still reads the other (EvalEngine has one:
         # it waits for every video's flags).  A slot is filled again once the upload of two videos ago has left it.
@@ -102,8 +151,20 @@ class DetectEngine(ClipEngine):
         if H < self.hw or W < self.hw:
             raise ValueError("frames of %d x %d are smaller than the %d x %d crop" % (H, W, self.hw, self.hw))
         starts = clip_starts(F, np.ones(F, np.int32), self.f_skip)        # every clip with a real frame: each frame belongs to exactly one
-        row0, pos = ring_place(self.pos, len(starts), self.capacity, self.bs)
+        row0, pos = ring_place(self.pos, len(starts) * len(self.video_views(H, W) or (0,)), self.capacity, self.bs)
         return v, starts, row0, pos
+
+    def video_views(self, H, W):
+        """The views of an H x W video, None for the centre crop alone on today's path.  ValueError for views the engine cannot take."""
+        if not self.multi:
+            return None
+        views = make_views(H, W, self.hw, self.tile, self.flip) if self.view_list is None else check_views(self.view_list, H, W, self.hw)
+        if len(views) > self.bs:
+            raise ValueError("frames of %d x %d take %d views per clip, more than the bs = %d clips of a batch" % (H, W, len(views), self.bs))
+        return views
+
+    def _width(self, rec):
+        return len(rec.views) if rec.views else 1
 
     def add_video(self, frames_u8):
         """One video: frames [F,H,W,3] uint8 (numpy, host tensor or device tensor).  Uploaded through page-locked memory on the copy stream; its
@@ -111,6 +172,7 @@ class DetectEngine(ClipEngine):
         v, starts, row0, pos = self.check_video(frames_u8)
         F, H, W = (int(s) for s in v.shape[:3])
         h0, w0 = centre_crop(H, W, self.hw)
+        views = self.video_views(H, W)
         slot = self.up_slot
         self.up_slot ^= 1
         if self.up_done[slot] is not None:
@@ -119,7 +181,7 @@ class DetectEngine(ClipEngine):
         dv, _none, entry = self._upload(v)
         self.up_pin[slot] = self.pin                                  # (grown, if the video was larger than the slot)
         rec = SimpleNamespace(video=dv, truth=None, entry=entry, F=F, H=H, W=W, h0=h0, w0=w0, ready=torch.cuda.Event(), waited=False,
-                              starts=starts, rows=len(starts), done=0)
+                              starts=starts, rows=len(starts) * len(views or (0,)), done=0, views=views)
         rec.ready.record(self.copy_stream)
         self.up_done[slot] = rec.ready
         # records [F][8] and the class vector [C + 2] side by side: one copy to the host takes both.  Every frame below F belongs to one clip,
@@ -127,16 +189,32 @@ class DetectEngine(ClipEngine):
         rec.dev = torch.empty(F * ops.DETECT_REC_WORDS + self.C + 2, dtype=torch.int32, device=self.dev)
         rec.mask = torch.empty(F, H, W, dtype=torch.uint8, device=self.dev) if self.masks else None
         rec.pin = None
+        if views:
+            need = ops.detect_frames_views_ws_bytes(min(self.bs, 32), H, W)
+            if self.ws_views is None or self.ws_views.numel() < need:
+                self.ws_views = torch.empty(need, dtype=torch.uint8, device=self.dev)
         self.videos.append(rec)
         self._join(rec, row0, pos)
         return len(self.videos) - 1
 
-    def _cut(self, rec, first, k, slot):
+    def _cut(self, rec, first, k, slot, seg):
         per = self.per
+        if rec.views:                        # view v of the segment's clip c at slot v * seg + c: this launch's clips start at `slot`
+            ops.clips_from_u8_views(rec.video, rec.views, self.hw, rec.starts[first:first + k], self.f_skip, view_stride=seg,
+                                    out=self.img[slot * per * 4:(slot + (len(rec.views) - 1) * seg + k) * per * 4])
+            return
         ops.clips_from_u8(rec.video, rec.h0, rec.w0, self.hw, rec.starts[first:first + k], self.f_skip, out=self.img[slot * per * 4:(slot + k) * per * 4])
 
     def _collect(self, rec, first, n, slot):
         per, hw, W8 = self.per, self.hw, ops.DETECT_REC_WORDS
+        if rec.views:
+            V = len(rec.views)
+            for q in range(0, n, 32):
+                k = min(32, n - q)
+                ops.detect_frames_views(self.out[(slot + q) * per:(slot + q + (V - 1) * n + k) * per].view(-1, 8, hw, hw), rec.views,
+                                        rec.starts[first + q:first + q + k], rec.F, rec.H, rec.W, self.f_skip, view_stride=n, row0=rec.row0 + (first + q) * V,
+                                        mask=rec.mask, rec=rec.dev[:rec.F * W8].view(rec.F, W8), ws=self.ws_views, want_mask=False)
+            return
         for q in range(0, n, 32):
             k = min(32, n - q)
             ops.detect_frames(self.out[(slot + q) * per:(slot + q + k) * per].view(k, 8, hw, hw), rec.starts[first + q:first + q + k], rec.F, rec.H, rec.W,
@@ -158,7 +236,8 @@ class DetectEngine(ClipEngine):
             words = rec.pin.numpy()
             counts, boxes, fscores, _rows = ops.decode_detect_records(words[:rec.F * ops.DETECT_REC_WORDS])
             cls = words[rec.F * ops.DETECT_REC_WORDS:].copy().view(np.float32)
-            out.append(Detection(int(cls[self.C]), float(cls[self.C + 1]), cls[:self.C].copy(), counts, boxes, fscores, rec.mask))
+            out.append(Detection(int(cls[self.C]), float(cls[self.C + 1]), cls[:self.C].copy(), counts, boxes, fscores, rec.mask,
+                                 list(rec.views) if rec.views else [(rec.h0, rec.w0, 0)]))
         return out
 
     def detect(self, frames_u8):

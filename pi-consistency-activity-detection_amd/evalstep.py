@@ -76,8 +76,9 @@ def _as_u8(a, what):
 class ClipEngine(PlanEngine):
     """What the engines that run decoded uint8 video through the eval plan share (EvalEngine here, detect.DetectEngine): one plan of `bs` clips
     whose first conv reads the clip tensor as the clip kernel writes it, the upload pool behind a copy stream, batch forming (pack on / off),
-    the ring of class-score rows, and the batch itself (_run_batch) with three steps left to the subclass: _cut (the clip-making launch),
-    _collect (what is read off a video segment's logits) and _finish (a video's last clip has run)."""
+    the ring of class-score rows, and the batch itself (_run_batch) with three steps left to the subclass: _cut (the clip-making launch;
+    its last argument is the clip count of the whole segment the launch's clips belong to), _collect (what is read off a video segment's logits)
+    and _finish (a video's last clip has run)."""
 
     def _setup(self, bs, hw, num_classes, device, state, engine, capacity, seed, f_skip, pack, on_batch):
         if not torch.cuda.is_available():
@@ -182,26 +183,35 @@ class ClipEngine(PlanEngine):
             e["buf"][:o_t + nt].copy_(self.pin[:o_t + nt], non_blocking=True)
         return e["buf"][:nv].view(v.shape), (None if t is None else e["buf"][o_t:o_t + nt].view(t.shape)), e
 
+    def _width(self, rec):
+        """Slots of the batch, and rows of the ring, a clip of this video takes: 1, but for the views of detect.DetectEngine."""
+        return 1
+
     def _join(self, rec, row0, pos):
-        """A video with rec.rows clips takes the rows ring_place gave it, and its clips join the batches."""
+        """A video with rec.rows ring rows (its clips times _width) takes the rows ring_place gave it, and its clips join the batches.  A clip's
+        _width slots always share a batch: a segment (video, first clip, clips) takes clips * _width consecutive slots."""
         if any(row0 < o.row0 + o.rows and o.row0 < row0 + rec.rows for o in self.live):
             self.flush()                     # rows of a video whose clips still wait for a full batch: run them first (pack=True, a small ring)
         rec.row0, self.pos = row0, pos
         self.live.append(rec)
         self.n_videos += 1
-        self.n_clips += rec.rows
+        clips, w = len(rec.starts), self._width(rec)
+        self.n_clips += clips
         if self.pack:
             first = 0
-            while first < rec.rows:
-                take = min(rec.rows - first, self.bs - self.fill)
+            while first < clips:
+                take = min(clips - first, (self.bs - self.fill) // w)
+                if take == 0:                # (w > 1 only) not one more clip fits: the batch runs short
+                    self._run_batch()
+                    continue
                 self.batch.append((rec, first, take))
-                self.fill += take
+                self.fill += take * w
                 first += take
                 if self.fill == self.bs:
                     self._run_batch()
         else:
-            for i in range(0, rec.rows, self.bs):
-                self.batch.append((rec, i, min(self.bs, rec.rows - i)))
+            for i in range(0, clips, self.bs // w):
+                self.batch.append((rec, i, min(self.bs // w, clips - i)))
                 self._run_batch()
 
     def flush(self):
@@ -219,10 +229,10 @@ class ClipEngine(PlanEngine):
                 main.wait_event(rec.ready)
                 rec.waited = True
             for q in range(0, n, MAX_LAUNCH_CLIPS):
-                self._cut(rec, first + q, min(MAX_LAUNCH_CLIPS, n - q), slot + q)
-            if first + n == rec.rows:
+                self._cut(rec, first + q, min(MAX_LAUNCH_CLIPS, n - q), slot + q, n)
+            if first + n == len(rec.starts):
                 self._release(rec)
-            slot += n
+            slot += n * self._width(rec)
         self.m = slot
         if self.gen_done != self.gen:                                          # first batch of the pass: the weight layouts
             ops.run_ops(c.ops["prep"])
@@ -232,20 +242,24 @@ class ClipEngine(PlanEngine):
         slot = 0
         for rec, first, n in self.batch:
             self._collect(rec, first, n, slot)
-            r = rec.row0 + first
-            self.scores[r:r + n].copy_(self.pred[slot:slot + n])
-            slot += n
+            w = self._width(rec)
+            r = rec.row0 + first * w
+            if w == 1:
+                self.scores[r:r + n].copy_(self.pred[slot:slot + n])
+            else:                                                              # slots view-major, rows clip-major: row0 + clip * w + view
+                self.scores[r:r + n * w].view(n, w, self.C).copy_(self.pred[slot:slot + n * w].view(w, n, self.C).transpose(0, 1))
+            slot += n * w
         if self.on_batch is not None:
             self.on_batch(self.m, *self.outputs())
         for rec, first, n in self.batch:
             rec.done += n
-            if rec.done == rec.rows:                                           # the video's last clip has run
+            if rec.done == len(rec.starts):                                    # the video's last clip has run
                 self._finish(rec)
                 self.live = [o for o in self.live if o is not rec]
         self.batch, self.fill = [], 0
 
     def outputs(self):
-        """(output (m,1,8,H,W) logits, predicted_action (m,C)) of the last batch: views of the plan's arena."""
+        """(output (m,1,8,H,W) logits, predicted_action (m,C)) of the last batch's m slots: views of the plan's arena."""
         return self.out[:self.m * self.per].view(self.m, 1, spec.FRAMES, self.hw, self.hw), self.pred[:self.m]
 
 
@@ -278,7 +292,7 @@ class EvalEngine(ClipEngine):
     def _clear(self):
         self.tables.zero_()
 
-    def _cut(self, rec, first, k, slot):
+    def _cut(self, rec, first, k, slot, seg):
         per = self.per
         ops.eval_clips_from_u8(rec.video, rec.truth, rec.h0, rec.w0, self.hw, rec.starts[first:first + k], self.f_skip,
                                out=(self.img[slot * per * 4:(slot + k) * per * 4], self.gt[slot * per:(slot + k) * per]))

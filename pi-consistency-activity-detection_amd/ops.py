@@ -656,6 +656,75 @@ def detect_frames(logits, starts, F, H, W, h0, w0, f_skip=2, row0=0, mask=None, 
     return mask, rec
 
 
+MAX_VIEWS = 32              # views of one pc_clips_from_u8_views / pc_detect_frames_views launch
+
+
+def _view_table(views, who):
+    """[(h0, w0, flip)] -> (the host table int32 [V][3] the views entries take, V)."""
+    rows = [tuple(int(x) for x in v) for v in views]
+    if not 1 <= len(rows) <= MAX_VIEWS or any(len(r) != 3 for r in rows):
+        raise ValueError("%s: 1..%d views (h0, w0, flip), got %r" % (who, MAX_VIEWS, views))
+    return (C.c_int32 * (3 * len(rows)))(*[x for r in rows for x in r]), len(rows)
+
+
+def clips_from_u8_views(video, views, S, starts, f_skip=2, view_stride=None, out=None):
+    """pc_clips_from_u8_views: clips_from_u8 for every view (h0, w0, flip) of the n <= 32 clips in one launch.  View v of clip c is written at
+    clip slot v * view_stride + c (view_stride >= n, default n).  -> data [V, view_stride, 8, S, S, 4] float32, or `out` (a contiguous float32
+    device tensor with room for (V - 1) * view_stride + n clips) as it was given; the slots between the views are not written."""
+    if video.dtype != torch.uint8 or video.dim() != 4 or video.shape[3] != 3 or not video.is_contiguous():
+        raise ValueError("clips_from_u8_views: contiguous uint8 [F,H,W,3] frames")
+    F, H, W = (int(v) for v in video.shape[:3])
+    tab, V = _view_table(views, "clips_from_u8_views")
+    n = len(starts)
+    stride = n if view_stride is None else int(view_stride)
+    if stride < n:
+        raise ValueError("clips_from_u8_views: view_stride = %d below the %d clips" % (stride, n))
+    if out is None:
+        out = torch.empty(V, stride, 8, S, S, 4, device=video.device)
+    elif out.dtype != torch.float32 or not out.is_contiguous() or out.numel() < ((V - 1) * stride + n) * 32 * S * S or out.device != video.device:
+        raise ValueError("clips_from_u8_views: out must be a contiguous float32 device tensor of at least ((V-1)*view_stride+n)*8*S*S*4 elements")
+    st = (C.c_int32 * max(n, 1))(*[int(v) for v in starts])
+    capi.call("pc_clips_from_u8_views", ptr(video), F, H, W, int(S), tab, V, stride, st, n, int(f_skip), ptr(out), stream())
+    return out
+
+
+def detect_frames_views_ws_bytes(n, H, W):
+    return int(capi.lib().pc_detect_frames_views_ws_bytes(int(n), int(H), int(W)))
+
+
+def detect_frames_views(logits, views, starts, F, H, W, f_skip=2, view_stride=None, row0=0, mask=None, rec=None, ws=None, want_mask=True):
+    """pc_detect_frames_views: detect_frames with the views (h0, w0, flip) of every clip merged per full-frame pixel.  logits contiguous float32
+    device (S from the last dim), view v of clip c at clip slot v * view_stride + c (default stride: n = len(starts)).
+    -> (mask uint8 [F,H,W] or None, rec int32 [F,8]) as detect_frames; rec[:, 6] = row0 + c * V."""
+    if logits.dtype != torch.float32 or not logits.is_contiguous():
+        raise ValueError("detect_frames_views: contiguous float32 logits")
+    tab, V = _view_table(views, "detect_frames_views")
+    S, n = int(logits.shape[-1]), len(starts)
+    stride = n if view_stride is None else int(view_stride)
+    if stride < n:
+        raise ValueError("detect_frames_views: view_stride = %d below the %d clips" % (stride, n))
+    if int(logits.shape[-2]) != S or logits.numel() < ((V - 1) * stride + n) * 8 * S * S:
+        raise ValueError("detect_frames_views: logits %s do not hold %d views of %d clips of 8 x %d x %d at stride %d" % (tuple(logits.shape), V, n, S, S, stride))
+    dev = logits.device
+    if mask is None and want_mask:
+        mask = torch.zeros(F, H, W, dtype=torch.uint8, device=dev)
+    if mask is not None and (mask.dtype != torch.uint8 or not mask.is_contiguous() or mask.numel() != F * H * W or mask.device != dev):
+        raise ValueError("detect_frames_views: mask must be a contiguous uint8 device tensor [F,H,W]")
+    if rec is None:
+        rec = torch.zeros(F, DETECT_REC_WORDS, dtype=torch.int32, device=dev)
+    elif rec.dtype != torch.int32 or not rec.is_contiguous() or rec.numel() != F * DETECT_REC_WORDS or rec.device != dev:
+        raise ValueError("detect_frames_views: rec must be a contiguous int32 device tensor [F,8]")
+    need = detect_frames_views_ws_bytes(n, H, W)
+    if ws is None and need > 0:
+        ws = torch.empty(need, dtype=torch.uint8, device=dev)
+    elif ws is not None and (not ws.is_contiguous() or ws.numel() * ws.element_size() < need or ws.device != dev):
+        raise ValueError("detect_frames_views: ws must hold detect_frames_views_ws_bytes(n, H, W) = %d bytes" % need)
+    st = (C.c_int32 * max(n, 1))(*[int(v) for v in starts])
+    capi.call("pc_detect_frames_views", ptr(logits), int(F), int(H), int(W), S, tab, V, stride, st, n, int(f_skip), int(row0), ptr(mask), ptr(rec),
+              ptr(ws), stream())
+    return mask, rec
+
+
 def decode_detect_records(rec):
     """Host int32 [F,8] records (numpy or torch) -> (counts int32 [F], boxes int32 [F,4] = x0, y0, x1, y1, frame_scores float32 [F], rows int32 [F])."""
     r = np.ascontiguousarray(rec.cpu().numpy() if torch.is_tensor(rec) else rec, dtype=np.int32).reshape(-1, DETECT_REC_WORDS)

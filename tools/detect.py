@@ -5,9 +5,12 @@ Weights: a checkpoint in the reference's key layout (--ckpt, a torch.save'd stat
 of uint8 frames [F,H,W,3] with frames at least hw x hw (ops.resize_u8 scales decoded frames on the device), or --synthetic N videos of
 synthetic.make_eval_videos_u8.  One pass; one .npz with, per video i: label_i, class_scores_i [C], counts_i [F], boxes_i [F,4] (x0, y0, x1, y1,
 half-open, full-frame coordinates), frame_scores_i [F], tubes_i [T,3] = (t0, t1 inclusive, score), and with --masks masks_i = np.packbits of
-the uint8 masks [F,H,W] (mask_shape_i to unpack them).
+the uint8 masks [F,H,W] (mask_shape_i to unpack them).  --tile: the whole frame instead of its centre crop, as overlapping hw x hw tiles
+whose logits are averaged per pixel; --flip: every crop also mirrored left-right, the two maps averaged (bs should be a multiple of the views
+per clip, e.g. --bs 16 for the 8 views of a 240 x 320 frame with both).  tile, flip and views_i [V,3] = (h0, w0, flip) are recorded.
 
-    python tools/detect.py --out detections.npz [--ckpt best_model.pth] [--synthetic 4 | video.npy ...] [--masks] [--pack] [--max-gap 0] [--min-pixels 1]
+    python tools/detect.py --out detections.npz [--ckpt best_model.pth] [--synthetic 4 | video.npy ...] [--masks] [--pack] [--tile] [--flip]
+                           [--max-gap 0] [--min-pixels 1]
 """
 import argparse
 import os
@@ -32,6 +35,8 @@ def main():
     ap.add_argument("--bs", type=int, default=14)
     ap.add_argument("--masks", action="store_true")
     ap.add_argument("--pack", action="store_true")
+    ap.add_argument("--tile", action="store_true", help="cover the whole frame with hw x hw tiles (detect.make_views)")
+    ap.add_argument("--flip", action="store_true", help="every crop also mirrored left-right")
     ap.add_argument("--min-pixels", type=int, default=1)
     ap.add_argument("--max-gap", type=int, default=0)
     a = ap.parse_args()
@@ -50,15 +55,15 @@ def main():
         n = a.synthetic or 4
         videos = [v[0] for v in synthetic.make_eval_videos_u8(n, num_classes=a.classes, hw=a.hw)]
         names = ["synthetic_%d" % i for i in range(n)]
-    engine = detect.DetectEngine(bs=a.bs, hw=a.hw, num_classes=a.classes, state=state, pack=a.pack, masks=a.masks)
+    engine = detect.DetectEngine(bs=a.bs, hw=a.hw, num_classes=a.classes, state=state, pack=a.pack, masks=a.masks, tile=a.tile, flip=a.flip)
     engine.begin()
     for v in videos:
         engine.add_video(v)
-    out = {"names": np.array(names)}
+    out = {"names": np.array(names), "tile": np.bool_(a.tile), "flip": np.bool_(a.flip)}
     for i, (name, d) in enumerate(zip(names, engine.results())):
         tubes = d.tubes(a.min_pixels, a.max_gap)
         out.update({"label_%d" % i: np.int32(d.label), "class_scores_%d" % i: d.class_scores, "counts_%d" % i: d.counts, "boxes_%d" % i: d.boxes,
-                    "frame_scores_%d" % i: d.frame_scores,
+                    "frame_scores_%d" % i: d.frame_scores, "views_%d" % i: np.array(d.views, np.int32).reshape(-1, 3),
                     "tubes_%d" % i: np.array([(t0, t1, s) for t0, t1, _b, s in tubes], np.float64).reshape(-1, 3)})
         if a.masks:
             m = d.masks.cpu().numpy()
