@@ -6,13 +6,13 @@
 //                          pc_seg_frame_counts takes; HBM-bound, 4 bytes read and 20 written per pixel
 //   pc_clips_from_u8       the same kernel without the truth side (unlabelled video: picons_amd/detect.py)
 //   pc_clips_from_u8_views pc_clips_from_u8 for V views (crops at their own offsets, some mirrored left-right) of the clips in one launch
+//                          all three are clips_from_u8_kernel<TRUTH> on the geometry of clipgeom.h: a centre crop is one view at stride n
 //   pc_video_vote          argmax(mean(predictions, axis=0)) == label, rows added in order in fp32 as numpy adds them
 #include "common.h"
 #include "evalpred.h"
+#include "clipgeom.h"
 
 namespace {
-
-constexpr int MAX_CLIPS = 32;
 
 __global__ __launch_bounds__(256) void truth_frame_flags_kernel(const uint8_t* __restrict__ truth, int H, int W, int h0, int w0, int S,
                                                                 int32_t* __restrict__ flags) {
@@ -31,42 +31,58 @@ __global__ __launch_bounds__(256) void truth_frame_flags_kernel(const uint8_t* _
     if (threadIdx.x == 0) flags[blockIdx.x] = part[0] + part[1] + part[2] + part[3];
 }
 
-struct EvalClipsK {
+struct ClipCutK {
     const uint8_t* video; const uint8_t* truth;
-    int F, H, W, h0, w0, S, f_skip;
-    int starts[MAX_CLIPS];
     float4* data; float* gt;
+    ClipGeom g;
 };
 
-// blockIdx.y = clip * 8 + frame of the clip, blockIdx.x strides over the frame's S*S pixels: one thread per pixel writes one whole float4
-// (a wave: 1 KiB contiguous) and one truth float (256 B contiguous).  The source bytes of a cropped RGB row start at any byte address, so
-// they are read as bytes; consecutive lanes read consecutive 3-byte pixels of one row.
-// TRUTH = false (pc_clips_from_u8): the same body without the truth side; p.truth and p.gt are never touched.
+// One frame of one view: FLIP reads the row backwards.  A template, and one branch per block, so that the unmirrored loop -- all there is to
+// the centre entries -- carries nothing of the mirror.  Selecting the column per pixel, and the view as blockIdx.y / (n * 8), put the centre
+// entries 2 - 3 % above the parent's kernel time (docs/MEASUREMENTS.md, "One clip cut": builds, shapes and every figure).
+template <bool TRUTH, bool FLIP>
+__device__ __forceinline__ void cut_frame(const float* lut, const uint8_t* vf, const uint8_t* tf, int S, int W, float4* data, float* gt) {
+    const int total = S * S;
+    for (int idx = blockIdx.x * 256 + threadIdx.x; idx < total; idx += gridDim.x * 256) {
+        const int y = idx / S, x = idx - y * S;
+        const size_t src = (size_t)y * W + (FLIP ? S - 1 - x : x);
+        const uint8_t* px = vf + src * 3;
+        data[idx] = make_float4(lut[px[0]], lut[px[1]], lut[px[2]], 0.f);
+        if (TRUTH) gt[idx] = (float)tf[src];                         // the value itself: the reference counts pred + gt == 2
+    }
+}
+
+// blockIdx.z = view, blockIdx.y = clip * 8 + frame of the clip, written at clip slot view * view_stride + clip; blockIdx.x strides over the frame's
+// S*S pixels: one thread per pixel writes one whole float4 (a wave: 1 KiB contiguous) and one truth float (256 B contiguous).  The source
+// bytes of a cropped RGB row start at any byte address, so they are read as bytes; consecutive lanes read consecutive 3-byte pixels of one
+// row, descending ones for a mirrored view, which reads its row backwards.
+// TRUTH = false (pc_clips_from_u8, pc_clips_from_u8_views): the same body without the truth side; p.truth and p.gt are never touched.
 template <bool TRUTH>
-__global__ __launch_bounds__(256) void eval_clips_from_u8_kernel(const EvalClipsK p) {
+__global__ __launch_bounds__(256) void clips_from_u8_kernel(const ClipCutK p) {
     __shared__ float lut[256];
+    const ClipGeom& g = p.g;
+    const int v = blockIdx.z, c = blockIdx.y >> 3, k = blockIdx.y & 7;
+    const int64_t f = (int64_t)g.starts[c] + (int64_t)k * g.f_skip;
+    const int vh0 = g.vh0[v], vw0 = g.vw0[v];                        // the block's table entries: asked for in front of the division below
+    const bool flip = (g.flips >> v) & 1u;
     lut[threadIdx.x] = (float)((double)threadIdx.x / 255.0);        // img / 255. in float64, then the float32 cast: once per block
     __syncthreads();
-    const int c = blockIdx.y >> 3, k = blockIdx.y & 7;
-    const int64_t f = (int64_t)p.starts[c] + (int64_t)k * p.f_skip;
-    const int total = p.S * p.S;
-    float4* data = p.data + (size_t)blockIdx.y * total;
-    float* gt = TRUTH ? p.gt + (size_t)blockIdx.y * total : nullptr;
-    if (f >= p.F) {                                                  // a frame past the end: zeros, nothing read (evaluate_ucf101.py:89-91)
+    const int S = g.S, total = S * S;
+    const size_t at = (((size_t)v * g.view_stride + c) * 8 + k) * total;
+    float4* data = p.data + at;
+    float* gt = TRUTH ? p.gt + at : nullptr;
+    if (f >= g.F) {                                                  // a frame past the end: zeros, nothing read (evaluate_ucf101.py:89-91)
         for (int idx = blockIdx.x * 256 + threadIdx.x; idx < total; idx += gridDim.x * 256) {
             data[idx] = make_float4(0.f, 0.f, 0.f, 0.f);
             if (TRUTH) gt[idx] = 0.f;
         }
         return;
     }
-    const uint8_t* vf = p.video + (((size_t)f * p.H + p.h0) * p.W + p.w0) * 3;
-    const uint8_t* tf = TRUTH ? p.truth + ((size_t)f * p.H + p.h0) * p.W + p.w0 : nullptr;
-    for (int idx = blockIdx.x * 256 + threadIdx.x; idx < total; idx += gridDim.x * 256) {
-        const int y = idx / p.S, x = idx - y * p.S;
-        const uint8_t* px = vf + ((size_t)y * p.W + x) * 3;
-        data[idx] = make_float4(lut[px[0]], lut[px[1]], lut[px[2]], 0.f);
-        if (TRUTH) gt[idx] = (float)tf[(size_t)y * p.W + x];         // the value itself: the reference counts pred + gt == 2
-    }
+    const size_t corner = ((size_t)f * g.H + vh0) * g.W + vw0;
+    const uint8_t* vf = p.video + corner * 3;
+    const uint8_t* tf = TRUTH ? p.truth + corner : nullptr;
+    if (flip) cut_frame<TRUTH, true>(lut, vf, tf, S, g.W, data, gt);
+    else cut_frame<TRUTH, false>(lut, vf, tf, S, g.W, data, gt);
 }
 
 __global__ __launch_bounds__(256) void video_vote_kernel(const float* __restrict__ pred, int n, int C, int label, int32_t* n_correct) {
@@ -88,38 +104,43 @@ extern "C" int pc_truth_frame_flags(const uint8_t* truth, int F, int H, int W, i
     return PC_OK;
 }
 
-// The checks and the launch pc_eval_clips_from_u8 (TRUTH) and pc_clips_from_u8 share; `who` names the entry in the messages.
+// The checks and the launch of the three cut entries; `who` names the entry in the messages.  crop: the (h0, w0) of a centre-crop entry, which
+// is the one view (h0, w0, 0) at stride n, or null for the entry that takes a view table.
 template <bool TRUTH>
-static int clips_from_u8(const char* who, const uint8_t* video, const uint8_t* truth, int F, int H, int W, int h0, int w0, int S,
-                         const int32_t* starts, int n, int f_skip, float* data, float* gt, pc_stream s) {
-    PC_CHECK_ARG(video && starts && data && (!TRUTH || (truth && gt)), "%s: null pointer", who);
-    PC_CHECK_ARG(F >= 1 && H >= 1 && W >= 1 && S >= 1 && S <= 32768 && h0 >= 0 && w0 >= 0 && (int64_t)h0 + S <= H && (int64_t)w0 + S <= W,
-                 "%s: %d frames, crop %d+%d x %d+%d outside %d x %d", who, F, h0, S, w0, S, H, W);
-    PC_CHECK_ARG(n >= 1 && n <= MAX_CLIPS, "%s: n = %d clips outside 1..%d", who, n, MAX_CLIPS);
-    PC_CHECK_ARG(f_skip >= 1, "%s: f_skip = %d", who, f_skip);
-    PC_CHECK_ARG(((uintptr_t)data % 16 == 0) && (!TRUTH || (uintptr_t)gt % 16 == 0), "%s: data / gt must be 16-byte aligned", who);
-    EvalClipsK k;
-    k.video = video; k.truth = truth; k.F = F; k.H = H; k.W = W; k.h0 = h0; k.w0 = w0; k.S = S; k.f_skip = f_skip;
-    k.data = (float4*)data; k.gt = gt;
-    for (int c = 0; c < MAX_CLIPS; ++c) {
-        if (c < n) PC_CHECK_ARG(starts[c] >= 0, "%s: start %d of clip %d is negative", who, starts[c], c);
-        k.starts[c] = c < n ? starts[c] : 0;
-    }
+static int clips_from_u8(const char* who, const uint8_t* video, const uint8_t* truth, int F, int H, int W, int S, const int32_t* crop,
+                         const int32_t* views, int V, int view_stride, const int32_t* starts, int n, int f_skip, float* data, float* gt,
+                         pc_stream s) {
+    ClipCutK k;
+    PC_CHECK_ARG(video && views && starts && data && (!TRUTH || (truth && gt)), "%s: null pointer", who);
+    if (int rc = geom_shape(k.g, who, F, H, W, S, crop)) return rc;
+    if (int rc = geom_counts(k.g, who, V, n, view_stride, f_skip)) return rc;
+    PC_CHECK_ARG(((uintptr_t)data % 16 == 0) && (!TRUTH || (uintptr_t)gt % 16 == 0), "%s: %s must be 16-byte aligned", who, crop ? "data / gt" : "data");
+    if (int rc = geom_views(k.g, who, views)) return rc;
+    if (int rc = geom_starts(k.g, who, starts)) return rc;
+    k.video = video; k.truth = truth; k.data = (float4*)data; k.gt = gt;
     int gx = cdiv((int64_t)S * S, 1024);                             // ~4 pixels per thread
     if (gx > 1024) gx = 1024;
-    hipLaunchKernelGGL(eval_clips_from_u8_kernel<TRUTH>, dim3((unsigned)gx, (unsigned)(n * 8)), dim3(256), 0, (hipStream_t)s, k);
+    hipLaunchKernelGGL(clips_from_u8_kernel<TRUTH>, dim3((unsigned)gx, (unsigned)(n * 8), (unsigned)V), dim3(256), 0, (hipStream_t)s, k);
     PC_CHECK_LAUNCH(who);
     return PC_OK;
 }
 
 extern "C" int pc_eval_clips_from_u8(const uint8_t* video, const uint8_t* truth, int F, int H, int W, int h0, int w0, int S,
                                      const int32_t* starts, int n, int f_skip, float* data, float* gt, pc_stream s) {
-    return clips_from_u8<true>("pc_eval_clips_from_u8", video, truth, F, H, W, h0, w0, S, starts, n, f_skip, data, gt, s);
+    const int32_t view[3] = {h0, w0, 0};
+    return clips_from_u8<true>("pc_eval_clips_from_u8", video, truth, F, H, W, S, view, view, 1, n, starts, n, f_skip, data, gt, s);
 }
 
 extern "C" int pc_clips_from_u8(const uint8_t* video, int F, int H, int W, int h0, int w0, int S, const int32_t* starts, int n, int f_skip,
                                 float* data, pc_stream s) {
-    return clips_from_u8<false>("pc_clips_from_u8", video, nullptr, F, H, W, h0, w0, S, starts, n, f_skip, data, nullptr, s);
+    const int32_t view[3] = {h0, w0, 0};
+    return clips_from_u8<false>("pc_clips_from_u8", video, nullptr, F, H, W, S, view, view, 1, n, starts, n, f_skip, data, nullptr, s);
+}
+
+extern "C" int pc_clips_from_u8_views(const uint8_t* video, int F, int H, int W, int S, const int32_t* views, int V, int view_stride,
+                                      const int32_t* starts, int n, int f_skip, float* data, pc_stream s) {
+    return clips_from_u8<false>("pc_clips_from_u8_views", video, nullptr, F, H, W, S, nullptr, views, V, view_stride, starts, n, f_skip, data,
+                                nullptr, s);
 }
 
 extern "C" int pc_video_vote(const float* pred, int n, int C, int label, int32_t* n_correct, pc_stream s) {
@@ -128,79 +149,5 @@ extern "C" int pc_video_vote(const float* pred, int n, int C, int label, int32_t
     PC_CHECK_ARG(label >= 0 && label < C, "pc_video_vote: label %d outside [0, %d)", label, C);
     hipLaunchKernelGGL(video_vote_kernel, dim3(1), dim3(256), 0, (hipStream_t)s, pred, n, C, label, n_correct);
     PC_CHECK_LAUNCH("video_vote");
-    return PC_OK;
-}
-
-// ---------------------------------------------------------------------- views (detect.DetectEngine, tile / flip)
-namespace {
-
-constexpr int MAX_VIEWS = 32;
-
-struct ClipViewsK {
-    const uint8_t* video;
-    int F, H, W, S, f_skip, n, view_stride;
-    int starts[MAX_CLIPS];
-    int vh0[MAX_VIEWS], vw0[MAX_VIEWS];
-    uint32_t flips;                                                  // bit v: view v is mirrored left-right
-    float4* data;
-};
-
-// pc_clips_from_u8 for V views (crops at their own offsets, some mirrored) of the n clips in one launch: blockIdx.y = (view * n + clip) * 8 +
-// frame of the clip, written at clip slot view * view_stride + clip; blockIdx.x strides over the S*S pixels, one whole float4 per thread as
-// in eval_clips_from_u8_kernel.  A mirrored view reads its row backwards: consecutive lanes, descending 3-byte pixels of one row.
-__global__ __launch_bounds__(256) void clips_from_u8_views_kernel(const ClipViewsK p) {
-    __shared__ float lut[256];
-    lut[threadIdx.x] = (float)((double)threadIdx.x / 255.0);        // the table of eval_clips_from_u8_kernel
-    __syncthreads();
-    const int v = blockIdx.y / (p.n * 8), ck = blockIdx.y - v * (p.n * 8);
-    const int c = ck >> 3, k = ck & 7;
-    const int64_t f = (int64_t)p.starts[c] + (int64_t)k * p.f_skip;
-    const int S = p.S, total = S * S;
-    float4* data = p.data + (((size_t)v * p.view_stride + c) * 8 + k) * total;
-    if (f >= p.F) {                                                  // a frame past the end: zeros, nothing read
-        for (int idx = blockIdx.x * 256 + threadIdx.x; idx < total; idx += gridDim.x * 256) data[idx] = make_float4(0.f, 0.f, 0.f, 0.f);
-        return;
-    }
-    const bool flip = (p.flips >> v) & 1u;
-    const uint8_t* vf = p.video + (((size_t)f * p.H + p.vh0[v]) * p.W + p.vw0[v]) * 3;
-    for (int idx = blockIdx.x * 256 + threadIdx.x; idx < total; idx += gridDim.x * 256) {
-        const int y = idx / S, x = idx - y * S;
-        const uint8_t* px = vf + ((size_t)y * p.W + (flip ? S - 1 - x : x)) * 3;
-        data[idx] = make_float4(lut[px[0]], lut[px[1]], lut[px[2]], 0.f);
-    }
-}
-
-}  // namespace
-
-extern "C" int pc_clips_from_u8_views(const uint8_t* video, int F, int H, int W, int S, const int32_t* views, int V, int view_stride,
-                                      const int32_t* starts, int n, int f_skip, float* data, pc_stream s) {
-    const char* who = "pc_clips_from_u8_views";
-    PC_CHECK_ARG(video && views && starts && data, "%s: null pointer", who);
-    PC_CHECK_ARG(F >= 1 && H >= 1 && W >= 1 && S >= 1 && S <= 32768 && S <= H && S <= W, "%s: %d frames, crop of %d outside %d x %d", who, F, S, H, W);
-    PC_CHECK_ARG(V >= 1 && V <= MAX_VIEWS, "%s: V = %d views outside 1..%d", who, V, MAX_VIEWS);
-    PC_CHECK_ARG(n >= 1 && n <= MAX_CLIPS, "%s: n = %d clips outside 1..%d", who, n, MAX_CLIPS);
-    PC_CHECK_ARG(view_stride >= n, "%s: view_stride = %d is below the n = %d clips of a view", who, view_stride, n);
-    PC_CHECK_ARG(f_skip >= 1, "%s: f_skip = %d", who, f_skip);
-    PC_CHECK_ARG((uintptr_t)data % 16 == 0, "%s: data must be 16-byte aligned", who);
-    ClipViewsK k;
-    k.video = video; k.F = F; k.H = H; k.W = W; k.S = S; k.f_skip = f_skip; k.n = n; k.view_stride = view_stride; k.flips = 0;
-    k.data = (float4*)data;
-    for (int v = 0; v < MAX_VIEWS; ++v) {
-        k.vh0[v] = k.vw0[v] = 0;
-        if (v >= V) continue;
-        const int h0 = views[3 * v], w0 = views[3 * v + 1], fl = views[3 * v + 2];
-        PC_CHECK_ARG(h0 >= 0 && w0 >= 0 && (int64_t)h0 + S <= H && (int64_t)w0 + S <= W, "%s: view %d, crop %d+%d x %d+%d outside %d x %d", who, v,
-                     h0, S, w0, S, H, W);
-        PC_CHECK_ARG(fl == 0 || fl == 1, "%s: view %d, flip = %d is neither 0 nor 1", who, v, fl);
-        k.vh0[v] = h0; k.vw0[v] = w0; k.flips |= (uint32_t)fl << v;
-    }
-    for (int c = 0; c < MAX_CLIPS; ++c) {
-        if (c < n) PC_CHECK_ARG(starts[c] >= 0, "%s: start %d of clip %d is negative", who, starts[c], c);
-        k.starts[c] = c < n ? starts[c] : 0;
-    }
-    int gx = cdiv((int64_t)S * S, 1024);                             // ~4 pixels per thread
-    if (gx > 1024) gx = 1024;
-    hipLaunchKernelGGL(clips_from_u8_views_kernel, dim3((unsigned)gx, (unsigned)(V * n * 8)), dim3(256), 0, (hipStream_t)s, k);
-    PC_CHECK_LAUNCH(who);
     return PC_OK;
 }

@@ -1,5 +1,5 @@
 """Detection output on one MI355X: where the action is in a video and which action it is, from DECODED uint8 video without truth.  The
-inference side of evalstep.EvalEngine -- the same upload pool, clip kernel (pc_clips_from_u8: the truth side compiled out), single eval plan
+inference side of evalstep.EvalEngine -- the same upload pool, clip kernel (pc_clips_from_u8_views: the truth side compiled out), single eval plan
 whose weight layouts are made once per pass, and class-score ring -- ending not in hit tables but in detections: behind each batch one
 pc_detect_frames per video segment undoes the clip interleave (frame k of a clip is start + k * f_skip) straight into the video's uint8 masks
 in frame order and full-frame coordinates and leaves one record per frame (pixel count, box, score); behind a video's last clip
@@ -108,7 +108,7 @@ class DetectEngine(ClipEngine):
     every video.  With any of the three the engine runs V views per clip: all V share a batch, so a batch holds bs // V clips -- bs should be
     a multiple of V, bs < V is refused -- and a video takes clips * V rows of the score ring, row0 + clip * V + view, over all of which its
     class is voted.  A segment of n clips lies view-major in the batch (view v of its clip c at slot v * n + c of the segment's n * V slots:
-    the order on_batch / outputs() show).  Without them: the centre crop, pc_clips_from_u8 and pc_detect_frames, as before."""
+    the order on_batch / outputs() show).  Without them: the centre crop, cut as the one view (h0, w0, 0), and pc_detect_frames."""
 
     def __init__(self, bs=14, hw=224, num_classes=24, device="cuda:0", state=None, engine=None, capacity=256, seed=47, f_skip=2, pack=False,
                  masks=True, on_batch=None, tile=False, flip=False, views=None):
@@ -198,12 +198,10 @@ class DetectEngine(ClipEngine):
         return len(self.videos) - 1
 
     def _cut(self, rec, first, k, slot, seg):
-        per = self.per
-        if rec.views:                        # view v of the segment's clip c at slot v * seg + c: this launch's clips start at `slot`
-            ops.clips_from_u8_views(rec.video, rec.views, self.hw, rec.starts[first:first + k], self.f_skip, view_stride=seg,
-                                    out=self.img[slot * per * 4:(slot + (len(rec.views) - 1) * seg + k) * per * 4])
-            return
-        ops.clips_from_u8(rec.video, rec.h0, rec.w0, self.hw, rec.starts[first:first + k], self.f_skip, out=self.img[slot * per * 4:(slot + k) * per * 4])
+        # view v of the segment's clip c at slot v * seg + c: this launch's clips start at `slot`.  The centre crop is the one view at stride seg.
+        per, views = self.per, rec.views or [(rec.h0, rec.w0, 0)]
+        ops.clips_from_u8_views(rec.video, views, self.hw, rec.starts[first:first + k], self.f_skip, view_stride=seg,
+                                out=self.img[slot * per * 4:(slot + (len(views) - 1) * seg + k) * per * 4])
 
     def _collect(self, rec, first, n, slot):
         per, hw, W8 = self.per, self.hw, ops.DETECT_REC_WORDS

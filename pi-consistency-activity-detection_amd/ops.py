@@ -555,12 +555,20 @@ def clip_from_u8_masks(video, span, h0, w0, maskframes, valid, S=224):
     return data, aug, mask, mask_cls
 
 
-def _u8_video(video, truth, who):
+def _u8_video(video, who, truth=None):
+    """The video check of the clip-cut wrappers (and the truth's, where one comes with it) -> F, H, W."""
     if video.dtype != torch.uint8 or video.dim() != 4 or video.shape[3] != 3 or not video.is_contiguous():
         raise ValueError("%s: contiguous uint8 [F,H,W,3] frames" % who)
-    if truth.dtype != torch.uint8 or not truth.is_contiguous() or truth.numel() != video.numel() // 3 or tuple(truth.shape[:3]) != tuple(video.shape[:3]):
+    if truth is not None and (truth.dtype != torch.uint8 or not truth.is_contiguous() or truth.numel() != video.numel() // 3
+                              or tuple(truth.shape[:3]) != tuple(video.shape[:3])):
         raise ValueError("%s: truth must be contiguous uint8 [F,H,W] of the video's size" % who)
     return (int(v) for v in video.shape[:3])
+
+
+def _starts_table(starts):
+    """First-frame indices (host) -> (the int32 table the clip entries take, n)."""
+    n = len(starts)
+    return (C.c_int32 * max(n, 1))(*[int(v) for v in starts]), n
 
 
 def truth_frame_flags(truth, h0, w0, S, flags=None):
@@ -581,8 +589,8 @@ def eval_clips_from_u8(video, truth, h0, w0, S, starts, f_skip=2, out=None):
     """pc_eval_clips_from_u8: video uint8 device [F,H,W,3], truth uint8 device [F,H,W]; starts: 1..32 first-frame indices (host).
     -> data [n,8,S,S,4] float32 (r, g, b, 0), gt [n,8,S,S] float32 (the truth values; zero frames past the end).  out: (data, gt) contiguous
     float32 device tensors with room for n clips -- a batch's place in the plan's clip tensor -- instead of fresh ones."""
-    F, H, W = _u8_video(video, truth, "eval_clips_from_u8")
-    n = len(starts)
+    F, H, W = _u8_video(video, "eval_clips_from_u8", truth)
+    st, n = _starts_table(starts)
     if out is None:
         data = torch.empty(n, 8, S, S, 4, device=video.device); gt = torch.empty(n, 8, S, S, device=video.device)
     else:
@@ -590,7 +598,6 @@ def eval_clips_from_u8(video, truth, h0, w0, S, starts, f_skip=2, out=None):
         for t, n_ in ((data, 32 * S * S), (gt, 8 * S * S)):
             if t.dtype != torch.float32 or not t.is_contiguous() or t.numel() < n * n_ or t.device != video.device:
                 raise ValueError("eval_clips_from_u8: out tensors must be contiguous float32 device tensors of at least n*8*S*S*4 / n*8*S*S elements")
-    st = (C.c_int32 * max(n, 1))(*[int(v) for v in starts])
     capi.call("pc_eval_clips_from_u8", ptr(video), ptr(truth), F, H, W, int(h0), int(w0), int(S), st, n, int(f_skip), ptr(data), ptr(gt), stream())
     return data, gt
 
@@ -607,15 +614,12 @@ def video_vote(pred, label, n_correct):
 def clips_from_u8(video, h0, w0, S, starts, f_skip=2, out=None):
     """pc_clips_from_u8: eval_clips_from_u8 without truth.  video uint8 device [F,H,W,3]; starts: 1..32 first-frame indices (host).
     -> data [n,8,S,S,4] float32 (r, g, b, 0).  out: a contiguous float32 device tensor with room for n clips to write into."""
-    if video.dtype != torch.uint8 or video.dim() != 4 or video.shape[3] != 3 or not video.is_contiguous():
-        raise ValueError("clips_from_u8: contiguous uint8 [F,H,W,3] frames")
-    F, H, W = (int(v) for v in video.shape[:3])
-    n = len(starts)
+    F, H, W = _u8_video(video, "clips_from_u8")
+    st, n = _starts_table(starts)
     if out is None:
         out = torch.empty(n, 8, S, S, 4, device=video.device)
     elif out.dtype != torch.float32 or not out.is_contiguous() or out.numel() < n * 32 * S * S or out.device != video.device:
         raise ValueError("clips_from_u8: out must be a contiguous float32 device tensor of at least n*8*S*S*4 elements")
-    st = (C.c_int32 * max(n, 1))(*[int(v) for v in starts])
     capi.call("pc_clips_from_u8", ptr(video), F, H, W, int(h0), int(w0), int(S), st, n, int(f_skip), ptr(out), stream())
     return out
 
@@ -627,36 +631,42 @@ def detect_frames_ws_bytes(n, S):
     return int(capi.lib().pc_detect_frames_ws_bytes(int(n), int(S)))
 
 
+def _detect_buffers(who, dev, F, H, W, mask, rec, ws, want_mask, ws_call, need):
+    """The mask / rec / ws of detect_frames and detect_frames_views: given ones checked, missing ones made (mask and rec zero-filled; no mask
+    with want_mask=False).  ws_call names the size function in the message; need: its value.  -> mask, rec, ws."""
+    if mask is None and want_mask:
+        mask = torch.zeros(F, H, W, dtype=torch.uint8, device=dev)
+    if mask is not None and (mask.dtype != torch.uint8 or not mask.is_contiguous() or mask.numel() != F * H * W or mask.device != dev):
+        raise ValueError("%s: mask must be a contiguous uint8 device tensor [F,H,W]" % who)
+    if rec is None:
+        rec = torch.zeros(F, DETECT_REC_WORDS, dtype=torch.int32, device=dev)
+    elif rec.dtype != torch.int32 or not rec.is_contiguous() or rec.numel() != F * DETECT_REC_WORDS or rec.device != dev:
+        raise ValueError("%s: rec must be a contiguous int32 device tensor [F,8]" % who)
+    if ws is None and need > 0:
+        ws = torch.empty(need, dtype=torch.uint8, device=dev)
+    elif ws is not None and (not ws.is_contiguous() or ws.numel() * ws.element_size() < need or ws.device != dev):
+        raise ValueError("%s: ws must hold %s = %d bytes" % (who, ws_call, need))
+    return mask, rec, ws
+
+
 def detect_frames(logits, starts, F, H, W, h0, w0, f_skip=2, row0=0, mask=None, rec=None, ws=None, want_mask=True):
     """pc_detect_frames: logits contiguous float32 device [n,8,S,S] (any shape with those elements; S from the last dim), the eval forward's
     output for the n <= 32 clips of one video cut at `starts`.  -> (mask uint8 [F,H,W] or None, rec int32 [F,8]); given tensors are written
     in place -- only the frames the clips address -- fresh ones are zero-filled first.  want_mask=False with mask=None: records only."""
     if logits.dtype != torch.float32 or not logits.is_contiguous():
         raise ValueError("detect_frames: contiguous float32 logits")
-    S, n = int(logits.shape[-1]), len(starts)
+    st, n = _starts_table(starts)
+    S = int(logits.shape[-1])
     if int(logits.shape[-2]) != S or logits.numel() < n * 8 * S * S:
         raise ValueError("detect_frames: logits %s do not hold %d clips of 8 x %d x %d" % (tuple(logits.shape), n, S, S))
-    dev = logits.device
-    if mask is None and want_mask:
-        mask = torch.zeros(F, H, W, dtype=torch.uint8, device=dev)
-    if mask is not None and (mask.dtype != torch.uint8 or not mask.is_contiguous() or mask.numel() != F * H * W or mask.device != dev):
-        raise ValueError("detect_frames: mask must be a contiguous uint8 device tensor [F,H,W]")
-    if rec is None:
-        rec = torch.zeros(F, DETECT_REC_WORDS, dtype=torch.int32, device=dev)
-    elif rec.dtype != torch.int32 or not rec.is_contiguous() or rec.numel() != F * DETECT_REC_WORDS or rec.device != dev:
-        raise ValueError("detect_frames: rec must be a contiguous int32 device tensor [F,8]")
-    need = detect_frames_ws_bytes(n, S)
-    if ws is None and need > 0:
-        ws = torch.empty(need, dtype=torch.uint8, device=dev)
-    elif ws is not None and (not ws.is_contiguous() or ws.numel() * ws.element_size() < need or ws.device != dev):
-        raise ValueError("detect_frames: ws must hold detect_frames_ws_bytes(n, S) = %d bytes" % need)
-    st = (C.c_int32 * max(n, 1))(*[int(v) for v in starts])
+    mask, rec, ws = _detect_buffers("detect_frames", logits.device, F, H, W, mask, rec, ws, want_mask, "detect_frames_ws_bytes(n, S)",
+                                    detect_frames_ws_bytes(n, S))
     capi.call("pc_detect_frames", ptr(logits), int(F), int(H), int(W), int(h0), int(w0), S, st, n, int(f_skip), int(row0), ptr(mask), ptr(rec),
               ptr(ws), stream())
     return mask, rec
 
 
-MAX_VIEWS = 32              # views of one pc_clips_from_u8_views / pc_detect_frames_views launch
+MAX_VIEWS = 32              # views of one pc_clips_from_u8_views / pc_detect_frames_views launch (csrc/clipgeom.h); detect.py takes it from here
 
 
 def _view_table(views, who):
@@ -671,11 +681,9 @@ def clips_from_u8_views(video, views, S, starts, f_skip=2, view_stride=None, out
     """pc_clips_from_u8_views: clips_from_u8 for every view (h0, w0, flip) of the n <= 32 clips in one launch.  View v of clip c is written at
     clip slot v * view_stride + c (view_stride >= n, default n).  -> data [V, view_stride, 8, S, S, 4] float32, or `out` (a contiguous float32
     device tensor with room for (V - 1) * view_stride + n clips) as it was given; the slots between the views are not written."""
-    if video.dtype != torch.uint8 or video.dim() != 4 or video.shape[3] != 3 or not video.is_contiguous():
-        raise ValueError("clips_from_u8_views: contiguous uint8 [F,H,W,3] frames")
-    F, H, W = (int(v) for v in video.shape[:3])
+    F, H, W = _u8_video(video, "clips_from_u8_views")
     tab, V = _view_table(views, "clips_from_u8_views")
-    n = len(starts)
+    st, n = _starts_table(starts)
     stride = n if view_stride is None else int(view_stride)
     if stride < n:
         raise ValueError("clips_from_u8_views: view_stride = %d below the %d clips" % (stride, n))
@@ -683,7 +691,6 @@ def clips_from_u8_views(video, views, S, starts, f_skip=2, view_stride=None, out
         out = torch.empty(V, stride, 8, S, S, 4, device=video.device)
     elif out.dtype != torch.float32 or not out.is_contiguous() or out.numel() < ((V - 1) * stride + n) * 32 * S * S or out.device != video.device:
         raise ValueError("clips_from_u8_views: out must be a contiguous float32 device tensor of at least ((V-1)*view_stride+n)*8*S*S*4 elements")
-    st = (C.c_int32 * max(n, 1))(*[int(v) for v in starts])
     capi.call("pc_clips_from_u8_views", ptr(video), F, H, W, int(S), tab, V, stride, st, n, int(f_skip), ptr(out), stream())
     return out
 
@@ -699,27 +706,15 @@ def detect_frames_views(logits, views, starts, F, H, W, f_skip=2, view_stride=No
     if logits.dtype != torch.float32 or not logits.is_contiguous():
         raise ValueError("detect_frames_views: contiguous float32 logits")
     tab, V = _view_table(views, "detect_frames_views")
-    S, n = int(logits.shape[-1]), len(starts)
+    st, n = _starts_table(starts)
+    S = int(logits.shape[-1])
     stride = n if view_stride is None else int(view_stride)
     if stride < n:
         raise ValueError("detect_frames_views: view_stride = %d below the %d clips" % (stride, n))
     if int(logits.shape[-2]) != S or logits.numel() < ((V - 1) * stride + n) * 8 * S * S:
         raise ValueError("detect_frames_views: logits %s do not hold %d views of %d clips of 8 x %d x %d at stride %d" % (tuple(logits.shape), V, n, S, S, stride))
-    dev = logits.device
-    if mask is None and want_mask:
-        mask = torch.zeros(F, H, W, dtype=torch.uint8, device=dev)
-    if mask is not None and (mask.dtype != torch.uint8 or not mask.is_contiguous() or mask.numel() != F * H * W or mask.device != dev):
-        raise ValueError("detect_frames_views: mask must be a contiguous uint8 device tensor [F,H,W]")
-    if rec is None:
-        rec = torch.zeros(F, DETECT_REC_WORDS, dtype=torch.int32, device=dev)
-    elif rec.dtype != torch.int32 or not rec.is_contiguous() or rec.numel() != F * DETECT_REC_WORDS or rec.device != dev:
-        raise ValueError("detect_frames_views: rec must be a contiguous int32 device tensor [F,8]")
-    need = detect_frames_views_ws_bytes(n, H, W)
-    if ws is None and need > 0:
-        ws = torch.empty(need, dtype=torch.uint8, device=dev)
-    elif ws is not None and (not ws.is_contiguous() or ws.numel() * ws.element_size() < need or ws.device != dev):
-        raise ValueError("detect_frames_views: ws must hold detect_frames_views_ws_bytes(n, H, W) = %d bytes" % need)
-    st = (C.c_int32 * max(n, 1))(*[int(v) for v in starts])
+    mask, rec, ws = _detect_buffers("detect_frames_views", logits.device, F, H, W, mask, rec, ws, want_mask, "detect_frames_views_ws_bytes(n, H, W)",
+                                    detect_frames_views_ws_bytes(n, H, W))
     capi.call("pc_detect_frames_views", ptr(logits), int(F), int(H), int(W), S, tab, V, stride, st, n, int(f_skip), int(row0), ptr(mask), ptr(rec),
               ptr(ws), stream())
     return mask, rec

@@ -1,6 +1,7 @@
 """GPU: the kernels of the detection output (csrc/detect.hip, and the truth switch of csrc/evalclips.hip) on their own.
 
-pc_clips_from_u8 must write the bits pc_eval_clips_from_u8 writes.  pc_detect_frames is checked against a torch restatement (sigmoid >= 0.5,
+pc_clips_from_u8 must write the bits pc_eval_clips_from_u8 writes, and both (one kernel) those of the numpy restatement of
+tests/clipcut_ref.py, truth included.  pc_detect_frames is checked against a torch restatement (sigmoid >= 0.5,
 the clip interleave undone on the host, pasted into full frames) at the smallest shapes at which each of its parts can go wrong: a clip with
 seven frames past the end; an odd W and a mask that starts at an odd address (byte stores); three clips whose frames interleave; two launches
 into one video; 32 clips in one launch; and one frame whose mask lies beyond byte 2^31.  Masks, counts and boxes are exact; the count also
@@ -12,6 +13,7 @@ import pytest
 import torch
 
 from picons_amd import evalstep, ops
+from tests import clipcut_ref
 
 pytestmark = pytest.mark.gpu
 SPECIALS = (0.0, -0.0, -5e-8, -1e-7, -9.9e-7, -1.1e-6, 80.0, -80.0, float("inf"), float("-inf"), float("nan"))
@@ -165,11 +167,14 @@ def test_clips_from_u8_writes_the_bits_of_eval_clips_from_u8(F, H, W, S, h0, w0)
     truth = torch.randint(0, 3, (F, H, W), generator=g, dtype=torch.uint8).cuda()
     starts = evalstep.clip_starts(F, np.ones(F))
     n = len(starts)
-    want, _gt = ops.eval_clips_from_u8(video, truth, h0, w0, S, starts)
-    buf = torch.full((n * 32 * S * S + 64,), 7.0, device="cuda")
-    got = ops.clips_from_u8(video, h0, w0, S, starts, out=buf[:n * 32 * S * S])
+    want, gt = ops.eval_clips_from_u8(video, truth, h0, w0, S, starts)
+    ref_data, ref_gt = clipcut_ref.cut(video.cpu().numpy(), [(h0, w0, 0)], S, starts, truth=truth.cpu().numpy())
+    assert clipcut_ref.same_bits(want, ref_data) and clipcut_ref.same_bits(gt, ref_gt)              # both entries share a kernel: the host's bits
+    buf = torch.full((64 + n * 32 * S * S + 64,), 7.0, device="cuda")
+    got = ops.clips_from_u8(video, h0, w0, S, starts, out=buf[64:64 + n * 32 * S * S])
     assert torch.equal(got.view(-1).view(torch.int32), want.view(-1).view(torch.int32))            # the same bits, -0.0 and all
-    assert bool((buf[n * 32 * S * S:] == 7.0).all())
+    assert clipcut_ref.same_bits(got, ref_data)
+    assert bool((buf[:64] == 7.0).all()) and bool((buf[64 + n * 32 * S * S:] == 7.0).all())
     assert torch.equal(ops.clips_from_u8(video, h0, w0, S, starts).view(-1), want.view(-1))
     assert bool((want.view(n, 8, S, S, 4)[..., 3] == 0).all()) and (F >= 16 or bool((want.view(n, 8, S, S, 4)[0, 7] == 0).all()))
 

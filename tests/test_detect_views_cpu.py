@@ -11,7 +11,7 @@ import numpy as np
 import pytest
 
 import __graft_entry__ as ge
-from picons_amd import capi, detect, evalstep
+from picons_amd import capi, detect, evalstep, ops
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -110,6 +110,13 @@ def test_bad_arguments_are_refused_without_gpu(built):
             rc = fn(*[args[k] for k in order], None)
             assert rc == -1, (fn.__name__, key, val, rc)         # PC_E_ARG, before any HIP call (there is no device here to make one on)
             assert word in built.pc_last_error(), (fn.__name__, key, val, built.pc_last_error())
+    # the cap of the library (csrc/clipgeom.h) and the one the Python side keeps (ops.MAX_VIEWS, which detect.py takes) are one number
+    cap = ops.MAX_VIEWS
+    for fn, order, ok, _bad in _refusals(built):
+        assert fn(*[dict(ok, V=cap + 1)[k] for k in order], None) == -1 and b"views outside 1..%d" % cap in built.pc_last_error()
+    assert ops._view_table([(0, 0, 0)] * cap, "test")[1] == cap and detect.MAX_VIEWS == cap
+    with pytest.raises(ValueError, match="1..%d views" % cap):
+        ops._view_table([(0, 0, 0)] * (cap + 1), "test")
     frames = built.pc_detect_frames_views
     assert frames(C.c_void_p(64), 20, 1 << 16, 1 << 16, 8, (C.c_int32 * 3)(0, 0, 0), 1, 2, (C.c_int32 * 2)(0, 1), 2, 2, 0, None, C.c_void_p(64),
                   C.c_void_p(64), None) == -1 and b"2^31" in built.pc_last_error()

@@ -2,7 +2,8 @@
 csrc/detect.hip).
 
 The cut kernel must write, per unflipped view, the bits pc_clips_from_u8 writes at that crop, per flipped view their left-right mirror image,
-and nothing in front of, between (view_stride > n) or behind the views.
+and nothing in front of, between (view_stride > n) or behind the views.  The two entries share a kernel, so every view is also held to the
+numpy restatement of tests/clipcut_ref.py bit for bit.
 
 The merge kernel is checked against the numpy float32 restatement of tests/detectviews_ref.py (views in table order, float32 adds, one
 division): masks, counts and boxes exact; a frame score no further from float64 than the larger of 1e-6 and twice the distance of an fp32
@@ -15,7 +16,7 @@ import pytest
 import torch
 
 from picons_amd import detect, evalstep, ops
-from tests import detectviews_ref as ref
+from tests import clipcut_ref, detectviews_ref as ref
 
 pytestmark = pytest.mark.gpu
 SPECIALS = (0.0, -0.0, -5e-8, -1e-7, -9.9e-7, -1.1e-6, 80.0, -80.0, float("nan"))
@@ -42,12 +43,14 @@ def test_clips_from_u8_views_writes_the_bits_of_clips_from_u8_per_view(F, H, W, 
     assert out.data_ptr() == buf[64:].data_ptr()
     assert bool((buf[:64] == 7.0).all()) and bool((buf[64 + body:] == 7.0).all())
     slots = buf[64:64 + body].view(-1, 8, S, S, 4)
+    host = clipcut_ref.cut(video.cpu().numpy(), views, S, starts)
     for v, (h0, w0, fl) in enumerate(views):
         want = ops.clips_from_u8(video, h0, w0, S, starts).view(n, 8, S, S, 4)
         if fl:
             want = want.flip(3)
         got = slots[v * stride:v * stride + n]
         assert torch.equal(got.contiguous().view(torch.int32), want.contiguous().view(torch.int32)), (v, h0, w0, fl)      # the same bits
+        assert clipcut_ref.same_bits(got, host[v]) and clipcut_ref.same_bits(want, host[v]), (v, h0, w0, fl)              # and the host's
         assert bool((got[..., 3] == 0).all())
         if v + 1 < V:
             assert bool((slots[v * stride + n:(v + 1) * stride] == 7.0).all()), v          # the stride gap is not written
