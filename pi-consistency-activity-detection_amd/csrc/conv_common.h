@@ -1,5 +1,5 @@
-// Pieces shared by the gather-GEMM conv kernels (conv.hip: fp32 MFMA; conv_x6.hip: fp32 emulated on the bf16 matrix cores):
-// the kernel-side descriptor, the LDS-DMA helpers and the output-tile epilogues.
+// Pieces shared by the gather-GEMM conv kernels (conv.hip: fp32 MFMA forward / dgrad; conv_x6.hip: fp32 emulated on the bf16 matrix cores;
+// wgrad.hip: the weight gradients, both ways): the kernel-side descriptor, the LDS-DMA helpers, the output-tile epilogues and the bf16 split.
 #pragma once
 #include "common.h"
 
@@ -146,6 +146,18 @@ __device__ __forceinline__ void x6_split2(float x0, float x1, uint32_t& h, uint3
     m = cvt_pk_bf16(r0, r1);
     const float s0 = r0 - __uint_as_float(m << 16), s1 = r1 - __uint_as_float(m & 0xffff0000u);
     l = cvt_pk_bf16(s0, s1);
+}
+// The six products of two split operands (planes h, m, l of eight bf16 each; weight-gradient kernels, where both operands are activations):
+// the five small ones go into `lo` -- h*l, l*h, m*m, h*m, m*h, in this order --, h*h into `hi`.  lo and hi may be the same accumulator.
+typedef __attribute__((ext_vector_type(8))) __bf16 x6_bf8;
+typedef __attribute__((ext_vector_type(4))) uint32_t x6_u4;
+__device__ __forceinline__ void x6_mfma(const x6_u4& a, const x6_u4& b, f32x16& c) {
+    c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(x6_bf8, a), __builtin_bit_cast(x6_bf8, b), c, 0, 0, 0);
+}
+__device__ __forceinline__ void x6_mma6(const x6_u4 (&A)[3], const x6_u4 (&B)[3], f32x16& lo, f32x16& hi) {
+    x6_mfma(A[0], B[2], lo); x6_mfma(A[2], B[0], lo); x6_mfma(A[1], B[1], lo);
+    x6_mfma(A[0], B[1], lo); x6_mfma(A[1], B[0], lo);
+    x6_mfma(A[0], B[0], hi);
 }
 
 }  // namespace

@@ -155,7 +155,7 @@ WG_CASES = [(64, 64, (2, 8, 112), 2, 1), (64, 192, (4, 6, 56), 2, 2), (96, 128, 
 
 @pytest.mark.parametrize("Ci,Co,thw,N,st", WG_CASES)
 def test_x6_row_segment_wgrad_vs_fp64_and_native(Ci, Co, thw, N, st):
-    """PC_WG_X6: the 3x3x3 weight gradient with both operands split in registers (csrc/conv.hip wgrad3_x6_kernel), against an fp64 torch
+    """PC_WG_X6: the 3x3x3 weight gradient with both operands split in registers (csrc/wgrad.hip wgrad3_x6_kernel), against an fp64 torch
     gradient and against the native fp32-MFMA kernel on the same launch: its error must be no larger (operands as the step has them: a
     gradient of mixed sign and a ReLU output)."""
     g = torch.Generator().manual_seed(21)
@@ -180,7 +180,7 @@ def test_x6_row_segment_wgrad_vs_fp64_and_native(Ci, Co, thw, N, st):
 
 @pytest.mark.parametrize("Co,thw,N", [(64, (8, 56, 56), 2), (64, (6, 224, 224), 1), (24, (5, 18, 112), 1)])
 def test_x6_stem_wgrad_vs_fp64_and_native(Co, thw, N):
-    """PC_WG_X6 | PC_WG_CS3 on the stem's 7x7x7 stride-2 weight gradient (round 6: csrc/conv.hip wgrad4_x6_kernel; autograd of Conv3d_1a_7x7,
+    """PC_WG_X6 | PC_WG_CS3 on the stem's 7x7x7 stride-2 weight gradient (round 6: csrc/wgrad.hip wgrad4_x6_kernel; autograd of Conv3d_1a_7x7,
     /root/reference/models/pytorch_i3d.py:221-225): chunks of two 16-position sub-chunks incl. rows that are not whole sub-chunks (W = 28 = 16 + 12),
     the real 112-wide rows, fewer than 64 output channels, odd extents along t / h.  Bar as for every converted kernel: no further from fp64 than
     the native fp32-MFMA kernel (wgrad4_kernel) on the same launch; operands as the step has them (a clip in [0, 1], a gradient of mixed sign)."""

@@ -1,6 +1,6 @@
 """The kernel variants the training step selects at the product shape, as a table (test infrastructure; a plain module).
 
-The dispatchers of csrc/conv.hip, conv_x6.hip, wino.hip and wino4.hip choose a kernel template instance per launch shape, so steps of
+The dispatchers of csrc/conv.hip, wgrad.hip, conv_x6.hip, wino.hip and wino4.hip choose a kernel template instance per launch shape, so steps of
 m = 2..8 clips run different instances and epilogues.  A CLASS is what one matrix launch exercises:
 
   conv / bf16-split conv:  (variant string of pc_conv_variant, epilogue flags, activation, activation from a channel on, batch groups > 1,

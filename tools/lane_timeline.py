@@ -26,7 +26,7 @@ def clean(name):
 
 
 # rocprofv3's dispatch record does not carry dynamic LDS and reports allocation granules, so the GEMM and EM kernels' resident
-# blocks per CU come from their launch code (conv.hip: __launch_bounds__(256, 2), 3 for the small-tile wgrad variants; caps.hip)
+# blocks per CU come from their launch code (conv.hip, wgrad.hip: __launch_bounds__(256, 2), 3 for the small-tile wgrad variants; caps.hip)
 OVERRIDE = (("conv_x6_kernel<256", 1), ("conv_x6_kernel<64, 64", 3), ("conv_x6_kernel", 2), ("wgrad4_kernel", 3), ("wgrad_kernel<64,", 3), ("wgrad_kernel<128, 256", 3), ("conv_gemm", 2), ("wgrad", 2), ("em_fwd", 1), ("em_bwd", 1))
 
 

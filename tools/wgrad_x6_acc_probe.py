@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""What the hi / lo accumulator pair buys in the generic bf16-split weight gradient (csrc/conv.hip wgrad_body<..., X6, HILO>):
+"""What the hi / lo accumulator pair buys in the generic bf16-split weight gradient (csrc/wgrad.hip wgrad_body<..., X6, HILO>):
 error against an fp64 torch gradient and time per launch for native fp32 MFMA, the split with the pair, and the split with one accumulator
 (flag bit 4, diagnostic library only).  Runs on the GPU box:  make -C pi-consistency-activity-detection_amd/csrc diag && python tools/wgrad_x6_acc_probe.py"""
 import os, sys
