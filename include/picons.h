@@ -66,7 +66,8 @@ typedef void* pc_stream;            /* hipStream_t */
  * 104: PC_F_BKMAJOR, pc_wino_weights_multi / PC_OP_WINO_WEIGHTS_MULTI; 105: pc_val_metrics / PC_OP_VAL_METRICS;
  * 106: pc_truth_frame_flags / pc_eval_clips_from_u8 / pc_video_vote;
  * 107: pc_clips_from_u8 / pc_detect_frames / pc_detect_frames_ws_bytes / pc_video_class; the entries pc_clips_from_u8_views / pc_detect_frames_views /
- * pc_detect_frames_views_ws_bytes came later and move nothing: no struct grew, no op's operands changed).  Descriptors must be zero-initialised by the caller:
+ * pc_detect_frames_views_ws_bytes came later and move nothing: no struct grew, no op's operands changed; so did pc_frame_instances with its
+ * PC_INST_* constants: came later, moves nothing).  Descriptors must be zero-initialised by the caller:
  * fields added later read as "old behaviour" when 0.  pc_version() returns the value the library was built with; the Python host
  * (capi.lib()) refuses a library whose version differs from the header it mirrors. */
 #define PC_VERSION 107
@@ -451,6 +452,28 @@ int     pc_clips_from_u8_views(const uint8_t* video, int F, int H, int W, int S,
 int64_t pc_detect_frames_views_ws_bytes(int n, int H, int W);
 int     pc_detect_frames_views(const float* logits, int F, int H, int W, int S, const int32_t* views, int V, int view_stride,
                                const int32_t* starts, int n, int f_skip, int row0, uint8_t* mask, int32_t* rec, void* ws, pc_stream s);
+/* Per-frame instances (csrc/instances.hip; picons_amd/detect.py: DetectEngine(instances=K)): the masks pc_detect_frames* leave, split into
+ * connected components on the device.  mask uint8 [F][H][W] (any non-zero byte is foreground; a frame may start at any byte address; frame
+ * offsets are 64-bit), conn 4 or 8.  For each of the frames f0 .. f0 + nf - 1 the launch writes the WHOLE record of `inst` int32
+ * [F][PC_INST_HDR + K * PC_INST_WORDS] and, if `imap` is not null, the WHOLE frame of imap uint8 [F][H][W]; no other frame is touched and
+ * nothing has to be zeroed in front of it.  A null imap gives bit-identical records.
+ *   header  [0] n_comp, the components of at least min_area pixels   [1] kept = min(n_comp, K)   [2] n_runs, the row runs (maximal horizontal
+ *           foreground segments) of the frame   [3] flags, bit 0 = overflow
+ *   slot r < K   area, x0, y0, x1, y1 (half-open box, full-frame coordinates), first = y * W + x of the component's first pixel in raster
+ *           order; ranked by area descending, ties by first ascending; slots from kept on are all zeros
+ *   imap    0 background, r + 1 on the component of rank r < kept, 255 on every other foreground pixel (below min_area or beyond K)
+ * One 256-thread block per frame labels the runs in LDS, at most PC_INST_MAX_RUNS of them and PC_INST_MAX_ROWS rows.  A frame with more runs
+ * (or whose labelling did not settle within its bound of n_runs + 1 iterations) is an OVERFLOW: flags = 1, n_comp = kept = 0, the slots zero,
+ * n_runs the true count, imap 255 on all foreground; the caller falls back to the frame's single box.  Integer LDS atomics only, no
+ * floating point: a record is bit-identical from run to run.  Refusals (PC_E_ARG before any HIP call, nothing allocated, enqueued on `s`
+ * only): null mask or inst; F, H, W < 1; H > PC_INST_MAX_ROWS; W > 65535; H * W >= 2^31; f0 < 0, nf < 1, f0 + nf > F; conn not 4 or 8;
+ * min_area < 1; K outside 1..32; inst not 4-byte aligned. */
+#define PC_INST_HDR      4
+#define PC_INST_WORDS    6
+#define PC_INST_MAX_RUNS 2048
+#define PC_INST_MAX_ROWS 2048
+int     pc_frame_instances(const uint8_t* mask, int F, int H, int W, int f0, int nf, int conn, int min_area, int K, int32_t* inst,
+                           uint8_t* imap, pc_stream s);
 /* cv2.resize on uint8 images [n][H][W][C] -> [n][Ho][Wo][C] (C <= 4), the calls of the reference's loaders:
  * datasets/jhmdb_dataloader.py:252 (frames, INTER_AREA 320x240 -> 256x256), :267,:281 (puppet masks, INTER_NEAREST),
  * :192,:208 and ucf_dataloader.py:165,171 (224 crop -> frame size, INTER_LINEAR; the identity at 224).  OpenCV's 8-bit

@@ -1,0 +1,334 @@
+// Per-frame instances on the device: the masks pc_detect_frames* leave (uint8 [F][H][W], video order, full-frame coordinates) split into
+// connected components, ranked by area, specks dropped -- what a caller had to copy every mask to the host and label there for.
+//   pc_frame_instances   one 256-thread block per frame, run-based labelling in LDS: the row runs (maximal horizontal foreground segments)
+//                        in raster order, labels as minima over adjacent runs with pointer jumping, area and box per root, K rounds of block
+//                        arg-max; optionally the map of ranks.  Latency-bound (F blocks on 256 CUs, a 240 x 320 frame is 77 KB and stays in
+//                        L2): nothing here is tuned for bandwidth.
+// Integer LDS atomics only; no global atomics, no floating point, nothing between blocks, no spin-waits.  The fixed point of the labelling
+// (every run holds the smallest run index of its component) is unique, so a record does not depend on scheduling although reads inside an
+// iteration race with writes: a label only decreases and never leaves its component.  Every loop's trip count is fixed before it starts; the
+// labelling loop has the explicit bound n_runs + 1 (synchronous propagation reaches distance k after k iterations and a component's diameter
+// is below n_runs) and a frame that hits it is reported as overflow, not looped on.
+#include "common.h"
+
+namespace {
+
+constexpr int BT = 256, NW = BT / 64;
+constexpr int MAXR = PC_INST_MAX_RUNS, MAXROWS = PC_INST_MAX_ROWS;
+constexpr int HDR = PC_INST_HDR, SLOT = PC_INST_WORDS;
+static_assert(MAXROWS == BT * 8, "the row prefix sum gives every thread eight rows");
+static_assert(MAXR <= 65536 && MAXROWS <= 65536, "run rows and columns are held as uint16");
+// static LDS: 3 uint16 + 5 int32 per run, the row table, the reduction scratch
+static_assert(MAXR * (3 * 2 + 5 * 4) + (MAXROWS + 1) * 4 + 256 <= 64 * 1024, "static LDS of frame_instances_kernel above 64 KiB");
+
+struct InstK {
+    const uint8_t* mask; int32_t* inst; uint8_t* imap;
+    int H, W, f0, conn, min_area, K;
+};
+
+__device__ __forceinline__ int wave_incl_scan(int v, int lane) {
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) {
+        const int t = __shfl_up(v, o, 64);
+        if (lane >= o) v += t;
+    }
+    return v;
+}
+
+// the set bits of a ballot in the lanes below this one
+__device__ __forceinline__ int lanes_below(unsigned long long m) {
+    return (int)__builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u));
+}
+
+// four pixels at q as bits 0..3 (non-zero byte = foreground); the first n (0..4) of them count, q itself must be a byte of the mask even for
+// n = 0.  A frame starts at any byte address when W is odd, so the four bytes come out of the one or two ALIGNED dwords that hold them -- the
+// second is fetched only if it holds one of the n bytes, so every dword read holds a byte of the mask and lies in its allocation -- and there is
+// no branch around the loads: a caller's loads for several rows are all issued before the first is waited for.
+__device__ __forceinline__ uint32_t fg_bits(const uint8_t* q, int n) {
+    const uintptr_t a = (uintptr_t)q;
+    const int sh = (int)(a & 3);
+    const uint32_t* p0 = (const uint32_t*)(a - sh);
+    const uint32_t* p1 = (4 - sh < n) ? p0 + 1 : p0;
+    const uint32_t w0 = *p0, w1 = *p1;
+    const uint32_t v = (uint32_t)((((unsigned long long)w1 << 32) | w0) >> (8 * sh));
+    const uint32_t b = ((v & 0xffu) ? 1u : 0u) | ((v & 0xff00u) ? 2u : 0u) | ((v & 0xff0000u) ? 4u : 0u) | ((v & 0xff000000u) ? 8u : 0u);
+    return b & ((1u << n) - 1u);
+}
+
+// One wave walks ROWS rows at a time (rows y0, y0 + NW, ...: the wave's next ones) in segments of 256 pixels, four per lane; the loads of all
+// ROWS rows are issued before the first is looked at (a wave that waits for each row's bytes before asking for the next spends its time
+// waiting), and a segment without foreground costs one ballot.  A pixel
+// starts a run iff it is foreground and its left neighbour is not, and ends one iff its right neighbour is not: both are decided per pixel
+// from the row itself, so a run that crosses a lane's or a segment's boundary is one run, and the j-th start and the j-th end of a row belong
+// to the same run.  WRITE: run `rowstart[y] + j` gets x0 / row from its start and x1 from its end; otherwise rowstart[y] = the runs of row y.
+constexpr int ROWS = 8;
+
+template <bool WRITE>
+__device__ __forceinline__ void scan_rows(const uint8_t* __restrict__ mf, int H, int W, int y0, int lane, int* rowstart, uint16_t* rx0,
+                                          uint16_t* rx1, uint16_t* rrow) {
+    const int nseg = (W + 255) >> 8;
+    int sb[ROWS], eb[ROWS], base[ROWS];
+    uint32_t carry[ROWS];                                            // the last pixel of the segment before: left neighbour of this one's first
+#pragma unroll
+    for (int j = 0; j < ROWS; ++j) {
+        const int y = y0 + j * NW;
+        sb[j] = eb[j] = 0;
+        carry[j] = 0;
+        base[j] = (WRITE && y < H) ? rowstart[y] : 0;
+    }
+    for (int g = 0; g < nseg; ++g) {
+        const int x = (g << 8) + (lane << 2);
+        uint32_t b[ROWS], after[ROWS];
+#pragma unroll
+        for (int j = 0; j < ROWS; ++j) {                             // no branch here: addresses outside the row are moved to its first byte
+            const int y = y0 + j * NW;
+            const bool in = y < H && x < W;
+            const uint8_t* rp = mf + (size_t)(y < H ? y : 0) * W;
+            b[j] = fg_bits(rp + (in ? x : 0), in ? min(4, W - x) : 0);
+            const bool last = in && lane == 63 && x + 4 < W;         // the right neighbour of the segment's last pixel
+            after[j] = last & (rp[last ? x + 4 : 0] != 0);
+        }
+#pragma unroll
+        for (int j = 0; j < ROWS; ++j) {
+            const int y = y0 + j * NW;
+            if (y >= H) continue;                                    // the same in every lane of the wave
+            if (__ballot(b[j] != 0u) == 0ull) { carry[j] = 0; continue; }     // no foreground in the segment (the same in every lane)
+            // the neighbours across the lanes: the last pixel of the lane before, the first of the lane after
+            const unsigned long long m0 = __ballot(b[j] & 1u), m3 = __ballot((b[j] >> 3) & 1u);
+            const uint32_t prev = lane > 0 ? (uint32_t)(m3 >> (lane - 1)) & 1u : carry[j];
+            const uint32_t next = lane < 63 ? (uint32_t)(m0 >> (lane + 1)) & 1u : after[j];
+            carry[j] = (uint32_t)(m3 >> 63);
+            const uint32_t ext = prev | (b[j] << 1) | (next << 5);   // bit e: the pixel left of pixel e; bit e + 2: the one right of it
+            const uint32_t st = b[j] & ~ext & 0xfu, en = b[j] & ~(ext >> 2) & 0xfu;
+            // starts and ends in the lanes below, and in the wave: ballots and bit counts, no trip through LDS.  Four pixels hold at most two
+            // starts and two ends.
+            const int ns = __popc(st), ne = __popc(en);
+            const unsigned long long s1 = __ballot(ns >= 1), s2 = __ballot(ns >= 2), e1 = __ballot(ne >= 1), e2 = __ballot(ne >= 2);
+            const int ts = __popcll(s1) + __popcll(s2), te = __popcll(e1) + __popcll(e2);
+            if (WRITE) {
+                int si = base[j] + sb[j] + lanes_below(s1) + lanes_below(s2), ei = base[j] + eb[j] + lanes_below(e1) + lanes_below(e2);
+#pragma unroll
+                for (int e = 0; e < 4; ++e) {
+                    if ((st >> e) & 1u) { if (si < MAXR) { rx0[si] = (uint16_t)(x + e); rrow[si] = (uint16_t)y; } ++si; }
+                    if ((en >> e) & 1u) { if (ei < MAXR) rx1[ei] = (uint16_t)(x + e + 1); ++ei; }
+                }
+            }
+            sb[j] += ts; eb[j] += te;
+        }
+    }
+    if (!WRITE && lane == 0) {
+#pragma unroll
+        for (int j = 0; j < ROWS; ++j)
+            if (y0 + j * NW < H) rowstart[y0 + j * NW] = sb[j];
+    }
+}
+
+// grid (nf): block b is frame f0 + b.
+__global__ __launch_bounds__(256) void frame_instances_kernel(const InstK p) {
+    __shared__ uint16_t rx0[MAXR], rx1[MAXR], rrow[MAXR];            // run i: row rrow[i], columns [rx0[i], rx1[i]); raster order
+    __shared__ int label[MAXR];
+    __shared__ int area[MAXR], xmin[MAXR], xmax[MAXR], ymax[MAXR];   // per root; area < 0: the root has rank -area - 1
+    __shared__ int rowstart[MAXROWS + 1];                            // the runs of row y are rowstart[y] .. rowstart[y + 1] - 1
+    __shared__ int wsum[NW];
+    __shared__ unsigned long long red[2][NW];
+    __shared__ int ncomp_sh;
+
+    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+    const int H = p.H, W = p.W, K = p.K;
+    const uint32_t HW = (uint32_t)H * (uint32_t)W;
+    const size_t f = (size_t)p.f0 + blockIdx.x;
+    const uint8_t* __restrict__ mf = p.mask + f * HW;
+    int32_t* rec = p.inst + f * (size_t)(HDR + K * SLOT);
+    uint8_t* __restrict__ im = p.imap ? p.imap + f * HW : nullptr;
+
+    // ---- runs: count per row, prefix sum over the rows, write
+    for (int y = wv; y < H; y += NW * ROWS) scan_rows<false>(mf, H, W, y, lane, rowstart, rx0, rx1, rrow);
+    __syncthreads();
+    int v[8], s = 0;
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+        const int y = tid * 8 + j;
+        v[j] = y < H ? rowstart[y] : 0;
+        s += v[j];
+    }
+    const int inc = wave_incl_scan(s, lane);
+    if (lane == 63) wsum[wv] = inc;
+    __syncthreads();
+    int off = inc - s, total = 0;
+#pragma unroll
+    for (int w = 0; w < NW; ++w) {
+        if (w < wv) off += wsum[w];
+        total += wsum[w];
+    }
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+        const int y = tid * 8 + j;
+        if (y < H) rowstart[y] = off;
+        off += v[j];
+    }
+    if (tid == 0) rowstart[H] = total;
+    __syncthreads();
+
+    bool over = total > MAXR;                                        // the same in every thread, here and below
+    const int n = over ? 0 : total;
+    if (!over) {
+        for (int y = wv; y < H; y += NW * ROWS) scan_rows<true>(mf, H, W, y, lane, rowstart, rx0, rx1, rrow);
+        for (int i = tid; i < n; i += BT) label[i] = i;
+        __syncthreads();
+        // ---- labels: minima over the adjacent runs of the rows above and below, one pointer jump, until nothing changes
+        const int slack = p.conn == 8 ? 1 : 0;                       // 4: a0 < b1 && b0 < a1; 8: a0 <= b1 && b0 <= a1
+        bool settled = false;
+        for (int it = 0; it <= n; ++it) {
+            int ch = 0;
+            for (int i = tid; i < n; i += BT) {
+                const int a0 = rx0[i], a1 = rx1[i] + slack, y = rrow[i], l = label[i];
+                int m = l;
+                if (y > 0) {
+                    const int j1 = rowstart[y];
+                    for (int j = rowstart[y - 1]; j < j1; ++j)
+                        if (a0 < (int)rx1[j] + slack && (int)rx0[j] < a1) m = min(m, label[j]);
+                }
+                if (y + 1 < H) {
+                    const int j1 = rowstart[y + 2];
+                    for (int j = rowstart[y + 1]; j < j1; ++j)
+                        if (a0 < (int)rx1[j] + slack && (int)rx0[j] < a1) m = min(m, label[j]);
+                }
+                m = min(m, label[m]);
+                if (m < l) { label[i] = m; ch = 1; }
+            }
+            if (!__syncthreads_or(ch)) { settled = true; break; }
+        }
+        over = !settled;
+    }
+
+    if (over) {
+        if (tid == 0) { rec[0] = 0; rec[1] = 0; rec[2] = total; rec[3] = 1; }
+        for (int t = tid; t < K * SLOT; t += BT) rec[HDR + t] = 0;
+    } else {
+        // ---- area and box per root
+        for (int i = tid; i < n; i += BT) { area[i] = 0; xmin[i] = 0x7fffffff; xmax[i] = 0; ymax[i] = 0; }
+        if (tid == 0) ncomp_sh = 0;
+        __syncthreads();
+        for (int i = tid; i < n; i += BT) {
+            const int r = label[i], a0 = rx0[i], a1 = rx1[i];
+            atomicAdd(&area[r], a1 - a0);
+            atomicMin(&xmin[r], a0);
+            atomicMax(&xmax[r], a1);
+            atomicMax(&ymax[r], (int)rrow[i] + 1);
+        }
+        __syncthreads();
+        int cnt = 0;
+        for (int i = tid; i < n; i += BT) cnt += area[i] >= p.min_area;      // a run that is no root keeps area 0 < min_area
+        if (cnt) atomicAdd(&ncomp_sh, cnt);
+        __syncthreads();
+        const int ncomp = ncomp_sh, kept = min(ncomp, K);
+        if (tid == 0) { rec[0] = ncomp; rec[1] = kept; rec[2] = total; rec[3] = 0; }
+        for (int t = tid; t < K * SLOT; t += BT)
+            if (t / SLOT >= kept) rec[HDR + t] = 0;
+        // ---- kept rounds of arg-max by (area descending, first pixel ascending): a root is the first run of its component in raster order, so
+        // the smaller root index is the smaller first pixel
+        for (int r = 0; r < kept; ++r) {
+            unsigned long long best = 0;
+            for (int i = tid; i < n; i += BT) {
+                const int a = area[i];
+                if (a >= p.min_area) {
+                    const unsigned long long key = ((unsigned long long)(uint32_t)a << 32) | (0xffffffffu - (uint32_t)i);
+                    best = key > best ? key : best;
+                }
+            }
+#pragma unroll
+            for (int o = 32; o > 0; o >>= 1) {
+                const uint32_t hi = __shfl_xor((uint32_t)(best >> 32), o, 64), lo = __shfl_xor((uint32_t)best, o, 64);
+                const unsigned long long other = ((unsigned long long)hi << 32) | lo;
+                best = other > best ? other : best;
+            }
+            if (lane == 0) red[r & 1][wv] = best;
+            __syncthreads();                                         // red[r & 1] is written again two rounds on, behind the next round's barrier
+            best = red[r & 1][0];
+#pragma unroll
+            for (int w = 1; w < NW; ++w) best = red[r & 1][w] > best ? red[r & 1][w] : best;
+            const int w = (int)(0xffffffffu - (uint32_t)best);
+            if (w >= 0 && w < n && (w & (BT - 1)) == tid) {          // the thread that scans root w: its own next scan sees the mark
+                int32_t* q = rec + HDR + r * SLOT;
+                q[0] = area[w]; q[1] = xmin[w]; q[2] = rrow[w]; q[3] = xmax[w]; q[4] = ymax[w]; q[5] = (int)rrow[w] * W + (int)rx0[w];
+                area[w] = -(r + 1);
+            }
+        }
+        __syncthreads();
+    }
+
+    // ---- the map of ranks: the frame in groups of four consecutive pixels, the run of a foreground pixel by bisection in its row; a thread
+    // has the loads of four groups in flight
+    if (im) {
+        const uint32_t total4 = (HW + 3u) >> 2;
+        for (uint32_t g0 = tid; g0 < total4; g0 += BT * 4) {
+            uint32_t bits[4];
+#pragma unroll
+            for (int u = 0; u < 4; ++u) {
+                const uint32_t g = g0 + u * BT, px = g << 2;
+                const bool in = g < total4;
+                bits[u] = fg_bits(mf + (in ? px : 0u), in ? (int)(HW - px < 4u ? HW - px : 4u) : 0);
+            }
+#pragma unroll
+            for (int u = 0; u < 4; ++u) {
+                const uint32_t g = g0 + u * BT, px = g << 2;
+                if (g >= total4) continue;
+                const int ny = (int)(HW - px < 4u ? HW - px : 4u);
+                const uint32_t b = bits[u];
+                int y = (int)(px / (uint32_t)W), x = (int)(px - (uint32_t)y * (uint32_t)W);
+                uint32_t out = 0, cval = 255u;
+                int cy = -1, cx1 = 0;                                    // the run found last: row, end, value
+#pragma unroll
+                for (int e = 0; e < 4; ++e) {
+                    if ((b >> e) & 1u) {
+                        uint32_t val = 255u;
+                        if (!over) {
+                            if (!(y == cy && x < cx1)) {                 // not the run the pixel before it lay in
+                                int lo = rowstart[y], hi = rowstart[y + 1];
+                                for (int step = hi - lo > 1 ? 32 - __clz(hi - lo - 1) : 0; step > 0; --step) {    // at most 11: 2^11 = PC_INST_MAX_RUNS
+                                    const int mid = (lo + hi) >> 1;
+                                    if (hi - lo > 1) { if ((int)rx0[mid] <= x) lo = mid; else hi = mid; }
+                                }
+                                lo = min(lo, MAXR - 1);
+                                const int a = area[label[lo]];
+                                cy = y; cx1 = rx1[lo]; cval = a < 0 ? (uint32_t)(-a) : 255u;
+                            }
+                            val = cval;
+                        }
+                        out |= val << (8 * e);
+                    }
+                    if (++x == W) { x = 0; ++y; }
+                }
+                uint8_t* q = im + px;
+                if (ny == 4 && ((uintptr_t)q & 3) == 0) {
+                    *(uint32_t*)q = out;
+                } else {
+                    for (int e = 0; e < ny; ++e) q[e] = (uint8_t)(out >> (8 * e));
+                }
+            }
+        }
+    }
+}
+
+}  // namespace
+
+extern "C" int pc_frame_instances(const uint8_t* mask, int F, int H, int W, int f0, int nf, int conn, int min_area, int K, int32_t* inst,
+                                  uint8_t* imap, pc_stream s) {
+    const char* who = "pc_frame_instances";
+    PC_CHECK_ARG(mask && inst, "%s: null pointer", who);
+    PC_CHECK_ARG(F >= 1 && H >= 1 && W >= 1, "%s: F = %d frames of %d x %d are outside what a mask holds", who, F, H, W);
+    PC_CHECK_ARG(H <= PC_INST_MAX_ROWS, "%s: H = %d rows, more than the %d of the row table", who, H, PC_INST_MAX_ROWS);
+    PC_CHECK_ARG(W <= 65535, "%s: W = %d columns, more than 65535", who, W);
+    PC_CHECK_ARG((int64_t)H * W < (1ll << 31), "%s: frames of %d x %d pixels are outside the 2^31 a frame may hold", who, H, W);
+    PC_CHECK_ARG(f0 >= 0 && nf >= 1 && (int64_t)f0 + nf <= F, "%s: frames f0 = %d, nf = %d outside the %d of the mask", who, f0, nf, F);
+    PC_CHECK_ARG(conn == 4 || conn == 8, "%s: conn = %d, 4 or 8", who, conn);
+    PC_CHECK_ARG(min_area >= 1, "%s: min_area = %d below 1", who, min_area);
+    PC_CHECK_ARG(K >= 1 && K <= 32, "%s: K = %d outside 1..32", who, K);
+    PC_CHECK_ARG((uintptr_t)inst % 4 == 0, "%s: inst must be 4-byte aligned", who);
+    InstK k;
+    k.mask = mask; k.inst = inst; k.imap = imap;
+    k.H = H; k.W = W; k.f0 = f0; k.conn = conn; k.min_area = min_area; k.K = K;
+    hipLaunchKernelGGL(frame_instances_kernel, dim3((unsigned)nf), dim3(BT), 0, (hipStream_t)s, k);
+    PC_CHECK_LAUNCH(who);
+    return PC_OK;
+}

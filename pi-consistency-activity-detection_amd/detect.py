@@ -16,6 +16,11 @@ video is cut into several VIEWS (h0, w0, flip) -- crops at their own offsets, op
 crops and its consistency loss ties the map of a clip to the map of its mirror image -- every view runs through the same plan, and
 pc_detect_frames_views merges their logits per full-frame pixel (the mean over the views that cover the pixel) in front of the threshold,
 the box and the score: one pc_clips_from_u8_views launch in front of the forward and one merge launch behind it per video segment.
+
+Instances.  One box per frame is stretched across the image by a single false-positive pixel and holds every actor of a multi-actor video.
+With instances=K one pc_frame_instances launch per video, behind its last clip, splits every frame's mask into its connected components on the
+device and leaves the K largest per frame (area, box, first pixel) next to the records; link_instance_tubes links them across frames into
+per-actor tubes by box IoU.
 """
 from types import SimpleNamespace
 
@@ -49,6 +54,72 @@ def link_tubes(counts, boxes, frame_scores, min_pixels=1, max_gap=0):
         else:
             runs.append([t, t])
     return [(t0, t1, boxes[t0:t1 + 1].copy(), float(scores[t0:t1 + 1][on[t0:t1 + 1]].mean())) for t0, t1 in runs]
+
+
+def box_iou(a, b):
+    """IoU of two half-open boxes x0, y0, x1, y1 (float; 0.0 when either is empty)."""
+    iw, ih = min(a[2], b[2]) - max(a[0], b[0]), min(a[3], b[3]) - max(a[1], b[1])
+    if iw <= 0 or ih <= 0:
+        return 0.0
+    inter = float(iw) * float(ih)
+    return inter / (float(a[2] - a[0]) * float(a[3] - a[1]) + float(b[2] - b[0]) * float(b[3] - b[1]) - inter)
+
+
+def link_instance_tubes(inst_kept, inst_boxes, inst_areas, frame_scores, iou_min=0.3, max_gap=0, min_len=1):
+    """Per-frame instances -> per-actor tubes, greedily and deterministically.  inst_kept [F], inst_boxes [F,K,4], inst_areas [F,K] as
+    Detection holds them (rank order), frame_scores [F].  Frames are taken in order and the open tubes in the order they were opened: each
+    tube takes the not-yet-taken instance of the frame with the highest box IoU against its last box, if that IoU >= iou_min (a tie goes to
+    the lower rank); instances no tube took open new tubes in rank order.  A tube closes once it has gone unmatched for more than max_gap
+    frames; a bridged frame carries an empty box and area 0.  Tubes with fewer than min_len detected frames are dropped.
+    -> [(t0, t1, boxes[t1 - t0 + 1, 4], areas[t1 - t0 + 1], score)] in the order the tubes were opened, t1 inclusive (the last DETECTED frame),
+    score the float64 mean of frame_scores over the tube's detected frames.  A per-instance confidence is out of scope: the frame score is
+    the mean sigmoid over all of the frame's positive pixels, the views path never materialises the merged logits, and no kernel in front
+    of pc_frame_instances changes for it.  iou_min = 0.3 is an API default, not a measured quantity."""
+    kept = np.asarray(inst_kept).reshape(-1)
+    F = kept.size
+    if F == 0:
+        return []
+    boxes = np.asarray(inst_boxes).reshape(F, -1, 4)
+    areas = np.asarray(inst_areas).reshape(F, -1)
+    scores = np.asarray(frame_scores, np.float64).reshape(-1)
+    if not (areas.shape[1] == boxes.shape[1] and scores.size == F) or kept.max() > boxes.shape[1]:
+        raise ValueError("link_instance_tubes: %d frames, boxes %s, areas %s, %d scores" % (F, boxes.shape, areas.shape, scores.size))
+    if not 0.0 <= iou_min <= 1.0 or max_gap < 0 or min_len < 1:
+        raise ValueError("link_instance_tubes: 0 <= iou_min <= 1, max_gap >= 0, min_len >= 1, got %r, %r, %r" % (iou_min, max_gap, min_len))
+    tubes, live = [], []                                  # a tube: dict(t0, frames {t: rank}, last box, last t)
+    for t in range(F):
+        n = int(kept[t])
+        taken = [False] * n
+        still = []
+        for tb in live:
+            best, best_iou = -1, -1.0
+            for r in range(n):
+                if not taken[r]:
+                    v = box_iou(tb["box"], boxes[t, r])
+                    if v >= iou_min and v > best_iou:
+                        best, best_iou = r, v
+            if best >= 0:
+                taken[best] = True
+                tb["frames"][t] = best
+                tb["box"], tb["last"] = boxes[t, best], t
+            if t - tb["last"] <= max_gap:
+                still.append(tb)
+        live = still
+        for r in range(n):
+            if not taken[r]:
+                tb = dict(t0=t, frames={t: r}, box=boxes[t, r], last=t)
+                tubes.append(tb)
+                live.append(tb)
+    out = []
+    for tb in tubes:
+        if len(tb["frames"]) < min_len:
+            continue
+        t0, t1 = tb["t0"], tb["last"]
+        bx, ar = np.zeros((t1 - t0 + 1, 4), boxes.dtype), np.zeros(t1 - t0 + 1, areas.dtype)
+        for t, r in tb["frames"].items():
+            bx[t - t0], ar[t - t0] = boxes[t, r], areas[t, r]
+        out.append((t0, t1, bx, ar, float(scores[sorted(tb["frames"])].mean())))
+    return out
 
 
 def _tile_offsets(L, hw):
@@ -87,14 +158,49 @@ class Detection:
     """One video's detections.  label / class_score / class_scores [C]: the arg-max of the mean class scores of its clips, that mean, all means;
     counts [F] positive pixels, boxes [F, 4] = x0, y0, x1, y1 (half-open, full-frame coordinates, zeros for an empty frame) and frame_scores [F]
     (mean sigmoid over the positive pixels) per frame; masks: device uint8 [F, H, W] or None; views: the (h0, w0, flip) the video was seen
-    through."""
+    through.
 
-    def __init__(self, label, class_score, class_scores, counts, boxes, frame_scores, masks, views=None):
+    With DetectEngine(instances=K) also the frame's connected components of at least min_area pixels, ranked by area (ties: the first pixel in
+    raster order): inst_n [F] how many there are, inst_kept [F] = min(inst_n, K) how many are held, inst_flags [F] (bit 0: the frame had more
+    row runs than the kernel labels -- it then holds ONE instance, the frame's own count and box, with first = -1), inst_areas [F, K],
+    inst_boxes [F, K, 4], inst_first [F, K] (y * W + x of the component's first pixel; zeros from inst_kept on), and imap: device uint8
+    [F, H, W] with 0 background, r + 1 on the instance of rank r, 255 on other foreground (instance_maps=True), else None.  All None without
+    instances."""
+
+    def __init__(self, label, class_score, class_scores, counts, boxes, frame_scores, masks, views=None, inst=None, imap=None):
         self.label, self.class_score, self.class_scores = label, class_score, class_scores
         self.counts, self.boxes, self.frame_scores, self.masks, self.views = counts, boxes, frame_scores, masks, views
+        self.inst_n, self.inst_kept, self.inst_flags, self.inst_areas, self.inst_boxes, self.inst_first = inst if inst is not None else (None,) * 6
+        self.imap = imap
 
     def tubes(self, min_pixels=1, max_gap=0):
         return link_tubes(self.counts, self.boxes, self.frame_scores, min_pixels, max_gap)
+
+    def instance_tubes(self, iou_min=0.3, max_gap=0, min_len=1):
+        if self.inst_kept is None:
+            raise ValueError("instance_tubes: the detection holds no instances (DetectEngine(instances=K))")
+        return link_instance_tubes(self.inst_kept, self.inst_boxes, self.inst_areas, self.frame_scores, iou_min, max_gap, min_len)
+
+
+def check_instances(instances, min_area, conn, masks):
+    """The instance arguments of DetectEngine -> (K, min_area, conn) as ints, or ValueError."""
+    K, min_area, conn = int(instances), int(min_area), int(conn)
+    if not 0 <= K <= ops.INST_MAX_K or min_area < 1 or conn not in (4, 8):
+        raise ValueError("DetectEngine: instances = %d (0..%d), min_area = %d (>= 1), conn = %d (4 or 8)" % (K, ops.INST_MAX_K, min_area, conn))
+    if K > 0 and not masks:
+        raise ValueError("DetectEngine: instances = %d needs masks=True (pc_frame_instances reads the masks)" % K)
+    return K, min_area, conn
+
+
+def substitute_overflow(counts, boxes, min_area, inst):
+    """The instance fields of a video with the frames whose overflow flag is set holding one instance, the frame's own count and box."""
+    n, kept, flags, areas, ibox, first = inst
+    for f in np.flatnonzero(flags & 1).tolist():
+        one = int(counts[f] >= min_area)
+        n[f] = kept[f] = one
+        if one:
+            areas[f, 0], ibox[f, 0], first[f, 0] = counts[f], boxes[f], -1
+    return n, kept, flags, areas, ibox, first
 
 
 class DetectEngine(ClipEngine):
@@ -108,11 +214,18 @@ class DetectEngine(ClipEngine):
     every video.  With any of the three the engine runs V views per clip: all V share a batch, so a batch holds bs // V clips -- bs should be
     a multiple of V, bs < V is refused -- and a video takes clips * V rows of the score ring, row0 + clip * V + view, over all of which its
     class is voted.  A segment of n clips lies view-major in the batch (view v of its clip c at slot v * n + c of the segment's n * V slots:
-    the order on_batch / outputs() show).  Without them: the centre crop, cut as the one view (h0, w0, 0), and pc_detect_frames."""
+    the order on_batch / outputs() show).  Without them: the centre crop, cut as the one view (h0, w0, 0), and pc_detect_frames.
+
+    instances=K > 0 (at most 32; needs masks): behind a video's last clip ONE pc_frame_instances launch over all its frames splits every mask
+    into its connected components (conn 4 or 8) of at least min_area pixels and leaves the K largest per frame behind the class vector, so
+    the one copy to the host takes them too; instance_maps=True also keeps the map of ranks on the device (Detection.imap).  instances=0:
+    nothing of this, today's path and buffer sizes."""
 
     def __init__(self, bs=14, hw=224, num_classes=24, device="cuda:0", state=None, engine=None, capacity=256, seed=47, f_skip=2, pack=False,
-                 masks=True, on_batch=None, tile=False, flip=False, views=None):
+                 masks=True, on_batch=None, tile=False, flip=False, views=None, instances=0, min_area=1, conn=8, instance_maps=False):
         hw = engine.hw if engine is not None else hw
+        self.inst_k, self.min_area, self.conn = check_instances(instances, min_area, conn, masks)
+        self.instance_maps = bool(instance_maps) and self.inst_k > 0
         if hw % 4:
             raise ValueError("DetectEngine: hw = %d must be a multiple of 4 (pc_detect_frames reads the logit rows 16 bytes at a time)" % hw)
         self._setup(bs, hw, num_classes, device, state, engine, capacity, seed, f_skip, pack, on_batch)
@@ -186,8 +299,11 @@ class DetectEngine(ClipEngine):
         self.up_done[slot] = rec.ready
         # records [F][8] and the class vector [C + 2] side by side: one copy to the host takes both.  Every frame below F belongs to one clip,
         # so every mask byte and every record is written by a launch: nothing is filled.
-        rec.dev = torch.empty(F * ops.DETECT_REC_WORDS + self.C + 2, dtype=torch.int32, device=self.dev)
+        # With instances the F records of 4 + 6K words follow behind the class vector: the earlier offsets do not move.
+        rec.inst_words = F * (ops.INST_HDR + self.inst_k * ops.INST_WORDS) if self.inst_k else 0
+        rec.dev = torch.empty(F * ops.DETECT_REC_WORDS + self.C + 2 + rec.inst_words, dtype=torch.int32, device=self.dev)
         rec.mask = torch.empty(F, H, W, dtype=torch.uint8, device=self.dev) if self.masks else None
+        rec.imap = torch.empty(F, H, W, dtype=torch.uint8, device=self.dev) if self.instance_maps else None
         rec.pin = None
         if views:
             need = ops.detect_frames_views_ws_bytes(min(self.bs, 32), H, W)
@@ -220,8 +336,13 @@ class DetectEngine(ClipEngine):
                               want_mask=False)
 
     def _finish(self, rec):
-        """The video's class from its score rows; records and class vector on their way to the host."""
-        ops.video_class(self.scores[rec.row0:rec.row0 + rec.rows], out=rec.dev[rec.F * ops.DETECT_REC_WORDS:].view(torch.float32))
+        """The video's class from its score rows, its instances from its masks (every frame has been written by now, on this stream); records,
+        class vector and instances on their way to the host."""
+        cls0 = rec.F * ops.DETECT_REC_WORDS
+        ops.video_class(self.scores[rec.row0:rec.row0 + rec.rows], out=rec.dev[cls0:cls0 + self.C + 2].view(torch.float32))
+        if self.inst_k:
+            ops.frame_instances(rec.mask, conn=self.conn, min_area=self.min_area, K=self.inst_k, inst=rec.dev[cls0 + self.C + 2:].view(rec.F, -1),
+                                imap=rec.imap, want_imap=False)
         rec.pin = self._stage(rec.dev.numel())
         rec.pin.copy_(rec.dev, non_blocking=True)
 
@@ -233,9 +354,14 @@ class DetectEngine(ClipEngine):
         for rec in self.videos:
             words = rec.pin.numpy()
             counts, boxes, fscores, _rows = ops.decode_detect_records(words[:rec.F * ops.DETECT_REC_WORDS])
-            cls = words[rec.F * ops.DETECT_REC_WORDS:].copy().view(np.float32)
+            cls0 = rec.F * ops.DETECT_REC_WORDS
+            cls = words[cls0:cls0 + self.C + 2].copy().view(np.float32)
+            inst = None
+            if self.inst_k:
+                n, kept, _runs, flags, areas, ibox, first = ops.decode_instances(words[cls0 + self.C + 2:], self.inst_k)
+                inst = substitute_overflow(counts, boxes, self.min_area, (n, kept, flags, areas, ibox, first))
             out.append(Detection(int(cls[self.C]), float(cls[self.C + 1]), cls[:self.C].copy(), counts, boxes, fscores, rec.mask,
-                                 list(rec.views) if rec.views else [(rec.h0, rec.w0, 0)]))
+                                 list(rec.views) if rec.views else [(rec.h0, rec.w0, 0)], inst, rec.imap if self.inst_k else None))
         return out
 
     def detect(self, frames_u8):

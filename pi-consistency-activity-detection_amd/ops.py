@@ -726,6 +726,44 @@ def decode_detect_records(rec):
     return r[:, 0].copy(), r[:, 1:5].copy(), r[:, 5].copy().view(np.float32), r[:, 6].copy()
 
 
+INST_HDR, INST_WORDS = 4, 6                # a pc_frame_instances record: n_comp, kept, n_runs, flags, then K slots of area, x0, y0, x1, y1, first
+INST_MAX_RUNS, INST_MAX_ROWS = 2048, 2048  # PC_INST_MAX_RUNS / PC_INST_MAX_ROWS of include/picons.h
+INST_MAX_K = 32
+
+
+def frame_instances(mask, f0=0, nf=None, conn=8, min_area=1, K=8, inst=None, imap=None, want_imap=True):
+    """pc_frame_instances: mask contiguous uint8 device [F,H,W] (any non-zero byte is foreground) -> (inst int32 [F, 4 + 6K], imap uint8 [F,H,W]
+    or None): the connected components (conn 4 or 8) of the frames f0 .. f0 + nf - 1 (default: all from f0 on), ranked by area.  Given tensors
+    are written in place -- only those frames -- fresh ones are zero-filled first.  want_imap=False with imap=None: records only."""
+    if mask.dtype != torch.uint8 or mask.dim() != 3 or not mask.is_contiguous():
+        raise ValueError("frame_instances: contiguous uint8 [F,H,W] mask")
+    F, H, W = (int(v) for v in mask.shape)
+    K = int(K)
+    if not 1 <= K <= INST_MAX_K:
+        raise ValueError("frame_instances: K = %d outside 1..%d" % (K, INST_MAX_K))
+    words = INST_HDR + K * INST_WORDS
+    nf = F - int(f0) if nf is None else int(nf)
+    if inst is None:
+        inst = torch.zeros(F, words, dtype=torch.int32, device=mask.device)
+    elif inst.dtype != torch.int32 or not inst.is_contiguous() or inst.numel() != F * words or inst.device != mask.device:
+        raise ValueError("frame_instances: inst must be a contiguous int32 device tensor [F, %d]" % words)
+    if imap is None and want_imap:
+        imap = torch.zeros(F, H, W, dtype=torch.uint8, device=mask.device)
+    if imap is not None and (imap.dtype != torch.uint8 or not imap.is_contiguous() or imap.numel() != F * H * W or imap.device != mask.device):
+        raise ValueError("frame_instances: imap must be a contiguous uint8 device tensor [F,H,W]")
+    capi.call("pc_frame_instances", ptr(mask), F, H, W, int(f0), nf, int(conn), int(min_area), K, ptr(inst), ptr(imap), stream())
+    return inst, imap
+
+
+def decode_instances(words, K):
+    """Host int32 [F, 4 + 6K] records (numpy or torch) -> (n_comp int32 [F], kept int32 [F], n_runs int32 [F], flags int32 [F], areas int32 [F,K],
+    boxes int32 [F,K,4] = x0, y0, x1, y1, first int32 [F,K])."""
+    K = int(K)
+    r = np.ascontiguousarray(words.cpu().numpy() if torch.is_tensor(words) else words, dtype=np.int32).reshape(-1, INST_HDR + K * INST_WORDS)
+    slots = r[:, INST_HDR:].reshape(-1, K, INST_WORDS)
+    return r[:, 0].copy(), r[:, 1].copy(), r[:, 2].copy(), r[:, 3].copy(), slots[:, :, 0].copy(), slots[:, :, 1:5].copy(), slots[:, :, 5].copy()
+
+
 def video_class(scores, out=None):
     """pc_video_class: scores contiguous float32 device [n,C] -> float32 device [C + 2]: mean class scores, arg-max (as a float), its mean."""
     if scores.dtype != torch.float32 or scores.dim() != 2 or not scores.is_contiguous():

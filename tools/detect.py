@@ -8,9 +8,13 @@ half-open, full-frame coordinates), frame_scores_i [F], tubes_i [T,3] = (t0, t1 
 the uint8 masks [F,H,W] (mask_shape_i to unpack them).  --tile: the whole frame instead of its centre crop, as overlapping hw x hw tiles
 whose logits are averaged per pixel; --flip: every crop also mirrored left-right, the two maps averaged (bs should be a multiple of the views
 per clip, e.g. --bs 16 for the 8 views of a 240 x 320 frame with both).  tile, flip and views_i [V,3] = (h0, w0, flip) are recorded.
+--instances K (implies masks on the device): per frame the K largest connected components (--conn 4 | 8) of at least --min_area pixels, as
+inst_n_i [F], inst_kept_i [F], inst_flags_i [F], inst_areas_i [F,K], inst_boxes_i [F,K,4], inst_first_i [F,K] and the per-actor tubes
+inst_tubes_i [T,3] = (t0, t1 inclusive, score) with inst_tube_boxes_i [sum of the tubes' lengths, 4] one tube after the other; with
+--instance_maps also imap_i, the uint8 map of ranks [F,H,W] as it is (imap_shape_i).
 
     python tools/detect.py --out detections.npz [--ckpt best_model.pth] [--synthetic 4 | video.npy ...] [--masks] [--pack] [--tile] [--flip]
-                           [--max-gap 0] [--min-pixels 1]
+                           [--max-gap 0] [--min-pixels 1] [--instances K] [--min_area 1] [--conn 8] [--instance_maps]
 """
 import argparse
 import os
@@ -39,6 +43,10 @@ def main():
     ap.add_argument("--flip", action="store_true", help="every crop also mirrored left-right")
     ap.add_argument("--min-pixels", type=int, default=1)
     ap.add_argument("--max-gap", type=int, default=0)
+    ap.add_argument("--instances", type=int, default=0, help="per frame the K largest connected components of the mask (pc_frame_instances)")
+    ap.add_argument("--min_area", type=int, default=1)
+    ap.add_argument("--conn", type=int, default=8, choices=(4, 8))
+    ap.add_argument("--instance_maps", action="store_true", help="with --instances: also the uint8 map of ranks per frame")
     a = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("tools/detect.py needs a GPU: the hot path is HIP-only (no CPU fallback)")
@@ -55,7 +63,8 @@ def main():
         n = a.synthetic or 4
         videos = [v[0] for v in synthetic.make_eval_videos_u8(n, num_classes=a.classes, hw=a.hw)]
         names = ["synthetic_%d" % i for i in range(n)]
-    engine = detect.DetectEngine(bs=a.bs, hw=a.hw, num_classes=a.classes, state=state, pack=a.pack, masks=a.masks, tile=a.tile, flip=a.flip)
+    engine = detect.DetectEngine(bs=a.bs, hw=a.hw, num_classes=a.classes, state=state, pack=a.pack, masks=a.masks or a.instances > 0, tile=a.tile,
+                                 flip=a.flip, instances=a.instances, min_area=a.min_area, conn=a.conn, instance_maps=a.instance_maps)
     engine.begin()
     for v in videos:
         engine.add_video(v)
@@ -68,9 +77,21 @@ def main():
         if a.masks:
             m = d.masks.cpu().numpy()
             out.update({"masks_%d" % i: np.packbits(m), "mask_shape_%d" % i: np.array(m.shape, np.int64)})
-        print("%s: %d frames, class %d (%.4f), %d frames detected, %d tube(s)%s" % (
+        itubes = []
+        if a.instances:
+            itubes = d.instance_tubes(max_gap=a.max_gap)
+            out.update({"inst_n_%d" % i: d.inst_n, "inst_kept_%d" % i: d.inst_kept, "inst_flags_%d" % i: d.inst_flags, "inst_areas_%d" % i: d.inst_areas,
+                        "inst_boxes_%d" % i: d.inst_boxes, "inst_first_%d" % i: d.inst_first,
+                        "inst_tubes_%d" % i: np.array([(t0, t1, s) for t0, t1, _b, _a, s in itubes], np.float64).reshape(-1, 3),
+                        "inst_tube_boxes_%d" % i: np.concatenate([t[2] for t in itubes] + [np.zeros((0, 4), np.int32)]).astype(np.int32)})
+            if d.imap is not None:
+                m = d.imap.cpu().numpy()
+                out.update({"imap_%d" % i: m, "imap_shape_%d" % i: np.array(m.shape, np.int64)})
+        print("%s: %d frames, class %d (%.4f), %d frames detected, %d tube(s)%s%s" % (
             name, d.counts.size, d.label, d.class_score, int((d.counts >= a.min_pixels).sum()), len(tubes),
-            "".join("  [%d..%d] %.3f" % (t0, t1, s) for t0, t1, _b, s in tubes[:4])))
+            "".join("  [%d..%d] %.3f" % (t0, t1, s) for t0, t1, _b, s in tubes[:4]),
+            "; %d instances in %d instance tube(s), %d frame(s) over the run cap" % (int(d.inst_kept.sum()), len(itubes), int((d.inst_flags & 1).sum()))
+            if a.instances else ""))
     os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
     np.savez_compressed(a.out, **out)
     print("wrote %s (%d videos, %d clips)" % (a.out, len(names), engine.n_clips))
