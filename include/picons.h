@@ -67,7 +67,7 @@ typedef void* pc_stream;            /* hipStream_t */
  * 106: pc_truth_frame_flags / pc_eval_clips_from_u8 / pc_video_vote;
  * 107: pc_clips_from_u8 / pc_detect_frames / pc_detect_frames_ws_bytes / pc_video_class; the entries pc_clips_from_u8_views / pc_detect_frames_views /
  * pc_detect_frames_views_ws_bytes came later and move nothing: no struct grew, no op's operands changed; so did pc_frame_instances with its
- * PC_INST_* constants: came later, moves nothing).  Descriptors must be zero-initialised by the caller:
+ * PC_INST_* constants, and pc_frame_probs / pc_instance_scores with PC_PROB_ONE / PC_SCORE_WORDS: came later, move nothing).  Descriptors must be zero-initialised by the caller:
  * fields added later read as "old behaviour" when 0.  pc_version() returns the value the library was built with; the Python host
  * (capi.lib()) refuses a library whose version differs from the header it mirrors. */
 #define PC_VERSION 107
@@ -474,6 +474,26 @@ int     pc_detect_frames_views(const float* logits, int F, int H, int W, int S, 
 #define PC_INST_MAX_ROWS 2048
 int     pc_frame_instances(const uint8_t* mask, int F, int H, int W, int f0, int nf, int conn, int min_area, int K, int32_t* inst,
                            uint8_t* imap, pc_stream s);
+/* A confidence per instance (csrc/detect.hip, csrc/instances.hip; picons_amd/detect.py: DetectEngine(instance_scores=True)).
+ * pc_frame_probs: the per-pixel probability in video order.  Geometry arguments, frame rules (f >= F neither read nor written, a frame the
+ * launch does not address untouched, nothing to zero in front of it) and the merged logit m of a full-frame pixel are pc_detect_frames_views'
+ * -- one device function (csrc/viewmerge.h) serves both kernels; the centre crop is the one view (h0, w0, 0) at stride n.  For every addressed
+ * frame f < F the launch writes the WHOLE frame of `prob` uint16 [F][H][W]: q = __float2uint_rn(p * 65535.0f) with the fp32
+ * p = 1 / (1 + expf(-m)), the expression the frame score sums; q = 0 for a pixel no view covers and for a NaN m.  So m = +-0.0 gives 32768,
+ * +80 and +inf give PC_PROB_ONE, -80 and -inf give 0.  Grid and four-pixel groups of pc_detect_frames_views; no atomics, no LDS, no
+ * workspace.  Refusals (PC_E_ARG before any HIP call): pc_detect_frames_views' list without row0 / rec / ws, a null prob, a prob that is not
+ * 2-byte aligned.
+ * pc_instance_scores: imap uint8 [F][H][W] as pc_frame_instances leaves it and prob as above (frames at any byte / element address) -> for
+ * each of the frames f0 .. f0 + nf - 1, and no others, the WHOLE record of `out` int32 [F][PC_SCORE_WORDS * (K + 1)]: slot j = (lo, hi, npix),
+ * the unsigned 64-bit sum of q over the slot's pixels and their number.  Slot r < K takes the pixels with map value r + 1, slot K every other
+ * non-zero value (255, and any in K + 1 .. 254); the prob of a pixel with map value 0 is not read.  One 256-thread block per frame, integer
+ * LDS atomics only: bit-identical from run to run, nothing to zero.  Refusals (PC_E_ARG before any HIP call): null imap / prob / out; F, H,
+ * W < 1; H * W >= 2^31; f0 < 0, nf < 1, f0 + nf > F; K outside 1..32; prob not 2-byte or out not 4-byte aligned. */
+#define PC_PROB_ONE    65535
+#define PC_SCORE_WORDS 3
+int     pc_frame_probs(const float* logits, int F, int H, int W, int S, const int32_t* views, int V, int view_stride, const int32_t* starts,
+                       int n, int f_skip, uint16_t* prob, pc_stream s);
+int     pc_instance_scores(const uint8_t* imap, const uint16_t* prob, int F, int H, int W, int f0, int nf, int K, int32_t* out, pc_stream s);
 /* cv2.resize on uint8 images [n][H][W][C] -> [n][Ho][Wo][C] (C <= 4), the calls of the reference's loaders:
  * datasets/jhmdb_dataloader.py:252 (frames, INTER_AREA 320x240 -> 256x256), :267,:281 (puppet masks, INTER_NEAREST),
  * :192,:208 and ucf_dataloader.py:165,171 (224 crop -> frame size, INTER_LINEAR; the identity at 224).  OpenCV's 8-bit

@@ -5,7 +5,9 @@
 //                      video-order uint8 masks (full frames, margin included) and one 8-word record per frame (count, box, score, row);
 //                      HBM-bound, 4 bytes read per crop pixel and 1 written per frame pixel
 //   pc_video_class     mean class scores, their arg-max and its score: pc_video_vote's reduction, returned instead of compared
-//   pc_detect_frames_views   pc_detect_frames with the logits of V views merged per full-frame pixel in front of it (end of this file)
+//   pc_detect_frames_views   pc_detect_frames with the logits of V views merged per full-frame pixel in front of it (below)
+//   pc_frame_probs     the per-pixel probability of the merged logit as uint16 in video order, for pc_instance_scores (end of this file);
+//                      its merge is the views kernel's own (viewmerge.h: merge_group4's), no records, no workspace
 // Two traversal kernels (detect_frames_kernel walks the crop's float4 and then the margin, detect_frames_views_kernel the full frame in
 // groups of four: another memory traffic and another order of the sums), one end (block_partial), one records kernel, one set of argument
 // checks (detect_args) on the geometry of clipgeom.h.
@@ -15,6 +17,7 @@
 #include "common.h"
 #include "evalpred.h"
 #include "clipgeom.h"
+#include "viewmerge.h"
 
 namespace {
 
@@ -160,21 +163,23 @@ extern "C" int64_t pc_detect_frames_ws_bytes(int n, int S) {
     return (int64_t)n * 8 * det_bpf(S) * (int64_t)sizeof(Partial);
 }
 
-// The checks pc_detect_frames and pc_detect_frames_views share, in the order they refuse; `who` names the entry in the messages.  crop: the
-// (h0, w0) of the centre entry, which is the one view (h0, w0, 0) at stride n, or null for the entry that takes a view table.
-static int detect_args(DetectK& k, const char* who, const float* logits, int F, int H, int W, int S, const int32_t* crop, const int32_t* views,
-                       int V, int view_stride, const int32_t* starts, int n, int f_skip, int row0, uint8_t* mask, int32_t* rec, void* ws) {
-    PC_CHECK_ARG(logits && views && starts && rec && ws, "%s: null pointer", who);
-    if (int rc = geom_shape(k.g, who, F, H, W, S, crop)) return rc;
+// The checks pc_detect_frames, pc_detect_frames_views and pc_frame_probs share, in the order they refuse; `who` names the entry in the messages.
+// crop: the (h0, w0) of the centre entry, which is the one view (h0, w0, 0) at stride n, or null for an entry that takes a view table.  The
+// record entries write rec through ws from row0 on; pc_frame_probs (probs) writes prob alone and has none of the three.
+static int detect_args(ClipGeom& g, const char* who, const float* logits, int F, int H, int W, int S, const int32_t* crop, const int32_t* views,
+                       int V, int view_stride, const int32_t* starts, int n, int f_skip, int row0, const void* rec, const void* ws, bool probs = false,
+                       const void* prob = nullptr) {
+    PC_CHECK_ARG(logits && views && starts && (probs ? prob != nullptr : rec && ws), "%s: null pointer", who);
+    if (int rc = geom_shape(g, who, F, H, W, S, crop)) return rc;
     PC_CHECK_ARG((int64_t)H * W < (1ll << 31), "%s: frames of %d x %d pixels are outside the 2^31 a frame may hold", who, H, W);
     PC_CHECK_ARG(S % 4 == 0, "%s: S = %d must be a multiple of 4", who, S);
-    if (int rc = geom_counts(k.g, who, V, n, view_stride, f_skip)) return rc;
-    PC_CHECK_ARG(row0 >= 0 && row0 <= 0x7fffffff - MAX_CLIPS * (crop ? 1 : MAX_VIEWS), "%s: row0 = %d", who, row0);
+    if (int rc = geom_counts(g, who, V, n, view_stride, f_skip)) return rc;
+    PC_CHECK_ARG(probs || (row0 >= 0 && row0 <= 0x7fffffff - MAX_CLIPS * (crop ? 1 : MAX_VIEWS)), "%s: row0 = %d", who, row0);
     PC_CHECK_ARG((uintptr_t)logits % 16 == 0, "%s: logits must be 16-byte aligned", who);
-    PC_CHECK_ARG(((uintptr_t)ws % 8 == 0) && ((uintptr_t)rec % 4 == 0), "%s: ws must be 8-byte and rec 4-byte aligned", who);
-    if (int rc = geom_views(k.g, who, views)) return rc;
-    if (int rc = geom_starts(k.g, who, starts)) return rc;
-    k.logits = logits; k.mask = mask; k.rec = rec; k.part = (Partial*)ws; k.row0 = row0;
+    PC_CHECK_ARG(probs || (((uintptr_t)ws % 8 == 0) && ((uintptr_t)rec % 4 == 0)), "%s: ws must be 8-byte and rec 4-byte aligned", who);
+    PC_CHECK_ARG(!probs || (uintptr_t)prob % 2 == 0, "%s: prob must be 2-byte aligned", who);
+    if (int rc = geom_views(g, who, views)) return rc;
+    if (int rc = geom_starts(g, who, starts)) return rc;
     return PC_OK;
 }
 
@@ -182,7 +187,8 @@ extern "C" int pc_detect_frames(const float* logits, int F, int H, int W, int h0
                                 int row0, uint8_t* mask, int32_t* rec, void* ws, pc_stream s_) {
     const int32_t view[3] = {h0, w0, 0};
     DetectK k;
-    if (int rc = detect_args(k, "pc_detect_frames", logits, F, H, W, S, view, view, 1, n, starts, n, f_skip, row0, mask, rec, ws)) return rc;
+    if (int rc = detect_args(k.g, "pc_detect_frames", logits, F, H, W, S, view, view, 1, n, starts, n, f_skip, row0, rec, ws)) return rc;
+    k.logits = logits; k.mask = mask; k.rec = rec; k.part = (Partial*)ws; k.row0 = row0;
     k.bpf = det_bpf(S);
     hipStream_t s = (hipStream_t)s_;
     hipLaunchKernelGGL(detect_frames_kernel, dim3((unsigned)k.bpf, (unsigned)(n * 8)), dim3(BT), 0, s, k);
@@ -223,9 +229,9 @@ __global__ __launch_bounds__(256) void detect_frames_views_kernel(const DetectK 
     const int c = blockIdx.y >> 3, k = blockIdx.y & 7;
     const int64_t f = (int64_t)g.starts[c] + (int64_t)k * g.f_skip;
     if (f >= g.F) return;                                            // a frame past the end: nothing read, nothing written
-    const int S = g.S, W = g.W;
+    const int W = g.W;
     const uint32_t HW = (uint32_t)g.H * (uint32_t)W, total4 = (HW + 3u) >> 2;
-    const size_t per = (size_t)S * S;
+    const size_t per = (size_t)g.S * g.S;
     const float* lp = p.logits + ((size_t)c * 8 + k) * per;          // view v: + v * view_stride * 8 * per
     const size_t vstep = (size_t)g.view_stride * 8 * per;
     uint8_t* mf = p.mask ? p.mask + (size_t)f * HW : nullptr;
@@ -233,43 +239,14 @@ __global__ __launch_bounds__(256) void detect_frames_views_kernel(const DetectK 
     int cnt = 0, x0 = 0x7fffffff, y0 = 0x7fffffff, x1 = -1, y1 = -1;
     for (uint32_t idx = blockIdx.x * BT + threadIdx.x; idx < total4; idx += (uint32_t)p.bpf * BT) {
         const uint32_t px = idx << 2;
-        const int ny = (int)(HW - px < 4u ? HW - px : 4u);           // pixels of the group inside the frame
-        const int gy = (int)(px / (uint32_t)W), gx = (int)(px - (uint32_t)gy * (uint32_t)W);
-        const bool row = ny == 4 && gx + 3 < W;                      // the group lies in one row
-        float acc[4] = {0.f, 0.f, 0.f, 0.f};
-        int num[4] = {0, 0, 0, 0};
-        for (int v = 0; v < g.V; ++v) {
-            const int h0 = g.vh0[v], w0 = g.vw0[v];
-            const bool flip = (g.flips >> v) & 1u;
-            const float* lv = lp + (size_t)v * vstep;
-            const int dy = gy - h0, dx = gx - w0;
-            if (row && dy >= 0 && dy < S && dx >= 0 && dx + 3 < S && (dx & 3) == 0) {
-                const f32x4 q = *(const f32x4*)(lv + (size_t)dy * S + (flip ? S - 4 - dx : dx));
-#pragma unroll
-                for (int e = 0; e < 4; ++e) {
-                    const float t = flip ? q[3 - e] : q[e];
-                    acc[e] = num[e] ? __fadd_rn(acc[e], t) : t;
-                    ++num[e];
-                }
-                continue;
-            }
-#pragma unroll
-            for (int e = 0; e < 4; ++e) {
-                int y = gy, x = gx + e;
-                if (x >= W) { x -= W; ++y; if (x >= W) { x -= W; ++y; if (x >= W) { x -= W; ++y; } } }     // W >= 1: at most three rows on
-                const int ey = y - h0, ex = x - w0;
-                if (e < ny && ey >= 0 && ey < S && ex >= 0 && ex < S) {
-                    const float t = lv[(size_t)ey * S + (flip ? S - 1 - ex : ex)];
-                    acc[e] = num[e] ? __fadd_rn(acc[e], t) : t;
-                    ++num[e];
-                }
-            }
-        }
+        float mg[4];
+        int num[4], gy, gx;
+        const int ny = merge_group4(g, lp, vstep, px, HW, gy, gx, mg, num);
         uint32_t bits = 0;
 #pragma unroll
         for (int e = 0; e < 4; ++e) {
             if (num[e] == 0) continue;                               // no view covers the pixel: background
-            const float m = num[e] > 1 ? __fdiv_rn(acc[e], (float)num[e]) : acc[e];
+            const float m = mg[e];
             if (seg_positive(m)) {
                 int y = gy, x = gx + e;
                 if (x >= W) { x -= W; ++y; if (x >= W) { x -= W; ++y; if (x >= W) { x -= W; ++y; } } }
@@ -304,11 +281,72 @@ extern "C" int pc_detect_frames_views(const float* logits, int F, int H, int W, 
                                       const int32_t* starts, int n, int f_skip, int row0, uint8_t* mask, int32_t* rec, void* ws, pc_stream s_) {
     const char* who = "pc_detect_frames_views";
     DetectK k;
-    if (int rc = detect_args(k, who, logits, F, H, W, S, nullptr, views, V, view_stride, starts, n, f_skip, row0, mask, rec, ws)) return rc;
+    if (int rc = detect_args(k.g, who, logits, F, H, W, S, nullptr, views, V, view_stride, starts, n, f_skip, row0, rec, ws)) return rc;
+    k.logits = logits; k.mask = mask; k.rec = rec; k.part = (Partial*)ws; k.row0 = row0;
     k.bpf = det_views_bpf((int64_t)H * W);
     hipStream_t s = (hipStream_t)s_;
     hipLaunchKernelGGL(detect_frames_views_kernel, dim3((unsigned)k.bpf, (unsigned)(n * 8)), dim3(BT), 0, s, k);
     hipLaunchKernelGGL(detect_records_kernel, dim3((unsigned)cdiv(n * 8, BT)), dim3(BT), 0, s, k, n * 8, 0, 0, V);
+    PC_CHECK_LAUNCH(who);
+    return PC_OK;
+}
+
+// ---------------------------------------------------------------------- the probability map (detect.DetectEngine, instance_scores)
+//   pc_frame_probs   the per-pixel probability of the merged logit in video order: what the frame score sums, kept as uint16 so that
+//                    pc_instance_scores (instances.hip) can reduce it per instance behind the video's last clip.  The merged logit is
+//                    merge_group4's, the one the mask was thresholded on.  Reads logits the detect launch in front of it has just read
+//                    (cache-resident), writes 2 bytes per frame pixel.  No atomics, no LDS, no workspace.
+namespace {
+
+struct ProbK {
+    const float* logits; uint16_t* prob;
+    int bpf;
+    ClipGeom g;
+};
+
+// grid (bpf, n * 8) and the groups of four of detect_frames_views_kernel.  A group's four values go out as one 8-byte store where the address
+// allows (a frame of odd H * W starts at an odd element), as 2-byte stores otherwise; a group that crosses the frame's end writes its ny.
+__global__ __launch_bounds__(256) void frame_probs_kernel(const ProbK p) {
+    const ClipGeom& g = p.g;
+    const int c = blockIdx.y >> 3, k = blockIdx.y & 7;
+    const int64_t f = (int64_t)g.starts[c] + (int64_t)k * g.f_skip;
+    if (f >= g.F) return;                                            // a frame past the end: nothing read, nothing written
+    const uint32_t HW = (uint32_t)g.H * (uint32_t)g.W, total4 = (HW + 3u) >> 2;
+    const size_t per = (size_t)g.S * g.S;
+    const float* lp = p.logits + ((size_t)c * 8 + k) * per;          // view v: + v * view_stride * 8 * per
+    const size_t vstep = (size_t)g.view_stride * 8 * per;
+    uint16_t* pf = p.prob + (size_t)f * HW;
+    for (uint32_t idx = blockIdx.x * BT + threadIdx.x; idx < total4; idx += (uint32_t)p.bpf * BT) {
+        const uint32_t px = idx << 2;
+        float mg[4];
+        int num[4], gy, gx;
+        const int ny = merge_group4(g, lp, vstep, px, HW, gy, gx, mg, num);
+        uint32_t q[4];
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+            const float m = mg[e];
+            // no view covers the pixel, or a NaN: 0, written as such and not left to the conversion
+            q[e] = (num[e] == 0 || m != m) ? 0u : __float2uint_rn((1.0f / (1.0f + expf(-m))) * (float)PC_PROB_ONE);
+        }
+        uint16_t* o = pf + px;
+        if (ny == 4 && ((uintptr_t)o & 7) == 0) {
+            *(uint2*)o = make_uint2(q[0] | (q[1] << 16), q[2] | (q[3] << 16));
+        } else {
+            for (int e = 0; e < ny; ++e) o[e] = (uint16_t)q[e];
+        }
+    }
+}
+
+}  // namespace
+
+extern "C" int pc_frame_probs(const float* logits, int F, int H, int W, int S, const int32_t* views, int V, int view_stride,
+                              const int32_t* starts, int n, int f_skip, uint16_t* prob, pc_stream s) {
+    const char* who = "pc_frame_probs";
+    ProbK k;
+    if (int rc = detect_args(k.g, who, logits, F, H, W, S, nullptr, views, V, view_stride, starts, n, f_skip, 0, nullptr, nullptr, true, prob)) return rc;
+    k.logits = logits; k.prob = prob;
+    k.bpf = det_views_bpf((int64_t)H * W);
+    hipLaunchKernelGGL(frame_probs_kernel, dim3((unsigned)k.bpf, (unsigned)(n * 8)), dim3(BT), 0, (hipStream_t)s, k);
     PC_CHECK_LAUNCH(who);
     return PC_OK;
 }

@@ -40,19 +40,29 @@ __device__ __forceinline__ int lanes_below(unsigned long long m) {
     return (int)__builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u));
 }
 
-// four pixels at q as bits 0..3 (non-zero byte = foreground); the first n (0..4) of them count, q itself must be a byte of the mask even for
-// n = 0.  A frame starts at any byte address when W is odd, so the four bytes come out of the one or two ALIGNED dwords that hold them -- the
-// second is fetched only if it holds one of the n bytes, so every dword read holds a byte of the mask and lies in its allocation -- and there is
+// bytes4: the four bytes at q, of which the first n (0..4) are wanted (the others hold whatever lies there); fg_bits: four pixels at q as bits
+// 0..3 (non-zero byte = foreground), the first n of them count.  q itself must be a byte of the mask even for n = 0.  A frame starts at any
+// byte address when W is odd, so the four bytes come out of the one or two ALIGNED dwords that hold them -- the second is fetched only if it holds one of the n bytes, so every dword read holds a byte of the mask and lies in its allocation -- and there is
 // no branch around the loads: a caller's loads for several rows are all issued before the first is waited for.
-__device__ __forceinline__ uint32_t fg_bits(const uint8_t* q, int n) {
+__device__ __forceinline__ uint32_t bytes4(const uint8_t* q, int n) {
     const uintptr_t a = (uintptr_t)q;
     const int sh = (int)(a & 3);
     const uint32_t* p0 = (const uint32_t*)(a - sh);
     const uint32_t* p1 = (4 - sh < n) ? p0 + 1 : p0;
     const uint32_t w0 = *p0, w1 = *p1;
-    const uint32_t v = (uint32_t)((((unsigned long long)w1 << 32) | w0) >> (8 * sh));
+    return (uint32_t)((((unsigned long long)w1 << 32) | w0) >> (8 * sh));
+}
+
+__device__ __forceinline__ uint32_t fg_bits(const uint8_t* q, int n) {
+    const uint32_t v = bytes4(q, n);
     const uint32_t b = ((v & 0xffu) ? 1u : 0u) | ((v & 0xff00u) ? 2u : 0u) | ((v & 0xff0000u) ? 4u : 0u) | ((v & 0xff000000u) ? 8u : 0u);
     return b & ((1u << n) - 1u);
+}
+
+// the four bytes themselves, the ones past the first n as zeros (pc_instance_scores: a map value, not a bit)
+__device__ __forceinline__ uint32_t map_bytes(const uint8_t* q, int n) {
+    const uint32_t v = bytes4(q, n);
+    return n >= 4 ? v : (v & ((1u << (8 * n)) - 1u));
 }
 
 // One wave walks ROWS rows at a time (rows y0, y0 + NW, ...: the wave's next ones) in segments of 256 pixels, four per lane; the loads of all
@@ -329,6 +339,104 @@ extern "C" int pc_frame_instances(const uint8_t* mask, int F, int H, int W, int 
     k.mask = mask; k.inst = inst; k.imap = imap;
     k.H = H; k.W = W; k.f0 = f0; k.conn = conn; k.min_area = min_area; k.K = K;
     hipLaunchKernelGGL(frame_instances_kernel, dim3((unsigned)nf), dim3(BT), 0, (hipStream_t)s, k);
+    PC_CHECK_LAUNCH(who);
+    return PC_OK;
+}
+
+// ---------------------------------------------------------------------- a confidence per instance (detect.DetectEngine, instance_scores)
+//   pc_instance_scores   the map of ranks pc_frame_instances leaves and the uint16 probability map pc_frame_probs (detect.hip) leaves, reduced
+//                        per instance: for every slot the 64-bit sum of its pixels' probabilities and their number.  One 256-thread block
+//                        per frame, latency-bound as the labelling is.  Integer addition only -- per-wave LDS bins, then folded -- so the
+//                        record is the same bits in whatever order the adds land; no global atomics, nothing to zero.
+namespace {
+
+constexpr int SWORDS = PC_SCORE_WORDS, MAXSLOTS = 32 + 1;            // K <= 32 ranks and the slot of all other foreground
+
+struct ScoreK {
+    const uint8_t* imap; const uint16_t* prob; int32_t* out;
+    int H, W, f0, K;
+};
+
+// grid (nf): block b is frame f0 + b.  A thread walks the frame's groups of four consecutive pixels (the loads of four groups in flight, as the
+// map's writer has them), keeps the sum and count of the slot it is in and flushes them into its wave's bins when the slot changes.  The
+// probability of a background pixel is never read: a group of four foreground pixels at an 8-byte address comes as one load, anything else
+// pixel by pixel.
+__global__ __launch_bounds__(256) void instance_scores_kernel(const ScoreK p) {
+    __shared__ unsigned long long bsum[NW][MAXSLOTS];
+    __shared__ int bcnt[NW][MAXSLOTS];
+    const int tid = threadIdx.x, wv = tid >> 6, K = p.K;
+    const uint32_t HW = (uint32_t)p.H * (uint32_t)p.W, total4 = (HW + 3u) >> 2;
+    const size_t f = (size_t)p.f0 + blockIdx.x;
+    const uint8_t* __restrict__ im = p.imap + f * HW;
+    const uint16_t* __restrict__ pf = p.prob + f * HW;
+    for (int t = tid; t < NW * MAXSLOTS; t += BT) { (&bsum[0][0])[t] = 0ull; (&bcnt[0][0])[t] = 0; }
+    __syncthreads();
+
+    int cur = -1, cnt = 0;                                           // the slot the thread is in; nothing to flush while cnt == 0
+    unsigned long long sum = 0ull;
+    for (uint32_t g0 = tid; g0 < total4; g0 += BT * 4) {
+        uint32_t vals[4];
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+            const uint32_t g = g0 + u * BT, px = g << 2;
+            const bool in = g < total4;
+            vals[u] = map_bytes(im + (in ? px : 0u), in ? (int)(HW - px < 4u ? HW - px : 4u) : 0);
+        }
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+            const uint32_t v4 = vals[u];
+            if (v4 == 0u) continue;                                  // background (or a group past the frame's end): nothing read
+            const uint32_t px = (g0 + u * BT) << 2;
+            const uint16_t* q = pf + px;
+            uint32_t qv[4] = {0u, 0u, 0u, 0u};
+            const bool all = (v4 & 0xffu) && (v4 & 0xff00u) && (v4 & 0xff0000u) && (v4 & 0xff000000u);      // then the group has four pixels
+            if (all && ((uintptr_t)q & 7) == 0) {
+                const uint2 w = *(const uint2*)q;
+                qv[0] = w.x & 0xffffu; qv[1] = w.x >> 16; qv[2] = w.y & 0xffffu; qv[3] = w.y >> 16;
+            } else {
+#pragma unroll
+                for (int e = 0; e < 4; ++e)
+                    if ((v4 >> (8 * e)) & 0xffu) qv[e] = q[e];
+            }
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+                const int v = (int)((v4 >> (8 * e)) & 0xffu);
+                if (v == 0) continue;
+                const int slot = v <= K ? v - 1 : K;
+                if (slot != cur) {
+                    if (cnt) { atomicAdd(&bsum[wv][cur], sum); atomicAdd(&bcnt[wv][cur], cnt); }
+                    cur = slot; sum = 0ull; cnt = 0;
+                }
+                sum += qv[e]; ++cnt;
+            }
+        }
+    }
+    if (cnt) { atomicAdd(&bsum[wv][cur], sum); atomicAdd(&bcnt[wv][cur], cnt); }
+    __syncthreads();
+    if (tid <= K) {
+        unsigned long long s = bsum[0][tid];
+        int n = bcnt[0][tid];
+#pragma unroll
+        for (int w = 1; w < NW; ++w) { s += bsum[w][tid]; n += bcnt[w][tid]; }
+        int32_t* o = p.out + (f * (size_t)(K + 1) + (size_t)tid) * SWORDS;
+        o[0] = (int32_t)(uint32_t)s; o[1] = (int32_t)(uint32_t)(s >> 32); o[2] = n;
+    }
+}
+
+}  // namespace
+
+extern "C" int pc_instance_scores(const uint8_t* imap, const uint16_t* prob, int F, int H, int W, int f0, int nf, int K, int32_t* out, pc_stream s) {
+    const char* who = "pc_instance_scores";
+    PC_CHECK_ARG(imap && prob && out, "%s: null pointer", who);
+    PC_CHECK_ARG(F >= 1 && H >= 1 && W >= 1, "%s: F = %d frames of %d x %d are outside what a map holds", who, F, H, W);
+    PC_CHECK_ARG((int64_t)H * W < (1ll << 31), "%s: frames of %d x %d pixels are beyond the 2^31 a frame may hold", who, H, W);
+    PC_CHECK_ARG(f0 >= 0 && nf >= 1 && (int64_t)f0 + nf <= F, "%s: frames f0 = %d, nf = %d outside the %d of the map", who, f0, nf, F);
+    PC_CHECK_ARG(K >= 1 && K <= 32, "%s: K = %d outside 1..32", who, K);
+    PC_CHECK_ARG((uintptr_t)prob % 2 == 0 && (uintptr_t)out % 4 == 0, "%s: prob must be 2-byte and out 4-byte aligned", who);
+    ScoreK k;
+    k.imap = imap; k.prob = prob; k.out = out;
+    k.H = H; k.W = W; k.f0 = f0; k.K = K;
+    hipLaunchKernelGGL(instance_scores_kernel, dim3((unsigned)nf), dim3(BT), 0, (hipStream_t)s, k);
     PC_CHECK_LAUNCH(who);
     return PC_OK;
 }

@@ -21,6 +21,11 @@ Instances.  One box per frame is stretched across the image by a single false-po
 With instances=K one pc_frame_instances launch per video, behind its last clip, splits every frame's mask into its connected components on the
 device and leaves the K largest per frame (area, box, first pixel) next to the records; link_instance_tubes links them across frames into
 per-actor tubes by box IoU.
+
+Instance scores.  With instance_scores=True one pc_frame_probs launch behind each pc_detect_frames* keeps the per-pixel probability of the
+merged logit (uint16, video order; the merge is one device function for mask and probability) until the video's last clip, where one
+pc_instance_scores launch behind pc_frame_instances reduces it per instance: every instance, and with it every per-actor tube, carries the mean
+probability of its own pixels instead of the frame's.
 """
 from types import SimpleNamespace
 
@@ -65,16 +70,16 @@ def box_iou(a, b):
     return inter / (float(a[2] - a[0]) * float(a[3] - a[1]) + float(b[2] - b[0]) * float(b[3] - b[1]) - inter)
 
 
-def link_instance_tubes(inst_kept, inst_boxes, inst_areas, frame_scores, iou_min=0.3, max_gap=0, min_len=1):
+def link_instance_tubes(inst_kept, inst_boxes, inst_areas, frame_scores, iou_min=0.3, max_gap=0, min_len=1, inst_scores=None):
     """Per-frame instances -> per-actor tubes, greedily and deterministically.  inst_kept [F], inst_boxes [F,K,4], inst_areas [F,K] as
     Detection holds them (rank order), frame_scores [F].  Frames are taken in order and the open tubes in the order they were opened: each
     tube takes the not-yet-taken instance of the frame with the highest box IoU against its last box, if that IoU >= iou_min (a tie goes to
     the lower rank); instances no tube took open new tubes in rank order.  A tube closes once it has gone unmatched for more than max_gap
     frames; a bridged frame carries an empty box and area 0.  Tubes with fewer than min_len detected frames are dropped.
     -> [(t0, t1, boxes[t1 - t0 + 1, 4], areas[t1 - t0 + 1], score)] in the order the tubes were opened, t1 inclusive (the last DETECTED frame),
-    score the float64 mean of frame_scores over the tube's detected frames.  A per-instance confidence is out of scope: the frame score is
-    the mean sigmoid over all of the frame's positive pixels, the views path never materialises the merged logits, and no kernel in front
-    of pc_frame_instances changes for it.  iou_min = 0.3 is an API default, not a measured quantity."""
+    score the float64 mean of frame_scores over the tube's detected frames -- or, with inst_scores [F,K] (Detection.inst_scores), the float64
+    mean of the scores of the tube's own instances over those frames; the linking is the same either way.  iou_min = 0.3 is an API default,
+    not a measured quantity."""
     kept = np.asarray(inst_kept).reshape(-1)
     F = kept.size
     if F == 0:
@@ -84,6 +89,10 @@ def link_instance_tubes(inst_kept, inst_boxes, inst_areas, frame_scores, iou_min
     scores = np.asarray(frame_scores, np.float64).reshape(-1)
     if not (areas.shape[1] == boxes.shape[1] and scores.size == F) or kept.max() > boxes.shape[1]:
         raise ValueError("link_instance_tubes: %d frames, boxes %s, areas %s, %d scores" % (F, boxes.shape, areas.shape, scores.size))
+    if inst_scores is not None:
+        inst_scores = np.asarray(inst_scores, np.float64).reshape(F, -1)
+        if inst_scores.shape[1] != boxes.shape[1]:
+            raise ValueError("link_instance_tubes: inst_scores %s against boxes %s" % (inst_scores.shape, boxes.shape))
     if not 0.0 <= iou_min <= 1.0 or max_gap < 0 or min_len < 1:
         raise ValueError("link_instance_tubes: 0 <= iou_min <= 1, max_gap >= 0, min_len >= 1, got %r, %r, %r" % (iou_min, max_gap, min_len))
     tubes, live = [], []                                  # a tube: dict(t0, frames {t: rank}, last box, last t)
@@ -118,7 +127,9 @@ def link_instance_tubes(inst_kept, inst_boxes, inst_areas, frame_scores, iou_min
         bx, ar = np.zeros((t1 - t0 + 1, 4), boxes.dtype), np.zeros(t1 - t0 + 1, areas.dtype)
         for t, r in tb["frames"].items():
             bx[t - t0], ar[t - t0] = boxes[t, r], areas[t, r]
-        out.append((t0, t1, bx, ar, float(scores[sorted(tb["frames"])].mean())))
+        det = sorted(tb["frames"])
+        score = scores[det].mean() if inst_scores is None else inst_scores[det, [tb["frames"][t] for t in det]].mean()
+        out.append((t0, t1, bx, ar, float(score)))
     return out
 
 
@@ -165,13 +176,20 @@ class Detection:
     row runs than the kernel labels -- it then holds ONE instance, the frame's own count and box, with first = -1), inst_areas [F, K],
     inst_boxes [F, K, 4], inst_first [F, K] (y * W + x of the component's first pixel; zeros from inst_kept on), and imap: device uint8
     [F, H, W] with 0 background, r + 1 on the instance of rank r, 255 on other foreground (instance_maps=True), else None.  All None without
-    instances."""
+    instances.
 
-    def __init__(self, label, class_score, class_scores, counts, boxes, frame_scores, masks, views=None, inst=None, imap=None):
+    With DetectEngine(instance_scores=True) also inst_scores float64 [F, K], the mean probability over the instance's own pixels (zeros from
+    inst_kept on; the one instance of an overflow frame: over all of the frame's foreground), other_score float64 [F], that mean over the
+    foreground no kept instance holds (0 when there is none), and probs: the device 16-bit [F, H, W] probability map, uint16 steps of
+    1 / 65535.  All None without the option."""
+
+    def __init__(self, label, class_score, class_scores, counts, boxes, frame_scores, masks, views=None, inst=None, imap=None, scores=None, probs=None):
         self.label, self.class_score, self.class_scores = label, class_score, class_scores
         self.counts, self.boxes, self.frame_scores, self.masks, self.views = counts, boxes, frame_scores, masks, views
         self.inst_n, self.inst_kept, self.inst_flags, self.inst_areas, self.inst_boxes, self.inst_first = inst if inst is not None else (None,) * 6
         self.imap = imap
+        self.inst_scores, self.other_score = scores if scores is not None else (None, None)
+        self.probs = probs
 
     def tubes(self, min_pixels=1, max_gap=0):
         return link_tubes(self.counts, self.boxes, self.frame_scores, min_pixels, max_gap)
@@ -179,7 +197,7 @@ class Detection:
     def instance_tubes(self, iou_min=0.3, max_gap=0, min_len=1):
         if self.inst_kept is None:
             raise ValueError("instance_tubes: the detection holds no instances (DetectEngine(instances=K))")
-        return link_instance_tubes(self.inst_kept, self.inst_boxes, self.inst_areas, self.frame_scores, iou_min, max_gap, min_len)
+        return link_instance_tubes(self.inst_kept, self.inst_boxes, self.inst_areas, self.frame_scores, iou_min, max_gap, min_len, self.inst_scores)
 
 
 def check_instances(instances, min_area, conn, masks):
@@ -203,6 +221,23 @@ def substitute_overflow(counts, boxes, min_area, inst):
     return n, kept, flags, areas, ibox, first
 
 
+def score_instances(sums, npix, kept, flags):
+    """The decoded pc_instance_scores record of a video (sums int64 [F, K + 1], npix int32 [F, K + 1]) and its instance fields AFTER
+    substitute_overflow -> (inst_scores float64 [F, K], other_score float64 [F]): sum / (65535 * npix) for the ranks below kept, 0 from there
+    on; slot K's mean, 0 when it is empty.  A frame with the overflow flag holds all its foreground in slot K (its map is 255 throughout):
+    its one substituted instance takes that score."""
+    sums, npix = np.asarray(sums, np.int64), np.asarray(npix, np.int64)
+    F, K = sums.shape[0], sums.shape[1] - 1
+    mean = np.where(npix > 0, sums.astype(np.float64) / (float(ops.PROB_ONE) * np.maximum(npix, 1)), 0.0)
+    inst_scores, other = mean[:, :K].copy(), mean[:, K].copy()
+    kept = np.asarray(kept).reshape(F)
+    inst_scores[np.arange(K)[None, :] >= kept[:, None]] = 0.0
+    for f in np.flatnonzero(np.asarray(flags).reshape(F) & 1).tolist():
+        if kept[f]:
+            inst_scores[f, 0] = other[f]
+    return inst_scores, other
+
+
 class DetectEngine(ClipEngine):
     """Detects with the weights in the flat buffers P, R: a StepEngine's own (StepEngine.detect_engine: no copy, behind its lanes) or, built
     from a state dict, buffers of its own (load_state per checkpoint).
@@ -219,13 +254,22 @@ class DetectEngine(ClipEngine):
     instances=K > 0 (at most 32; needs masks): behind a video's last clip ONE pc_frame_instances launch over all its frames splits every mask
     into its connected components (conn 4 or 8) of at least min_area pixels and leaves the K largest per frame behind the class vector, so
     the one copy to the host takes them too; instance_maps=True also keeps the map of ranks on the device (Detection.imap).  instances=0:
-    nothing of this, today's path and buffer sizes."""
+    nothing of this, today's path and buffer sizes.
+
+    instance_scores=True (needs instances > 0): one pc_frame_probs launch behind every pc_detect_frames* keeps the per-pixel probability of
+    the video (16-bit [F,H,W], Detection.probs), one pc_instance_scores launch behind pc_frame_instances reduces it per instance into
+    F * 3 * (K + 1) words behind the instance records: Detection.inst_scores / other_score.  The map of ranks is then made whether or not
+    instance_maps asks for it.  False: nothing of this, no buffer and no launch."""
 
     def __init__(self, bs=14, hw=224, num_classes=24, device="cuda:0", state=None, engine=None, capacity=256, seed=47, f_skip=2, pack=False,
-                 masks=True, on_batch=None, tile=False, flip=False, views=None, instances=0, min_area=1, conn=8, instance_maps=False):
+                 masks=True, on_batch=None, tile=False, flip=False, views=None, instances=0, min_area=1, conn=8, instance_maps=False,
+                 instance_scores=False):
         hw = engine.hw if engine is not None else hw
         self.inst_k, self.min_area, self.conn = check_instances(instances, min_area, conn, masks)
         self.instance_maps = bool(instance_maps) and self.inst_k > 0
+        self.instance_scores = bool(instance_scores)
+        if self.instance_scores and self.inst_k == 0:
+            raise ValueError("DetectEngine: instance_scores=True needs instances > 0 (the scores are reduced over pc_frame_instances' map of ranks)")
         if hw % 4:
             raise ValueError("DetectEngine: hw = %d must be a multiple of 4 (pc_detect_frames reads the logit rows 16 bytes at a time)" % hw)
         self._setup(bs, hw, num_classes, device, state, engine, capacity, seed, f_skip, pack, on_batch)
@@ -301,9 +345,12 @@ class DetectEngine(ClipEngine):
         # so every mask byte and every record is written by a launch: nothing is filled.
         # With instances the F records of 4 + 6K words follow behind the class vector: the earlier offsets do not move.
         rec.inst_words = F * (ops.INST_HDR + self.inst_k * ops.INST_WORDS) if self.inst_k else 0
-        rec.dev = torch.empty(F * ops.DETECT_REC_WORDS + self.C + 2 + rec.inst_words, dtype=torch.int32, device=self.dev)
+        # With instance scores the F records of 3 (K + 1) words follow behind those.
+        rec.score_words = F * ops.SCORE_WORDS * (self.inst_k + 1) if self.instance_scores else 0
+        rec.dev = torch.empty(F * ops.DETECT_REC_WORDS + self.C + 2 + rec.inst_words + rec.score_words, dtype=torch.int32, device=self.dev)
         rec.mask = torch.empty(F, H, W, dtype=torch.uint8, device=self.dev) if self.masks else None
-        rec.imap = torch.empty(F, H, W, dtype=torch.uint8, device=self.dev) if self.instance_maps else None
+        rec.imap = torch.empty(F, H, W, dtype=torch.uint8, device=self.dev) if self.instance_maps or self.instance_scores else None
+        rec.prob = torch.empty(F, H, W, dtype=torch.int16, device=self.dev) if self.instance_scores else None
         rec.pin = None
         if views:
             need = ops.detect_frames_views_ws_bytes(min(self.bs, 32), H, W)
@@ -328,12 +375,18 @@ class DetectEngine(ClipEngine):
                 ops.detect_frames_views(self.out[(slot + q) * per:(slot + q + (V - 1) * n + k) * per].view(-1, 8, hw, hw), rec.views,
                                         rec.starts[first + q:first + q + k], rec.F, rec.H, rec.W, self.f_skip, view_stride=n, row0=rec.row0 + (first + q) * V,
                                         mask=rec.mask, rec=rec.dev[:rec.F * W8].view(rec.F, W8), ws=self.ws_views, want_mask=False)
+                if rec.prob is not None:
+                    ops.frame_probs(self.out[(slot + q) * per:(slot + q + (V - 1) * n + k) * per].view(-1, 8, hw, hw), rec.views,
+                                    rec.starts[first + q:first + q + k], rec.F, rec.H, rec.W, self.f_skip, view_stride=n, prob=rec.prob)
             return
         for q in range(0, n, 32):
             k = min(32, n - q)
             ops.detect_frames(self.out[(slot + q) * per:(slot + q + k) * per].view(k, 8, hw, hw), rec.starts[first + q:first + q + k], rec.F, rec.H, rec.W,
                               rec.h0, rec.w0, self.f_skip, row0=rec.row0 + first + q, mask=rec.mask, rec=rec.dev[:rec.F * W8].view(rec.F, W8), ws=self.ws,
                               want_mask=False)
+            if rec.prob is not None:
+                ops.frame_probs(self.out[(slot + q) * per:(slot + q + k) * per].view(k, 8, hw, hw), [(rec.h0, rec.w0, 0)], rec.starts[first + q:first + q + k],
+                                rec.F, rec.H, rec.W, self.f_skip, prob=rec.prob)
 
     def _finish(self, rec):
         """The video's class from its score rows, its instances from its masks (every frame has been written by now, on this stream); records,
@@ -341,8 +394,11 @@ class DetectEngine(ClipEngine):
         cls0 = rec.F * ops.DETECT_REC_WORDS
         ops.video_class(self.scores[rec.row0:rec.row0 + rec.rows], out=rec.dev[cls0:cls0 + self.C + 2].view(torch.float32))
         if self.inst_k:
-            ops.frame_instances(rec.mask, conn=self.conn, min_area=self.min_area, K=self.inst_k, inst=rec.dev[cls0 + self.C + 2:].view(rec.F, -1),
+            inst0 = cls0 + self.C + 2
+            ops.frame_instances(rec.mask, conn=self.conn, min_area=self.min_area, K=self.inst_k, inst=rec.dev[inst0:inst0 + rec.inst_words].view(rec.F, -1),
                                 imap=rec.imap, want_imap=False)
+            if rec.prob is not None:
+                ops.instance_scores(rec.imap, rec.prob, self.inst_k, out=rec.dev[inst0 + rec.inst_words:].view(rec.F, -1))
         rec.pin = self._stage(rec.dev.numel())
         rec.pin.copy_(rec.dev, non_blocking=True)
 
@@ -356,12 +412,16 @@ class DetectEngine(ClipEngine):
             counts, boxes, fscores, _rows = ops.decode_detect_records(words[:rec.F * ops.DETECT_REC_WORDS])
             cls0 = rec.F * ops.DETECT_REC_WORDS
             cls = words[cls0:cls0 + self.C + 2].copy().view(np.float32)
-            inst = None
+            inst = scores = None
             if self.inst_k:
-                n, kept, _runs, flags, areas, ibox, first = ops.decode_instances(words[cls0 + self.C + 2:], self.inst_k)
+                inst0 = cls0 + self.C + 2
+                n, kept, _runs, flags, areas, ibox, first = ops.decode_instances(words[inst0:inst0 + rec.inst_words], self.inst_k)
                 inst = substitute_overflow(counts, boxes, self.min_area, (n, kept, flags, areas, ibox, first))
+                if self.instance_scores:
+                    sums, npix = ops.decode_instance_scores(words[inst0 + rec.inst_words:], self.inst_k)
+                    scores = score_instances(sums, npix, inst[1], inst[2])
             out.append(Detection(int(cls[self.C]), float(cls[self.C + 1]), cls[:self.C].copy(), counts, boxes, fscores, rec.mask,
-                                 list(rec.views) if rec.views else [(rec.h0, rec.w0, 0)], inst, rec.imap if self.inst_k else None))
+                                 list(rec.views) if rec.views else [(rec.h0, rec.w0, 0)], inst, rec.imap if self.instance_maps else None, scores, rec.prob))
         return out
 
     def detect(self, frames_u8):

@@ -764,6 +764,70 @@ def decode_instances(words, K):
     return r[:, 0].copy(), r[:, 1].copy(), r[:, 2].copy(), r[:, 3].copy(), slots[:, :, 0].copy(), slots[:, :, 1:5].copy(), slots[:, :, 5].copy()
 
 
+PROB_ONE, SCORE_WORDS = 65535, 3           # PC_PROB_ONE / PC_SCORE_WORDS of include/picons.h: probability 1.0 as uint16; lo, hi, npix of a slot
+_PROB_DTYPES = tuple(d for d in (torch.int16, getattr(torch, "uint16", None)) if d is not None)
+
+
+def _prob_tensor(who, prob, F, H, W, dev):
+    """The probability map of frame_probs / instance_scores: a contiguous 16-bit integer device tensor [F,H,W], np.uint16 on the host
+    (prob.cpu().numpy().view(np.uint16)).  A missing one is made zero-filled (int16: the dtype every torch build can allocate and copy)."""
+    if prob is None:
+        return torch.zeros(F, H, W, dtype=torch.int16, device=dev)
+    if prob.dtype not in _PROB_DTYPES or not prob.is_contiguous() or prob.numel() != F * H * W or prob.device != dev:
+        raise ValueError("%s: prob must be a contiguous 16-bit integer device tensor [F,H,W]" % who)
+    return prob
+
+
+def frame_probs(logits, views, starts, F, H, W, f_skip=2, view_stride=None, prob=None):
+    """pc_frame_probs: the logits, views and starts of detect_frames_views (the centre crop: the one view (h0, w0, 0)) -> prob, 16-bit integer
+    device [F,H,W]: round(65535 * sigmoid(merged logit)) as uint16, 0 where no view covers the pixel.  A given tensor is written in place
+    -- only the frames the clips address -- a fresh one is zero-filled first."""
+    if logits.dtype != torch.float32 or not logits.is_contiguous():
+        raise ValueError("frame_probs: contiguous float32 logits")
+    tab, V = _view_table(views, "frame_probs")
+    st, n = _starts_table(starts)
+    S = int(logits.shape[-1])
+    stride = n if view_stride is None else int(view_stride)
+    if stride < n:
+        raise ValueError("frame_probs: view_stride = %d below the %d clips" % (stride, n))
+    if int(logits.shape[-2]) != S or logits.numel() < ((V - 1) * stride + n) * 8 * S * S:
+        raise ValueError("frame_probs: logits %s do not hold %d views of %d clips of 8 x %d x %d at stride %d" % (tuple(logits.shape), V, n, S, S, stride))
+    prob = _prob_tensor("frame_probs", prob, int(F), int(H), int(W), logits.device)
+    capi.call("pc_frame_probs", ptr(logits), int(F), int(H), int(W), S, tab, V, stride, st, n, int(f_skip), ptr(prob), stream())
+    return prob
+
+
+def instance_scores(imap, prob, K, f0=0, nf=None, out=None):
+    """pc_instance_scores: imap contiguous uint8 device [F,H,W] (frame_instances' map of ranks) and prob (frame_probs') -> out int32
+    [F, 3 * (K + 1)]: per slot the 64-bit sum of prob over its pixels as (lo, hi) and their number, for the frames f0 .. f0 + nf - 1
+    (default: all from f0 on).  A given out is written in place -- only those frames -- a fresh one is zero-filled first."""
+    if imap.dtype != torch.uint8 or imap.dim() != 3 or not imap.is_contiguous():
+        raise ValueError("instance_scores: contiguous uint8 [F,H,W] imap")
+    F, H, W = (int(v) for v in imap.shape)
+    K = int(K)
+    if not 1 <= K <= INST_MAX_K:
+        raise ValueError("instance_scores: K = %d outside 1..%d" % (K, INST_MAX_K))
+    if prob is None:
+        raise ValueError("instance_scores: prob is missing")
+    prob = _prob_tensor("instance_scores", prob, F, H, W, imap.device)
+    words = SCORE_WORDS * (K + 1)
+    nf = F - int(f0) if nf is None else int(nf)
+    if out is None:
+        out = torch.zeros(F, words, dtype=torch.int32, device=imap.device)
+    elif out.dtype != torch.int32 or not out.is_contiguous() or out.numel() != F * words or out.device != imap.device:
+        raise ValueError("instance_scores: out must be a contiguous int32 device tensor [F, %d]" % words)
+    capi.call("pc_instance_scores", ptr(imap), ptr(prob), F, H, W, int(f0), nf, K, ptr(out), stream())
+    return out
+
+
+def decode_instance_scores(words, K):
+    """Host int32 [F, 3 * (K + 1)] records (numpy or torch) -> (sums int64 [F, K + 1], npix int32 [F, K + 1]); slot K: all other foreground."""
+    K = int(K)
+    r = np.ascontiguousarray(words.cpu().numpy() if torch.is_tensor(words) else words, dtype=np.int32).reshape(-1, K + 1, SCORE_WORDS)
+    lo, hi = r[:, :, 0].astype(np.int64) & 0xffffffff, r[:, :, 1].astype(np.int64) & 0xffffffff
+    return (hi << 32) | lo, r[:, :, 2].copy()
+
+
 def video_class(scores, out=None):
     """pc_video_class: scores contiguous float32 device [n,C] -> float32 device [C + 2]: mean class scores, arg-max (as a float), its mean."""
     if scores.dtype != torch.float32 or scores.dim() != 2 or not scores.is_contiguous():

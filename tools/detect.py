@@ -12,9 +12,11 @@ per clip, e.g. --bs 16 for the 8 views of a 240 x 320 frame with both).  tile, f
 inst_n_i [F], inst_kept_i [F], inst_flags_i [F], inst_areas_i [F,K], inst_boxes_i [F,K,4], inst_first_i [F,K] and the per-actor tubes
 inst_tubes_i [T,3] = (t0, t1 inclusive, score) with inst_tube_boxes_i [sum of the tubes' lengths, 4] one tube after the other; with
 --instance_maps also imap_i, the uint8 map of ranks [F,H,W] as it is (imap_shape_i).
+--instance_scores (needs --instances K > 0): a confidence per instance, inst_scores_i [F,K] the mean probability over the instance's own pixels
+and other_score_i [F] that over the foreground no kept instance holds; the scores of inst_tubes_i are then the means of their own instances'.
 
     python tools/detect.py --out detections.npz [--ckpt best_model.pth] [--synthetic 4 | video.npy ...] [--masks] [--pack] [--tile] [--flip]
-                           [--max-gap 0] [--min-pixels 1] [--instances K] [--min_area 1] [--conn 8] [--instance_maps]
+                           [--max-gap 0] [--min-pixels 1] [--instances K] [--min_area 1] [--conn 8] [--instance_maps] [--instance_scores]
 """
 import argparse
 import os
@@ -47,7 +49,10 @@ def main():
     ap.add_argument("--min_area", type=int, default=1)
     ap.add_argument("--conn", type=int, default=8, choices=(4, 8))
     ap.add_argument("--instance_maps", action="store_true", help="with --instances: also the uint8 map of ranks per frame")
+    ap.add_argument("--instance_scores", action="store_true", help="with --instances: a confidence per instance and per instance tube")
     a = ap.parse_args()
+    if a.instance_scores and a.instances <= 0:
+        raise SystemExit("tools/detect.py: --instance_scores needs --instances K with K > 0 (the scores are reduced per instance)")
     if not torch.cuda.is_available():
         raise SystemExit("tools/detect.py needs a GPU: the hot path is HIP-only (no CPU fallback)")
     if a.ckpt:
@@ -64,7 +69,8 @@ def main():
         videos = [v[0] for v in synthetic.make_eval_videos_u8(n, num_classes=a.classes, hw=a.hw)]
         names = ["synthetic_%d" % i for i in range(n)]
     engine = detect.DetectEngine(bs=a.bs, hw=a.hw, num_classes=a.classes, state=state, pack=a.pack, masks=a.masks or a.instances > 0, tile=a.tile,
-                                 flip=a.flip, instances=a.instances, min_area=a.min_area, conn=a.conn, instance_maps=a.instance_maps)
+                                 flip=a.flip, instances=a.instances, min_area=a.min_area, conn=a.conn, instance_maps=a.instance_maps,
+                                 instance_scores=a.instance_scores)
     engine.begin()
     for v in videos:
         engine.add_video(v)
@@ -84,6 +90,8 @@ def main():
                         "inst_boxes_%d" % i: d.inst_boxes, "inst_first_%d" % i: d.inst_first,
                         "inst_tubes_%d" % i: np.array([(t0, t1, s) for t0, t1, _b, _a, s in itubes], np.float64).reshape(-1, 3),
                         "inst_tube_boxes_%d" % i: np.concatenate([t[2] for t in itubes] + [np.zeros((0, 4), np.int32)]).astype(np.int32)})
+            if d.inst_scores is not None:
+                out.update({"inst_scores_%d" % i: d.inst_scores, "other_score_%d" % i: d.other_score})
             if d.imap is not None:
                 m = d.imap.cpu().numpy()
                 out.update({"imap_%d" % i: m, "imap_shape_%d" % i: np.array(m.shape, np.int64)})
