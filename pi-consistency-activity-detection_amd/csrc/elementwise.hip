@@ -115,15 +115,13 @@ __global__ __launch_bounds__(256) void bn_apply_kernel(const float* __restrict__
 }
 
 // ------------------------------------------------------------------------------ column reductions
-// Generic per-channel reduction of two quantities over a block of rows.  MODE 0: BN backward
-// (sum dzh, sum dzh*xhat); MODE 1: activation backward (sum dz, unused).
+// Per-channel reduction of two quantities over a block of rows for the BatchNorm backward (sum dzh, sum dzh*xhat).
 struct RedP {
     const float* a; int lda; const float* b; int ldb; const float* stat; int C4; int64_t rows, rows_per_group;
     int64_t rows_per_block; int act; float* part;   // part [nblk][2][C]
     int64_t a_gs, b_gs, stat_gs, part_gs;           // blockIdx.y = batch group: element strides of a, b, stat, part (0 for one group)
 };
 
-template <int MODE>
 __global__ __launch_bounds__(256) void colreduce_kernel(RedP p) {
     p.a += blockIdx.y * p.a_gs; p.b += blockIdx.y * p.b_gs; p.stat += blockIdx.y * p.stat_gs; p.part += blockIdx.y * p.part_gs;
     const int C4 = p.C4, C = C4 * 4;
@@ -143,25 +141,15 @@ __global__ __launch_bounds__(256) void colreduce_kernel(RedP p) {
         for (int64_t r = r0 + rl; r < r1; r += rpi) {
             const f32x4 dy = *(const f32x4*)(p.a + r * p.lda + c);
             const f32x4 zz = *(const f32x4*)(p.b + r * p.ldb + c);
-            if (MODE == 0) {
-                const float* st = p.stat;              // one batch group per blockIdx.y (p.rows == p.rows_per_group)
-                const f32x4 mean = *(const f32x4*)(st + c), inv = *(const f32x4*)(st + C + c);
-                const f32x4 sc = *(const f32x4*)(st + 2 * C + c), sh_ = *(const f32x4*)(st + 3 * C + c);
+            const float* st = p.stat;                  // one batch group per blockIdx.y (p.rows == p.rows_per_group)
+            const f32x4 mean = *(const f32x4*)(st + c), inv = *(const f32x4*)(st + C + c);
+            const f32x4 sc = *(const f32x4*)(st + 2 * C + c), sh_ = *(const f32x4*)(st + 3 * C + c);
 #pragma unroll
-                for (int e = 0; e < 4; ++e) {
-                    const float yv = zz[e] * sc[e] + sh_[e];
-                    const float d = (p.act == PC_ACT_RELU && !(yv > 0.f)) ? 0.f : dy[e];
-                    s[e] += d;
-                    s[4 + e] += d * (zz[e] - mean[e]) * inv[e];
-                }
-            } else {
-#pragma unroll
-                for (int e = 0; e < 4; ++e) {
-                    float d = dy[e];
-                    if (p.act == PC_ACT_RELU) d = zz[e] > 0.f ? d : 0.f;
-                    else if (p.act == PC_ACT_SIGMOID) d = d * zz[e] * (1.f - zz[e]);
-                    s[e] += d;
-                }
+            for (int e = 0; e < 4; ++e) {
+                const float yv = zz[e] * sc[e] + sh_[e];
+                const float d = (p.act == PC_ACT_RELU && !(yv > 0.f)) ? 0.f : dy[e];
+                s[e] += d;
+                s[4 + e] += d * (zz[e] - mean[e]) * inv[e];
             }
             if (++run == 4) {
                 run = 0;
@@ -390,51 +378,161 @@ __global__ __launch_bounds__(FIN_T) void colsum_finalize_kernel(const float* __r
     if (rl == 0 && c < C) out[c] = (accum ? out[c] : 0.f) + (float)s;
 }
 
+__device__ __forceinline__ f32x4 act_bwd_of(const f32x4 d, const f32x4 yy, int act) {
+    f32x4 o;
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+        float v = d[e];
+        if (act == PC_ACT_RELU) v = yy[e] > 0.f ? v : 0.f;
+        else if (act == PC_ACT_SIGMOID) v = v * yy[e] * (1.f - yy[e]);
+        o[e] = v;
+    }
+    return o;
+}
+
 __global__ __launch_bounds__(256) void act_bwd_apply_kernel(const float* __restrict__ dy, int lddy, const float* __restrict__ y, int ldy,
                                                             int act, int C4, int64_t total4, float* __restrict__ dz, int lddz) {
     for (int64_t idx = (int64_t)blockIdx.x * 256 + threadIdx.x; idx < total4; idx += (int64_t)gridDim.x * 256) {
         const size_t row = (unsigned)idx / (unsigned)C4;
         const int c = (int)((unsigned)idx - (unsigned)row * C4) * 4;
         const f32x4 d = *(const f32x4*)(dy + row * lddy + c), yy = *(const f32x4*)(y + row * ldy + c);
-        f32x4 o;
+        *(f32x4*)(dz + row * lddz + c) = act_bwd_of(d, yy, act);
+    }
+}
+
+// Bias gradient and dz in ONE pass over (dy, y): partial column sums [nblk][2][C] (second half unused, as colsum_finalize_kernel reads them) and,
+// with WRITE, dz for every element read.  Block and thread partition, the runs of four rows flushed into double and the LDS combine are those of
+// colreduce_kernel, so the sums are the same bits whether dz is written or not; four rows are in flight per thread (eight 16-byte loads).
+// dz may be dy (each element is read and written by one thread, read first).
+template <bool WRITE>
+__global__ __launch_bounds__(256) void act_bwd_reduce_kernel(const float* dy, int lddy, const float* __restrict__ y, int ldy, int act, int C4, int64_t rows,
+                                                             int64_t rows_per_block, float* dz, int lddz, float* __restrict__ part) {
+    const int C = C4 * 4;
+    const int rpi = 256 / C4;                       // rows per iteration
+    const int c4 = threadIdx.x % C4, rl = threadIdx.x / C4;
+    const int64_t r0 = (int64_t)blockIdx.x * rows_per_block;
+    const int64_t r1 = min(rows, r0 + rows_per_block);
+    double sd[4] = {0, 0, 0, 0};
+    if (rl < rpi) {
+        const int c = c4 * 4;
+        int64_t r = r0 + rl;
+        for (; r + 3 * (int64_t)rpi < r1; r += 4 * (int64_t)rpi) {
+            f32x4 d[4], yy[4];
 #pragma unroll
-        for (int e = 0; e < 4; ++e) {
-            float v = d[e];
-            if (act == PC_ACT_RELU) v = yy[e] > 0.f ? v : 0.f;
-            else if (act == PC_ACT_SIGMOID) v = v * yy[e] * (1.f - yy[e]);
-            o[e] = v;
+            for (int u = 0; u < 4; ++u) {
+                d[u] = *(const f32x4*)(dy + (r + (int64_t)u * rpi) * lddy + c);
+                yy[u] = *(const f32x4*)(y + (r + (int64_t)u * rpi) * ldy + c);
+            }
+            float s[4] = {0, 0, 0, 0};
+#pragma unroll
+            for (int u = 0; u < 4; ++u) {
+                const f32x4 o = act_bwd_of(d[u], yy[u], act);
+                if (WRITE) *(f32x4*)(dz + (r + (int64_t)u * rpi) * lddz + c) = o;
+#pragma unroll
+                for (int e = 0; e < 4; ++e) s[e] += o[e];
+            }
+#pragma unroll
+            for (int e = 0; e < 4; ++e) sd[e] += (double)s[e];
         }
-        *(f32x4*)(dz + row * lddz + c) = o;
+        float s[4] = {0, 0, 0, 0};                  // the last, shorter run
+        for (; r < r1; r += rpi) {
+            const f32x4 o = act_bwd_of(*(const f32x4*)(dy + r * lddy + c), *(const f32x4*)(y + r * ldy + c), act);
+            if (WRITE) *(f32x4*)(dz + r * lddz + c) = o;
+#pragma unroll
+            for (int e = 0; e < 4; ++e) s[e] += o[e];
+        }
+#pragma unroll
+        for (int e = 0; e < 4; ++e) sd[e] += (double)s[e];
+    }
+    __shared__ double shd[256 * 4];
+#pragma unroll
+    for (int e = 0; e < 4; ++e) shd[threadIdx.x * 4 + e] = sd[e];
+    __syncthreads();
+    if (threadIdx.x < C4) {
+        double t[4] = {0, 0, 0, 0};
+        for (int q = 0; q < rpi; ++q)
+#pragma unroll
+            for (int e = 0; e < 4; ++e) t[e] += shd[(q * C4 + threadIdx.x) * 4 + e];
+        float* o = part + (size_t)blockIdx.x * 2 * C + threadIdx.x * 4;
+#pragma unroll
+        for (int e = 0; e < 4; ++e) { o[e] = (float)t[e]; o[C + e] = 0.f; }
     }
 }
 
 // ------------------------------------------------------------------------------ max pool
+// Work order of both directions: a block owns a contiguous run of `ppb` positions (output positions forward, input positions backward) with all
+// their channels, and the block that owns run i is the one whose xcd_remap id is i.  A line of the other tensor is needed by up to 27 positions
+// of neighbouring rows and planes; blocks that run at the same time on one XCD then sweep adjacent rows, and that XCD's L2 serves the overlap
+// (dealt out round-robin, the rows around a line ran on all eight XCDs, whose L2s are private).  The remap moves work between blocks and nothing else.
+// The windows the planner emits are compile-time forms <KT, KH, KW, ST, SH, SW>: the taps of one temporal plane are loaded together (clamped
+// addresses for the spatial padding, no load for a padded plane) and then compared / added in order.  KT = 0: any window, from the descriptor.
+constexpr int POOL_ITEMS = 1024;                    // float4 items per block: four per thread
+
+template <int KT, int KH, int KW, int ST, int SH, int SW>
 __global__ __launch_bounds__(256) void maxpool_fwd_kernel(const pc_pool_desc d, const float* __restrict__ x, float* __restrict__ y,
-                                                          uint8_t* __restrict__ am, int64_t total4) {
-    const int C4 = d.C / 4;
-    for (int64_t idx = (int64_t)blockIdx.x * 256 + threadIdx.x; idx < total4; idx += (int64_t)gridDim.x * 256) {
-        unsigned pos = (unsigned)idx / (unsigned)C4;
-        const int c = (int)((unsigned)idx - pos * C4) * 4;
+                                                          uint8_t* __restrict__ am, unsigned npos, unsigned ppb) {
+    const unsigned C4 = (unsigned)d.C / 4;
+    const unsigned p0 = (unsigned)xcd_remap((int)blockIdx.x, (int)gridDim.x) * ppb;
+    if (p0 >= npos) return;
+    const unsigned items = (min(npos, p0 + ppb) - p0) * C4;
+    for (unsigned i = threadIdx.x; i < items; i += 256) {
+        unsigned pos = p0 + i / C4;
+        const int c = (int)(i % C4) * 4;
         const size_t opos = pos;
         const int wo = (int)(pos % (unsigned)d.Wo); pos /= (unsigned)d.Wo;
         const int ho = (int)(pos % (unsigned)d.Ho); pos /= (unsigned)d.Ho;
         const int to = (int)(pos % (unsigned)d.To); const int n = (int)(pos / (unsigned)d.To);
         f32x4 best = {-INFINITY, -INFINITY, -INFINITY, -INFINITY};
         int bi[4] = {255, 255, 255, 255};
-        int tap = 0;
-        for (int a = 0; a < d.k[0]; ++a) {
-            const int t = to * d.s[0] - d.padf[0] + a;
-            for (int b = 0; b < d.k[1]; ++b) {
-                const int h = ho * d.s[1] - d.padf[1] + b;
-                for (int cc = 0; cc < d.k[2]; ++cc, ++tap) {
-                    const int w = wo * d.s[2] - d.padf[2] + cc;
-                    const bool inb = (unsigned)t < (unsigned)d.Ti && (unsigned)h < (unsigned)d.Hi && (unsigned)w < (unsigned)d.Wi;
-                    f32x4 v = {0.f, 0.f, 0.f, 0.f};   // F.pad zero (pytorch_i3d.py:44)
-                    if (inb) v = *(const f32x4*)(x + ((size_t)((n * d.Ti + t) * d.Hi + h) * d.Wi + w) * d.ldi + c);
+        if constexpr (KT == 0) {
+            int tap = 0;
+            for (int a = 0; a < d.k[0]; ++a) {
+                const int t = to * d.s[0] - d.padf[0] + a;
+                for (int b = 0; b < d.k[1]; ++b) {
+                    const int h = ho * d.s[1] - d.padf[1] + b;
+                    for (int cc = 0; cc < d.k[2]; ++cc, ++tap) {
+                        const int w = wo * d.s[2] - d.padf[2] + cc;
+                        const bool inb = (unsigned)t < (unsigned)d.Ti && (unsigned)h < (unsigned)d.Hi && (unsigned)w < (unsigned)d.Wi;
+                        f32x4 v = {0.f, 0.f, 0.f, 0.f};   // F.pad zero (pytorch_i3d.py:44)
+                        if (inb) v = *(const f32x4*)(x + ((size_t)((n * d.Ti + t) * d.Hi + h) * d.Wi + w) * d.ldi + c);
+#pragma unroll
+                        for (int e = 0; e < 4; ++e)
+                            if (v[e] > best[e]) { best[e] = v[e]; bi[e] = inb ? tap : 255; }
+                    }
+                }
+            }
+        } else {
+            const int h0 = ho * SH - d.padf[1], w0 = wo * SW - d.padf[2];
+#pragma unroll
+            for (int a = 0; a < KT; ++a) {
+                const int t = to * ST - d.padf[0] + a;
+                if ((unsigned)t >= (unsigned)d.Ti) {       // a plane of padding: nine zeros with index 255, of which only the first can win
 #pragma unroll
                     for (int e = 0; e < 4; ++e)
-                        if (v[e] > best[e]) { best[e] = v[e]; bi[e] = inb ? tap : 255; }
+                        if (0.f > best[e]) { best[e] = 0.f; bi[e] = 255; }
+                    continue;
                 }
+                f32x4 v[KH * KW];
+                const float* xp = x + (size_t)(n * d.Ti + t) * d.Hi * d.Wi * d.ldi + c;
+#pragma unroll
+                for (int b = 0; b < KH; ++b)
+#pragma unroll
+                    for (int cc = 0; cc < KW; ++cc) {
+                        const int h = min(max(h0 + b, 0), d.Hi - 1), w = min(max(w0 + cc, 0), d.Wi - 1);
+                        v[b * KW + cc] = *(const f32x4*)(xp + ((size_t)h * d.Wi + w) * d.ldi);
+                    }
+#pragma unroll
+                for (int b = 0; b < KH; ++b)
+#pragma unroll
+                    for (int cc = 0; cc < KW; ++cc) {
+                        const bool inb = (unsigned)(h0 + b) < (unsigned)d.Hi && (unsigned)(w0 + cc) < (unsigned)d.Wi;
+                        const int tap = (a * KH + b) * KW + cc;
+#pragma unroll
+                        for (int e = 0; e < 4; ++e) {
+                            const float u = inb ? v[b * KW + cc][e] : 0.f;   // F.pad zero (pytorch_i3d.py:44)
+                            if (u > best[e]) { best[e] = u; bi[e] = inb ? tap : 255; }
+                        }
+                    }
             }
         }
         *(f32x4*)(y + opos * d.ldo + c) = best;
@@ -442,44 +540,86 @@ __global__ __launch_bounds__(256) void maxpool_fwd_kernel(const pc_pool_desc d, 
     }
 }
 
+template <int KT, int KH, int KW, int ST, int SH, int SW>
 __global__ __launch_bounds__(256) void maxpool_bwd_kernel(const pc_pool_desc d, const float* __restrict__ dy, const uint8_t* __restrict__ am,
-                                                          float* __restrict__ dx, int accum, int64_t total4) {
-    const int C4 = d.C / 4;
-    for (int64_t idx = (int64_t)blockIdx.x * 256 + threadIdx.x; idx < total4; idx += (int64_t)gridDim.x * 256) {
-        unsigned pos = (unsigned)idx / (unsigned)C4;
-        const int c = (int)((unsigned)idx - pos * C4) * 4;
+                                                          float* __restrict__ dx, int accum, unsigned npos, unsigned ppb) {
+    const unsigned C4 = (unsigned)d.C / 4;
+    const unsigned p0 = (unsigned)xcd_remap((int)blockIdx.x, (int)gridDim.x) * ppb;
+    if (p0 >= npos) return;
+    const unsigned items = (min(npos, p0 + ppb) - p0) * C4;
+    const int K[3] = {KT ? KT : d.k[0], KT ? KH : d.k[1], KT ? KW : d.k[2]}, S[3] = {KT ? ST : d.s[0], KT ? SH : d.s[1], KT ? SW : d.s[2]};
+    for (unsigned i = threadIdx.x; i < items; i += 256) {
+        unsigned pos = p0 + i / C4;
+        const int c = (int)(i % C4) * 4;
         const size_t ipos = pos;
         const int w = (int)(pos % (unsigned)d.Wi); pos /= (unsigned)d.Wi;
         const int h = (int)(pos % (unsigned)d.Hi); pos /= (unsigned)d.Hi;
         const int t = (int)(pos % (unsigned)d.Ti); const int n = (int)(pos / (unsigned)d.Ti);
+        float* o = dx + ipos * d.ldi + c;
+        f32x4 old = {0.f, 0.f, 0.f, 0.f};
+        if (accum) old = *(const f32x4*)o;
         f32x4 g = {0.f, 0.f, 0.f, 0.f};
         // windows that cover this input position: per dimension the outputs o with 0 <= x + padf - o*s < k
         int lo[3], hi[3];
         const int xs[3] = {t, h, w}, Os[3] = {d.To, d.Ho, d.Wo};
 #pragma unroll
         for (int q = 0; q < 3; ++q) {
-            const int top = xs[q] + d.padf[q], bot = top - d.k[q] + 1;
-            hi[q] = min(top / d.s[q], Os[q] - 1);
-            lo[q] = bot <= 0 ? 0 : (bot + d.s[q] - 1) / d.s[q];
+            const int top = xs[q] + d.padf[q], bot = top - K[q] + 1;
+            hi[q] = min(top / S[q], Os[q] - 1);
+            lo[q] = bot <= 0 ? 0 : (bot + S[q] - 1) / S[q];
         }
-        for (int to = lo[0]; to <= hi[0]; ++to) {
-            const int a = t + d.padf[0] - to * d.s[0];
-            for (int ho = lo[1]; ho <= hi[1]; ++ho) {
-                const int b = h + d.padf[1] - ho * d.s[1];
-                for (int wo = lo[2]; wo <= hi[2]; ++wo) {
-                    const int tap = (a * d.k[1] + b) * d.k[2] + (w + d.padf[2] - wo * d.s[2]);
-                    const size_t op = (size_t)((n * d.To + to) * d.Ho + ho) * d.Wo + wo;
-                    const uchar4 ix = *(const uchar4*)(am + op * d.C + c);
-                    const f32x4 v = *(const f32x4*)(dy + op * d.ldo + c);
-                    if (ix.x == tap) g[0] += v[0];
-                    if (ix.y == tap) g[1] += v[1];
-                    if (ix.z == tap) g[2] += v[2];
-                    if (ix.w == tap) g[3] += v[3];
+        if constexpr (KT == 0) {
+            for (int to = lo[0]; to <= hi[0]; ++to) {
+                const int a = t + d.padf[0] - to * S[0];
+                for (int ho = lo[1]; ho <= hi[1]; ++ho) {
+                    const int b = h + d.padf[1] - ho * S[1];
+                    for (int wo = lo[2]; wo <= hi[2]; ++wo) {
+                        const int tap = (a * K[1] + b) * K[2] + (w + d.padf[2] - wo * S[2]);
+                        const size_t op = (size_t)((n * d.To + to) * d.Ho + ho) * d.Wo + wo;
+                        const uchar4 ix = *(const uchar4*)(am + op * d.C + c);
+                        const f32x4 v = *(const f32x4*)(dy + op * d.ldo + c);
+                        if (ix.x == tap) g[0] += v[0];
+                        if (ix.y == tap) g[1] += v[1];
+                        if (ix.z == tap) g[2] += v[2];
+                        if (ix.w == tap) g[3] += v[3];
+                    }
                 }
             }
+        } else {
+            // at most ceil(k / s) windows per dimension: those of one output plane are loaded together (clamped: a window past hi is not added)
+            constexpr int MT = (KT + ST - 1) / ST, MH = (KH + SH - 1) / SH, MW = (KW + SW - 1) / SW;
+#pragma unroll
+            for (int jt = 0; jt < MT; ++jt) {
+                const int to = lo[0] + jt;
+                if (to > hi[0]) break;
+                const int a = t + d.padf[0] - to * ST;
+                uchar4 ix[MH * MW];
+                f32x4 v[MH * MW];
+#pragma unroll
+                for (int jh = 0; jh < MH; ++jh)
+#pragma unroll
+                    for (int jw = 0; jw < MW; ++jw) {
+                        const int ho = min(lo[1] + jh, d.Ho - 1), wo = min(lo[2] + jw, d.Wo - 1);
+                        const size_t op = (size_t)((n * d.To + to) * d.Ho + ho) * d.Wo + wo;
+                        ix[jh * MW + jw] = *(const uchar4*)(am + op * d.C + c);
+                        v[jh * MW + jw] = *(const f32x4*)(dy + op * d.ldo + c);
+                    }
+#pragma unroll
+                for (int jh = 0; jh < MH; ++jh)
+#pragma unroll
+                    for (int jw = 0; jw < MW; ++jw) {
+                        const int ho = lo[1] + jh, wo = lo[2] + jw;
+                        const int tap = (ho <= hi[1] && wo <= hi[2]) ? (a * KH + (h + d.padf[1] - ho * SH)) * KW + (w + d.padf[2] - wo * SW) : 256;
+                        const uchar4 q = ix[jh * MW + jw];
+                        const f32x4 u = v[jh * MW + jw];
+                        if (q.x == tap) g[0] += u[0];
+                        if (q.y == tap) g[1] += u[1];
+                        if (q.z == tap) g[2] += u[2];
+                        if (q.w == tap) g[3] += u[3];
+                    }
+            }
         }
-        float* o = dx + ipos * d.ldi + c;
-        if (accum) { const f32x4 old = *(const f32x4*)o; g += old; }
+        if (accum) g += old;
         *(f32x4*)o = g;
     }
 }
@@ -679,6 +819,15 @@ inline int grid_for(int64_t n, int per_thread = 1) {
     if (b < 1) b = 1;
     return (int)b;
 }
+inline int pool_blocks(int64_t total4) { return total4 > POOL_ITEMS ? (int)((total4 + POOL_ITEMS - 1) / POOL_ITEMS) : 1; }
+// which compile-time window / stride form of the pool kernels a descriptor takes (0: the generic body)
+inline int pool_form(const pc_pool_desc* d) {
+    const auto is = [](const int32_t* v, int a, int b, int c) { return v[0] == a && v[1] == b && v[2] == c; };
+    if (is(d->k, 1, 3, 3) && is(d->s, 1, 2, 2)) return 1;
+    if (is(d->k, 3, 3, 3) && is(d->s, 2, 1, 1)) return 2;
+    if (is(d->k, 3, 3, 3) && is(d->s, 1, 1, 1)) return 3;
+    return 0;
+}
 // the double nearest to the shortest decimal string that converts back to exactly this float (0.999f -> 0.999, 0.9f -> 0.9)
 inline double pc_decimal_of_float(float x) {
     char buf[40];
@@ -800,7 +949,7 @@ extern "C" int pc_bn_bwd(const float* dy, int lddy, const float* z, int ldz, con
         p.stat = stat; p.C4 = C / 4; p.rows = rpg; p.rows_per_group = rpg; p.rows_per_block = rpb;
         p.act = relu ? PC_ACT_RELU : PC_ACT_NONE; p.part = part;
         p.a_gs = rpg * lddy; p.b_gs = rpg * ldz; p.stat_gs = 4 * C; p.part_gs = (int64_t)npg * 2 * C;
-        hipLaunchKernelGGL(colreduce_kernel<0>, dim3(npg, groups), dim3(256), 0, s, p);
+        hipLaunchKernelGGL(colreduce_kernel, dim3(npg, groups), dim3(256), 0, s, p);
     }
     PC_CHECK_LAUNCH("bn_bwd reduce");
     if (fused) {
@@ -822,18 +971,36 @@ extern "C" int pc_bn_bwd(const float* dy, int lddy, const float* z, int ldz, con
 extern "C" int pc_maxpool_fwd(const pc_pool_desc* d, const float* x, float* y, uint8_t* argmax, pc_stream s) {
     PC_CHECK_ARG(d && x && y && argmax && d->C % 4 == 0 && d->ldi % 4 == 0 && d->ldo % 4 == 0, "pc_maxpool_fwd: bad args");
     PC_CHECK_ARG(d->k[0] * d->k[1] * d->k[2] < 255, "pc_maxpool_fwd: window too large");
-    const int64_t total4 = (int64_t)d->N * d->To * d->Ho * d->Wo * (d->C / 4);
+    const int64_t npos = (int64_t)d->N * d->To * d->Ho * d->Wo, total4 = npos * (d->C / 4);
     PC_CHECK_ARG(total4 < (1ll << 31), "elementwise kernels index with 32 bits: %lld float4 elements", (long long)total4);
-    hipLaunchKernelGGL(maxpool_fwd_kernel, dim3(grid_for(total4)), dim3(256), 0, (hipStream_t)s, *d, x, y, argmax, total4);
+    const int nblk = pool_blocks(total4);
+    const unsigned ppb = (unsigned)cdiv(npos, nblk);
+#define PC_POOL_FWD(...) hipLaunchKernelGGL((maxpool_fwd_kernel<__VA_ARGS__>), dim3(nblk), dim3(256), 0, (hipStream_t)s, *d, x, y, argmax, (unsigned)npos, ppb)
+    switch (pool_form(d)) {
+        case 1: PC_POOL_FWD(1, 3, 3, 1, 2, 2); break;
+        case 2: PC_POOL_FWD(3, 3, 3, 2, 1, 1); break;
+        case 3: PC_POOL_FWD(3, 3, 3, 1, 1, 1); break;
+        default: PC_POOL_FWD(0, 0, 0, 0, 0, 0);
+    }
+#undef PC_POOL_FWD
     PC_CHECK_LAUNCH("maxpool_fwd");
     return PC_OK;
 }
 
 extern "C" int pc_maxpool_bwd(const pc_pool_desc* d, const float* dy, const uint8_t* argmax, float* dx, int accum, pc_stream s) {
     PC_CHECK_ARG(d && dy && dx && argmax && d->C % 4 == 0 && d->ldi % 4 == 0 && d->ldo % 4 == 0, "pc_maxpool_bwd: bad args");
-    const int64_t total4 = (int64_t)d->N * d->Ti * d->Hi * d->Wi * (d->C / 4);
+    const int64_t npos = (int64_t)d->N * d->Ti * d->Hi * d->Wi, total4 = npos * (d->C / 4);
     PC_CHECK_ARG(total4 < (1ll << 31), "elementwise kernels index with 32 bits: %lld float4 elements", (long long)total4);
-    hipLaunchKernelGGL(maxpool_bwd_kernel, dim3(grid_for(total4)), dim3(256), 0, (hipStream_t)s, *d, dy, argmax, dx, accum, total4);
+    const int nblk = pool_blocks(total4);
+    const unsigned ppb = (unsigned)cdiv(npos, nblk);
+#define PC_POOL_BWD(...) hipLaunchKernelGGL((maxpool_bwd_kernel<__VA_ARGS__>), dim3(nblk), dim3(256), 0, (hipStream_t)s, *d, dy, argmax, dx, accum, (unsigned)npos, ppb)
+    switch (pool_form(d)) {
+        case 1: PC_POOL_BWD(1, 3, 3, 1, 2, 2); break;
+        case 2: PC_POOL_BWD(3, 3, 3, 2, 1, 1); break;
+        case 3: PC_POOL_BWD(3, 3, 3, 1, 1, 1); break;
+        default: PC_POOL_BWD(0, 0, 0, 0, 0, 0);
+    }
+#undef PC_POOL_BWD
     PC_CHECK_LAUNCH("maxpool_bwd");
     return PC_OK;
 }
@@ -857,21 +1024,20 @@ extern "C" int pc_act_bwd(const float* dy, int lddy, const float* y, int ldy, in
                           float* dbias, int accum, float* ws, pc_stream s_) {
     hipStream_t s = (hipStream_t)s_;
     PC_CHECK_ARG(dy && y && C % 4 == 0 && C <= 1024 && lddy % 4 == 0 && ldy % 4 == 0, "pc_act_bwd: bad args (C=%d)", C);
-    if (dbias) {
+    const bool write = dz && (act != PC_ACT_NONE || dz != dy);
+    const int64_t total4 = rows * (C / 4);
+    if (write) {
+        PC_CHECK_ARG(lddz % 4 == 0, "pc_act_bwd: lddz");
+        PC_CHECK_ARG(total4 < (1ll << 31), "elementwise kernels index with 32 bits: %lld float4 elements", (long long)total4);
+    }
+    if (dbias) {        // one pass over (dy, y): the partial sums and, where asked for, dz
         PC_CHECK_ARG(ws, "pc_act_bwd: ws required for dbias");
         const int64_t rpb = red_rows_per_block(rows);
         const int nblk = (int)((rows + rpb - 1) / rpb);
-        RedP p;
-        p.a = dy; p.lda = lddy; p.b = y; p.ldb = ldy; p.stat = nullptr; p.C4 = C / 4; p.rows = rows; p.rows_per_group = rows;
-        p.rows_per_block = rpb; p.act = act; p.part = ws;
-        p.a_gs = p.b_gs = p.stat_gs = p.part_gs = 0;
-        hipLaunchKernelGGL(colreduce_kernel<1>, dim3(nblk), dim3(256), 0, s, p);
+        if (write) hipLaunchKernelGGL(act_bwd_reduce_kernel<true>, dim3(nblk), dim3(256), 0, s, dy, lddy, y, ldy, act, C / 4, rows, rpb, dz, lddz, ws);
+        else hipLaunchKernelGGL(act_bwd_reduce_kernel<false>, dim3(nblk), dim3(256), 0, s, dy, lddy, y, ldy, act, C / 4, rows, rpb, (float*)nullptr, 0, ws);
         hipLaunchKernelGGL(colsum_finalize_kernel, dim3(cdiv(C, FIN_CL)), dim3(FIN_T), 0, s, ws, nblk, C, dbias, accum);
-    }
-    if (dz && (act != PC_ACT_NONE || dz != dy)) {
-        PC_CHECK_ARG(lddz % 4 == 0, "pc_act_bwd: lddz");
-        const int64_t total4 = rows * (C / 4);
-        PC_CHECK_ARG(total4 < (1ll << 31), "elementwise kernels index with 32 bits: %lld float4 elements", (long long)total4);
+    } else if (write) {
         hipLaunchKernelGGL(act_bwd_apply_kernel, dim3(grid_for(total4, 2)), dim3(256), 0, s, dy, lddy, y, ldy, act, C / 4, total4, dz, lddz);
     }
     PC_CHECK_LAUNCH("act_bwd");
