@@ -624,6 +624,167 @@ __global__ __launch_bounds__(256) void maxpool_bwd_kernel(const pc_pool_desc d, 
     }
 }
 
+// The 3x3x3 windows with stride 1 along h and w (ST = 1 or 2 along t): a thread owns a register tile of four adjacent positions times four
+// channels -- forward 2 x 2 outputs (h x w), backward POOL_WT input positions along w -- one (tile, channel quad) item per thread, a block
+// 256 consecutive items (tiles in row order, channels fastest), blocks in the same XCD-local order.  The positions of a tile share taps: a
+// temporal plane is loaded once for all four (forward 4 x 4 = 16 quads, backward 3 x 6 = 18 (argmax, dy) pairs, instead of 36) and then
+// compared / added per position in exactly the order of the kernels above -- forward (kt, kh, kw) with a strict `>`, a padding tap 0 with
+// index 255, a padded plane one compare; backward ascending (to, ho, wo), the old dx last.  Lanes stay channel-contiguous, so every access
+// is a coalesced 16-byte one.  A tile that reaches past the end of a row (or, forward, past the last row) loads clamped addresses there
+// and stores nothing.
+constexpr int POOL_WT = 4;
+
+template <int ST>
+__global__ __launch_bounds__(256, 4) void maxpool333_fwd_tile_kernel(const pc_pool_desc d, const float* __restrict__ x, float* __restrict__ y,
+                                                                     uint8_t* __restrict__ am, unsigned nitems) {
+    const unsigned C4 = (unsigned)d.C / 4, tw = ((unsigned)d.Wo + 1) / 2, th = ((unsigned)d.Ho + 1) / 2;
+    const unsigned i = (unsigned)xcd_remap((int)blockIdx.x, (int)gridDim.x) * 256 + threadIdx.x;
+    if (i < nitems) {
+        unsigned q = i / C4;
+        const int c = (int)(i % C4) * 4;
+        const int wo0 = (int)(q % tw) * 2; q /= tw;
+        const int ho0 = (int)(q % th) * 2; q /= th;
+        const int to = (int)(q % (unsigned)d.To); const int n = (int)(q / (unsigned)d.To);
+        f32x4 best[4];                                     // position u = 2 * (row of the tile) + column
+        unsigned bi[4];                                    // the winning tap of each of the four channels, one byte each
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+            best[u] = f32x4{-INFINITY, -INFINITY, -INFINITY, -INFINITY};
+            bi[u] = 0xFFFFFFFFu;
+        }
+        const int h0 = ho0 - d.padf[1], w0 = wo0 - d.padf[2];
+#pragma unroll 1
+        for (int a = 0; a < 3; ++a) {
+            const int t = to * ST - d.padf[0] + a;
+            if ((unsigned)t >= (unsigned)d.Ti) {       // a plane of padding: nine zeros with index 255, of which only the first can win
+#pragma unroll
+                for (int u = 0; u < 4; ++u)
+#pragma unroll
+                    for (int e = 0; e < 4; ++e)
+                        if (0.f > best[u][e]) { best[u][e] = 0.f; bi[u] |= 0xFFu << (8 * e); }
+                continue;
+            }
+            // Registers: the taps take 64 and the running maxima 20.  An address is a 32-bit byte offset from x, one register (the host sends
+            // inputs of 4 GB and more to the kernel above), and is worked out here, per plane: the asm keeps the compiler from holding the
+            // sixteen in-plane offsets in registers across the plane loop
+            f32x4 v[4][4];
+            const unsigned pb = ((unsigned)((n * d.Ti + t) * d.Hi) * (unsigned)d.Wi * (unsigned)d.ldi + (unsigned)c) * 4u;
+            int h0a = h0, w0a = w0;
+            asm volatile("" : "+v"(h0a), "+v"(w0a));
+#pragma unroll
+            for (int r = 0; r < 4; ++r)
+#pragma unroll
+                for (int j = 0; j < 4; ++j) {
+                    const int h = min(max(h0a + r, 0), d.Hi - 1), w = min(max(w0a + j, 0), d.Wi - 1);
+                    v[r][j] = *(const f32x4*)((const char*)x + (pb + (unsigned)(h * d.Wi + w) * (unsigned)d.ldi * 4u));
+                }
+#pragma unroll
+            for (int r = 0; r < 4; ++r)
+#pragma unroll
+                for (int j = 0; j < 4; ++j)
+                    if (!((unsigned)(h0 + r) < (unsigned)d.Hi && (unsigned)(w0 + j) < (unsigned)d.Wi)) v[r][j] = f32x4{0.f, 0.f, 0.f, 0.f};   // F.pad zero (pytorch_i3d.py:44)
+            const unsigned tap0 = (unsigned)a * 9u;
+#pragma unroll
+            for (int u = 0; u < 4; ++u)
+#pragma unroll
+                for (int b = 0; b < 3; ++b)
+#pragma unroll
+                    for (int cc = 0; cc < 3; ++cc) {
+                        const unsigned tap4 = (tap0 + (unsigned)(b * 3 + cc)) * 0x01010101u;
+                        const f32x4 z = v[u / 2 + b][u % 2 + cc];
+#pragma unroll
+                        for (int e = 0; e < 4; ++e) {
+                            const unsigned m = 0xFFu << (8 * e);
+                            if (z[e] > best[u][e]) { best[u][e] = z[e]; bi[u] = (bi[u] & ~m) | (tap4 & m); }
+                        }
+                    }
+        }
+        // a winning tap that lies in the spatial padding reads 255: bit (kh, kw) of `in9` says whether that tap of position u is inside, the
+        // same for the three planes (a padded plane has written 255 itself, and 255 & 31 = 31 is a clear bit)
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+            const int ho = ho0 + u / 2, wo = wo0 + u % 2;
+            unsigned in9 = 0;
+#pragma unroll
+            for (int b = 0; b < 3; ++b)
+#pragma unroll
+                for (int cc = 0; cc < 3; ++cc)
+                    if ((unsigned)(h0 + u / 2 + b) < (unsigned)d.Hi && (unsigned)(w0 + u % 2 + cc) < (unsigned)d.Wi) in9 |= 1u << (b * 3 + cc);
+            const unsigned in27 = in9 | in9 << 9 | in9 << 18;
+#pragma unroll
+            for (int e = 0; e < 4; ++e)
+                if (!(in27 >> ((bi[u] >> (8 * e)) & 31u) & 1u)) bi[u] |= 0xFFu << (8 * e);
+            if (ho < d.Ho && wo < d.Wo) {
+                const size_t opos = (size_t)((n * d.To + to) * d.Ho + ho) * d.Wo + wo;
+                *(f32x4*)(y + opos * d.ldo + c) = best[u];
+                *(unsigned*)(am + opos * d.C + c) = bi[u];
+            }
+        }
+    }
+}
+
+template <int ST, int WT>
+__global__ __launch_bounds__(256, 4) void maxpool333_bwd_tile_kernel(const pc_pool_desc d, const float* __restrict__ dy, const uint8_t* __restrict__ am,
+                                                                     float* __restrict__ dx, int accum, unsigned nitems) {
+    const unsigned C4 = (unsigned)d.C / 4, tw = ((unsigned)d.Wi + WT - 1) / WT;
+    const unsigned i = (unsigned)xcd_remap((int)blockIdx.x, (int)gridDim.x) * 256 + threadIdx.x;
+    if (i < nitems) {
+        unsigned q = i / C4;
+        const int c = (int)(i % C4) * 4;
+        const int w0 = (int)(q % tw) * WT; q /= tw;
+        const int h = (int)(q % (unsigned)d.Hi); q /= (unsigned)d.Hi;
+        const int t = (int)(q % (unsigned)d.Ti); const int n = (int)(q / (unsigned)d.Ti);
+        f32x4 g[WT];
+#pragma unroll
+        for (int u = 0; u < WT; ++u) g[u] = f32x4{0.f, 0.f, 0.f, 0.f};
+        // windows that cover an input position: per dimension the outputs o with 0 <= x + padf - o*s < 3.  Along h and w (stride 1) those are
+        // o = x + padf - 2 .. x + padf where they exist: rows hb .. hb + 2 and, for the whole tile, columns wb .. wb + WT + 1
+        const int top = t + d.padf[0], bot = top - 2;
+        const int thi = min(top / ST, d.To - 1), tlo = bot <= 0 ? 0 : (bot + ST - 1) / ST;
+        const int hb = h + d.padf[1] - 2, wb = w0 + d.padf[2] - 2;
+        constexpr int MT = (3 + ST - 1) / ST;
+#pragma unroll 1
+        for (int jt = 0; jt < MT; ++jt) {
+            const int to = tlo + jt;
+            if (to > thi) break;
+            const int a = top - to * ST;
+            uchar4 ix[3][WT + 2];
+            f32x4 v[3][WT + 2];
+#pragma unroll
+            for (int jh = 0; jh < 3; ++jh)
+#pragma unroll
+                for (int j = 0; j < WT + 2; ++j) {
+                    const int ho = min(max(hb + jh, 0), d.Ho - 1), wo = min(max(wb + j, 0), d.Wo - 1);
+                    const size_t op = (size_t)((n * d.To + to) * d.Ho + ho) * d.Wo + wo;
+                    ix[jh][j] = *(const uchar4*)(am + op * d.C + c);
+                    v[jh][j] = *(const f32x4*)(dy + op * d.ldo + c);
+                }
+#pragma unroll
+            for (int jh = 0; jh < 3; ++jh)                 // row by row: every position still sees its windows in (ho, wo) order
+#pragma unroll
+                for (int u = 0; u < WT; ++u)
+#pragma unroll
+                    for (int jw = 0; jw < 3; ++jw) {          // output (hb + jh, wb + u + jw) holds this position as tap (a, 2 - jh, 2 - jw)
+                        const bool ok = (unsigned)(hb + jh) < (unsigned)d.Ho && (unsigned)(wb + u + jw) < (unsigned)d.Wo;
+                        const int tap = ok ? (a * 3 + (2 - jh)) * 3 + (2 - jw) : 256;
+                        const uchar4 k = ix[jh][u + jw];
+                        const f32x4 z = v[jh][u + jw];
+                        if (k.x == tap) g[u][0] += z[0];
+                        if (k.y == tap) g[u][1] += z[1];
+                        if (k.z == tap) g[u][2] += z[2];
+                        if (k.w == tap) g[u][3] += z[3];
+                    }
+        }
+        float* o = dx + ((size_t)((n * d.Ti + t) * d.Hi + h) * d.Wi + w0) * d.ldi + c;
+#pragma unroll
+        for (int u = 0; u < WT; ++u)
+            if (w0 + u < d.Wi) {
+                if (accum) g[u] += *(const f32x4*)(o + (size_t)u * d.ldi);
+                *(f32x4*)(o + (size_t)u * d.ldi) = g[u];
+            }
+    }
+}
+
 // ------------------------------------------------------------------------------ misc elementwise
 __global__ __launch_bounds__(256) void chscale_kernel(const float* __restrict__ x, int ldx, const float* __restrict__ sc, int64_t pos_per_n,
                                                       int C4, int64_t total4, float* __restrict__ y, int ldy, int accum) {
@@ -751,6 +912,70 @@ __global__ __launch_bounds__(256) void transpose_multi_kernel(const TPack pk) {
     }
 }
 
+// The jobs of a pc_transpose_multi call that move rows, not tiles.  Two kinds, both with unit stride on the source side:
+//   C == 1 without slices and src_ld == 1 (the forward re-layout of a 1x1x1 weight): dst[b][r] (+)= src[b][r], a copy per batch;
+//   R == 1 (the gradient of such a weight, with its K-slice images): dst[b][c * dst_ld] (+)= sum over the images of src[b][c].
+// Through the tile kernel these launch a block per 32 floats, and in the sliced ones 8 of its 256 threads do the sums.  Here a job is
+// batch rows of L floats, a thread owns one quad of one row, a block 256 consecutive quads of the job (rows are not padded to the block),
+// and a sliced job has sixteen 16-byte loads in flight in every thread.  The value is the tile kernel's, expression for expression:
+// without slices the source element itself, with slices a sum that starts from zero and adds the images in ascending order; then
+// (accum ? old : 0) + value.  vld / vst: whether the rows allow 16-byte loads / stores (set by the host from the pointers and strides);
+// a quad that reaches past L stores its elements one by one.
+struct RJobK { const float* src; float* dst; long long sbs, dbs, sst; int batch, L, dstep, accum, nsl, qpr, vld, vst; };
+struct RPack { RJobK j[TM_JOBS]; int first[TM_JOBS + 1]; int n; };
+
+__global__ __launch_bounds__(256) void relayout_rows_kernel(const RPack pk) {
+    int k = 0;
+    while (k + 1 < pk.n && (int)blockIdx.x >= pk.first[k + 1]) ++k;
+    const RJobK& J = pk.j[k];
+    const long long gq = (long long)((int)blockIdx.x - pk.first[k]) * 256 + threadIdx.x;
+    const long long b = gq / J.qpr;
+    if (b >= J.batch) return;
+    const int c = (int)(gq - b * J.qpr) * 4;
+    const float* s = J.src + b * J.sbs + c;
+    f32x4 v = {0.f, 0.f, 0.f, 0.f};
+    if (J.nsl <= 1) {
+        if (J.vld) v = *(const f32x4*)s;
+        else {
+#pragma unroll
+            for (int e = 0; e < 4; ++e)
+                if (c + e < J.L) v[e] = s[e];
+        }
+    } else {                                               // the host has checked alignment and that the quad lies inside the row (L <= src_ld)
+        const f32x4* q = (const f32x4*)s;
+        const size_t st4 = (size_t)J.sst / 4;
+        int i = 0;
+        for (; i + 16 <= J.nsl; i += 16) {
+            f32x4 t[16];
+#pragma unroll
+            for (int u = 0; u < 16; ++u) t[u] = q[(size_t)(i + u) * st4];
+#pragma unroll
+            for (int u = 0; u < 16; ++u) v += t[u];
+        }
+        for (; i + 4 <= J.nsl; i += 4) {
+            f32x4 t[4];
+#pragma unroll
+            for (int u = 0; u < 4; ++u) t[u] = q[(size_t)(i + u) * st4];
+#pragma unroll
+            for (int u = 0; u < 4; ++u) v += t[u];
+        }
+        for (; i < J.nsl; ++i) v += q[(size_t)i * st4];
+    }
+    float* o = J.dst + b * J.dbs + (long long)c * J.dstep;
+    if (J.vst && c + 4 <= J.L) {
+        f32x4 old = {0.f, 0.f, 0.f, 0.f};
+        if (J.accum) old = *(const f32x4*)o;
+        *(f32x4*)o = old + v;
+    } else {
+#pragma unroll
+        for (int e = 0; e < 4; ++e)
+            if (c + e < J.L) {
+                float* p = o + (long long)e * J.dstep;
+                *p = (J.accum ? *p : 0.f) + v[e];
+            }
+    }
+}
+
 // K-slice images of an ordered split-K weight gradient, folded in place: image g * group of every group of `group` consecutive images
 // becomes the sum of the group's images, added in slice order.  One thread per float4 of the image and group: `group` independent loads.
 template <int GROUP>
@@ -820,6 +1045,10 @@ inline int grid_for(int64_t n, int per_thread = 1) {
     return (int)b;
 }
 inline int pool_blocks(int64_t total4) { return total4 > POOL_ITEMS ? (int)((total4 + POOL_ITEMS - 1) / POOL_ITEMS) : 1; }
+// items of the register-tile pool kernels: `rows` rows of W positions cut into tiles of POOL_WT, times C4 channel quads (never more than total4)
+inline int64_t pool_tile_items(int64_t rows, int W, int C4) { return rows * ((W + POOL_WT - 1) / POOL_WT) * C4; }
+// the forward tile kernel addresses its input with 32-bit byte offsets
+inline bool pool_in_4g(const pc_pool_desc* d) { return (int64_t)d->N * d->Ti * d->Hi * d->Wi * d->ldi * 4 < (1ll << 32); }
 // which compile-time window / stride form of the pool kernels a descriptor takes (0: the generic body)
 inline int pool_form(const pc_pool_desc* d) {
     const auto is = [](const int32_t* v, int a, int b, int c) { return v[0] == a && v[1] == b && v[2] == c; };
@@ -976,12 +1205,20 @@ extern "C" int pc_maxpool_fwd(const pc_pool_desc* d, const float* x, float* y, u
     const int nblk = pool_blocks(total4);
     const unsigned ppb = (unsigned)cdiv(npos, nblk);
 #define PC_POOL_FWD(...) hipLaunchKernelGGL((maxpool_fwd_kernel<__VA_ARGS__>), dim3(nblk), dim3(256), 0, (hipStream_t)s, *d, x, y, argmax, (unsigned)npos, ppb)
+#define PC_POOL_FWD_TILE(ST)                                                                                                                     \
+    do {                                                                                                                                         \
+        const int64_t items = (int64_t)d->N * d->To * ((d->Ho + 1) / 2) * ((d->Wo + 1) / 2) * (d->C / 4);                                       \
+        hipLaunchKernelGGL((maxpool333_fwd_tile_kernel<ST>), dim3(items > 256 ? (unsigned)cdiv(items, 256) : 1), dim3(256), 0, (hipStream_t)s, \
+                           *d, x, y, argmax, (unsigned)items);                                                                                   \
+    } while (0)
+    const bool tile = pool_in_4g(d);
     switch (pool_form(d)) {
         case 1: PC_POOL_FWD(1, 3, 3, 1, 2, 2); break;
-        case 2: PC_POOL_FWD(3, 3, 3, 2, 1, 1); break;
-        case 3: PC_POOL_FWD(3, 3, 3, 1, 1, 1); break;
+        case 2: if (tile) PC_POOL_FWD_TILE(2); else PC_POOL_FWD(3, 3, 3, 2, 1, 1); break;
+        case 3: if (tile) PC_POOL_FWD_TILE(1); else PC_POOL_FWD(3, 3, 3, 1, 1, 1); break;
         default: PC_POOL_FWD(0, 0, 0, 0, 0, 0);
     }
+#undef PC_POOL_FWD_TILE
 #undef PC_POOL_FWD
     PC_CHECK_LAUNCH("maxpool_fwd");
     return PC_OK;
@@ -994,12 +1231,19 @@ extern "C" int pc_maxpool_bwd(const pc_pool_desc* d, const float* dy, const uint
     const int nblk = pool_blocks(total4);
     const unsigned ppb = (unsigned)cdiv(npos, nblk);
 #define PC_POOL_BWD(...) hipLaunchKernelGGL((maxpool_bwd_kernel<__VA_ARGS__>), dim3(nblk), dim3(256), 0, (hipStream_t)s, *d, dy, argmax, dx, accum, (unsigned)npos, ppb)
+#define PC_POOL_BWD_TILE(ST)                                                                                                                     \
+    do {                                                                                                                                         \
+        const int64_t items = pool_tile_items((int64_t)d->N * d->Ti * d->Hi, d->Wi, d->C / 4);                                                  \
+        hipLaunchKernelGGL((maxpool333_bwd_tile_kernel<ST, POOL_WT>), dim3(items > 256 ? (unsigned)cdiv(items, 256) : 1), dim3(256), 0, (hipStream_t)s, \
+                           *d, dy, argmax, dx, accum, (unsigned)items);                                                                          \
+    } while (0)
     switch (pool_form(d)) {
         case 1: PC_POOL_BWD(1, 3, 3, 1, 2, 2); break;
-        case 2: PC_POOL_BWD(3, 3, 3, 2, 1, 1); break;
-        case 3: PC_POOL_BWD(3, 3, 3, 1, 1, 1); break;
+        case 2: PC_POOL_BWD_TILE(2); break;
+        case 3: PC_POOL_BWD_TILE(1); break;
         default: PC_POOL_BWD(0, 0, 0, 0, 0, 0);
     }
+#undef PC_POOL_BWD_TILE
 #undef PC_POOL_BWD
     PC_CHECK_LAUNCH("maxpool_bwd");
     return PC_OK;
@@ -1072,31 +1316,78 @@ extern "C" int pc_transpose_batched(const float* src, int batch, int R, int Cc, 
 
 extern "C" int pc_transpose_multi(const pc_transpose_job* jobs, int njobs, pc_stream s) {
     PC_CHECK_ARG(jobs && njobs >= 1, "pc_transpose_multi: bad args");
-    for (int j0 = 0; j0 < njobs; j0 += TM_JOBS) {
-        TPack pk;
-        pk.n = njobs - j0 < TM_JOBS ? njobs - j0 : TM_JOBS;
-        int tiles = 0;
-        for (int q = 0; q < pk.n; ++q) {
-            const pc_transpose_job& a = jobs[j0 + q];
-            PC_CHECK_ARG(a.src && a.dst && a.batch >= 1 && a.R >= 1 && a.C >= 1, "pc_transpose_multi: bad job %d", j0 + q);
-            TJobK& k = pk.j[q];
-            k.src = (const float*)(uintptr_t)a.src; k.dst = (float*)(uintptr_t)a.dst; k.sbs = a.src_batch_stride; k.dbs = a.dst_batch_stride;
-            PC_CHECK_ARG(a.nslices >= 0 && (a.nslices <= 1 || a.slice_stride > 0), "pc_transpose_multi: job %d has %d slices %lld floats apart", j0 + q, a.nslices, (long long)a.slice_stride);
-            k.R = a.R; k.Cc = a.C; k.sld = a.src_ld; k.dld = a.dst_ld; k.accum = a.accum; k.nsl = a.nslices; k.sst = a.slice_stride;
-            PC_CHECK_ARG(a.nslices <= 1 || (a.C <= a.src_ld && a.src_ld % 4 == 0 && a.slice_stride % 4 == 0 && a.src_batch_stride % 4 == 0 && a.src % 16 == 0),
-                         "pc_transpose_multi: job %d sums slice images: src_ld (>= C) and the strides must be multiples of 4 floats and src 16-byte aligned", j0 + q);
-            // 32-row tiles (one 16-byte quad per thread and image, 256 threads busy) unless the job is too small to give every CU a block: then
-            // 8-row tiles, four times the blocks (the sum over many images is a chain of dependent loads per thread)
-            k.tr = (a.nslices > 1 && (long long)a.batch * cdiv(a.C, 32) * cdiv(a.R, 32) < 192) ? 8 : 32; k.pad_ = 0;
-            k.tiles_c = cdiv(a.C, 32); k.tiles_rc = k.tiles_c * cdiv(a.R, k.tr);
-            pk.first[q] = tiles;
-            tiles += a.batch * k.tiles_rc;
-        }
+    for (int j = 0; j < njobs; ++j) {
+        const pc_transpose_job& a = jobs[j];
+        PC_CHECK_ARG(a.src && a.dst && a.batch >= 1 && a.R >= 1 && a.C >= 1, "pc_transpose_multi: bad job %d", j);
+        PC_CHECK_ARG(a.nslices >= 0 && (a.nslices <= 1 || a.slice_stride > 0), "pc_transpose_multi: job %d has %d slices %lld floats apart", j, a.nslices, (long long)a.slice_stride);
+        PC_CHECK_ARG(a.nslices <= 1 || (a.C <= a.src_ld && a.src_ld % 4 == 0 && a.slice_stride % 4 == 0 && a.src_batch_stride % 4 == 0 && a.src % 16 == 0),
+                     "pc_transpose_multi: job %d sums slice images: src_ld (>= C) and the strides must be multiples of 4 floats and src 16-byte aligned", j);
+    }
+    // Jobs by class (the jobs of a call are independent, so their order is free): rows -- R == 1, or C == 1 read with unit stride and
+    // without slices -- go to relayout_rows_kernel, everything else to the tile kernel.  Both take their jobs by value, TM_JOBS to a launch.
+    const auto is_rows = [](const pc_transpose_job& a) { return a.R == 1 || (a.C == 1 && a.src_ld == 1 && a.nslices <= 1); };
+    TPack pk;
+    pk.n = 0;
+    int tiles = 0;
+    const auto flush_tiles = [&]() -> int {
+        if (!pk.n) return PC_OK;
         pk.first[pk.n] = tiles;
         hipLaunchKernelGGL(transpose_multi_kernel, dim3(tiles), dim3(256), 0, (hipStream_t)s, pk);
         PC_CHECK_LAUNCH("transpose_multi");
+        pk.n = 0; tiles = 0;
+        return PC_OK;
+    };
+    for (int j = 0; j < njobs; ++j) {
+        const pc_transpose_job& a = jobs[j];
+        if (is_rows(a)) continue;
+        TJobK k;
+        k.src = (const float*)(uintptr_t)a.src; k.dst = (float*)(uintptr_t)a.dst; k.sbs = a.src_batch_stride; k.dbs = a.dst_batch_stride;
+        k.R = a.R; k.Cc = a.C; k.sld = a.src_ld; k.dld = a.dst_ld; k.accum = a.accum; k.nsl = a.nslices; k.sst = a.slice_stride;
+        // 32-row tiles (one 16-byte quad per thread and image, 256 threads busy) unless the job is too small to give every CU a block: then
+        // 8-row tiles, four times the blocks (the sum over many images is a chain of dependent loads per thread)
+        k.tr = (a.nslices > 1 && (long long)a.batch * cdiv(a.C, 32) * cdiv(a.R, 32) < 192) ? 8 : 32; k.pad_ = 0;
+        k.tiles_c = cdiv(a.C, 32); k.tiles_rc = k.tiles_c * cdiv(a.R, k.tr);
+        const long long t = (long long)a.batch * k.tiles_rc;
+        PC_CHECK_ARG(t < (1ll << 30), "pc_transpose_multi: job %d is too large", j);
+        if (tiles + t >= (1ll << 30)) { const int rc = flush_tiles(); if (rc != PC_OK) return rc; }
+        pk.j[pk.n] = k;
+        pk.first[pk.n++] = tiles;
+        tiles += (int)t;
+        if (pk.n == TM_JOBS) { const int rc = flush_tiles(); if (rc != PC_OK) return rc; }
     }
-    return PC_OK;
+    { const int rc = flush_tiles(); if (rc != PC_OK) return rc; }
+    RPack rp;
+    rp.n = 0;
+    int units = 0;
+    const auto flush_rows = [&]() -> int {
+        if (!rp.n) return PC_OK;
+        rp.first[rp.n] = units;
+        hipLaunchKernelGGL(relayout_rows_kernel, dim3(units), dim3(256), 0, (hipStream_t)s, rp);
+        PC_CHECK_LAUNCH("transpose_multi rows");
+        rp.n = 0; units = 0;
+        return PC_OK;
+    };
+    for (int j = 0; j < njobs; ++j) {
+        const pc_transpose_job& a = jobs[j];
+        if (!is_rows(a)) continue;
+        RJobK k;
+        k.src = (const float*)(uintptr_t)a.src; k.dst = (float*)(uintptr_t)a.dst; k.sbs = a.src_batch_stride; k.dbs = a.dst_batch_stride; k.sst = a.slice_stride;
+        k.batch = a.batch; k.accum = a.accum; k.nsl = a.nslices;
+        if (a.R == 1) { k.L = a.C; k.dstep = a.dst_ld; }   // dst[b][c][0] (+)= src[b][0][c]
+        else { k.L = a.R; k.dstep = 1; }                   // dst[b][0][r] (+)= src[b][r][0], src_ld = 1
+        k.qpr = cdiv(k.L, 4);
+        const bool rows_al = a.batch == 1 || (a.src_batch_stride % 4 == 0);
+        k.vld = a.nslices > 1 || (a.src % 16 == 0 && rows_al && k.L % 4 == 0);
+        k.vst = k.dstep == 1 && a.dst % 16 == 0 && (a.batch == 1 || a.dst_batch_stride % 4 == 0);
+        const long long u = ((long long)a.batch * k.qpr + 255) / 256;
+        PC_CHECK_ARG(u < (1ll << 30), "pc_transpose_multi: job %d is too large", j);
+        if (units + u >= (1ll << 30)) { const int rc = flush_rows(); if (rc != PC_OK) return rc; }
+        rp.j[rp.n] = k;
+        rp.first[rp.n++] = units;
+        units += (int)u;
+        if (rp.n == TM_JOBS) { const int rc = flush_rows(); if (rc != PC_OK) return rc; }
+    }
+    return flush_rows();
 }
 
 extern "C" int pc_wgrad_fold_group(void) { return 16; }
