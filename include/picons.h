@@ -67,7 +67,8 @@ typedef void* pc_stream;            /* hipStream_t */
  * 106: pc_truth_frame_flags / pc_eval_clips_from_u8 / pc_video_vote;
  * 107: pc_clips_from_u8 / pc_detect_frames / pc_detect_frames_ws_bytes / pc_video_class; the entries pc_clips_from_u8_views / pc_detect_frames_views /
  * pc_detect_frames_views_ws_bytes came later and move nothing: no struct grew, no op's operands changed; so did pc_frame_instances with its
- * PC_INST_* constants, and pc_frame_probs / pc_instance_scores with PC_PROB_ONE / PC_SCORE_WORDS: came later, move nothing).  Descriptors must be zero-initialised by the caller:
+ * PC_INST_* constants, pc_frame_probs / pc_instance_scores with PC_PROB_ONE / PC_SCORE_WORDS, and pc_instance_overlaps with PC_LINK_MAX_LAGS:
+ * came later, move nothing).  Descriptors must be zero-initialised by the caller:
  * fields added later read as "old behaviour" when 0.  pc_version() returns the value the library was built with; the Python host
  * (capi.lib()) refuses a library whose version differs from the header it mirrors. */
 #define PC_VERSION 107
@@ -494,6 +495,18 @@ int     pc_frame_instances(const uint8_t* mask, int F, int H, int W, int f0, int
 int     pc_frame_probs(const float* logits, int F, int H, int W, int S, const int32_t* views, int V, int view_stride, const int32_t* starts,
                        int n, int f_skip, uint16_t* prob, pc_stream s);
 int     pc_instance_scores(const uint8_t* imap, const uint16_t* prob, int F, int H, int W, int f0, int nf, int K, int32_t* out, pc_stream s);
+/* Mask overlaps between frames (csrc/instances.hip; picons_amd/detect.py: DetectEngine(instance_links=L), link_instance_tubes_by_mask).
+ * pc_instance_overlaps: imap uint8 [F][H][W] as pc_frame_instances leaves it (a frame may start at any byte address; frame offsets are
+ * 64-bit) -> for each of the frames f0 .. f0 + nf - 1, and no others, the WHOLE record of `out` int32 [F][L][K + 1][K + 1]: out[f][l][a][b]
+ * is the number of pixels whose slot is a in frame f and b in frame f + l + 1.  The slots are pc_instance_scores': map value r + 1 <= K is
+ * slot r, every other non-zero value (255, and any in K + 1 .. 254) slot K, value 0 belongs to nothing.  A lag with f + l + 1 >= F is written
+ * as zeros; the partner frame may lie outside f0 .. f0 + nf - 1 as long as it is below F -- it is only read.  Nothing has to be zeroed in
+ * front of the launch.  Grid (nf, L), one 256-thread block per (frame, lag); the partner's bytes of a four-pixel group are read only where
+ * frame f holds foreground.  Integer LDS atomics only (per-wave bins of (K + 1)^2 int32, folded at the end), no global atomics, no floating
+ * point: bit-identical from run to run.  Refusals (PC_E_ARG before any HIP call): null imap or out; F, H, W < 1; H * W >= 2^31; f0 < 0,
+ * nf < 1, f0 + nf > F; K outside 1..32; L outside 1..PC_LINK_MAX_LAGS; out not 4-byte aligned. */
+#define PC_LINK_MAX_LAGS 4
+int     pc_instance_overlaps(const uint8_t* imap, int F, int H, int W, int f0, int nf, int K, int L, int32_t* out, pc_stream s);
 /* cv2.resize on uint8 images [n][H][W][C] -> [n][Ho][Wo][C] (C <= 4), the calls of the reference's loaders:
  * datasets/jhmdb_dataloader.py:252 (frames, INTER_AREA 320x240 -> 256x256), :267,:281 (puppet masks, INTER_NEAREST),
  * :192,:208 and ucf_dataloader.py:165,171 (224 crop -> frame size, INTER_LINEAR; the identity at 224).  OpenCV's 8-bit

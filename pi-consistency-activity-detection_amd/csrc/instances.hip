@@ -440,3 +440,100 @@ extern "C" int pc_instance_scores(const uint8_t* imap, const uint16_t* prob, int
     PC_CHECK_LAUNCH(who);
     return PC_OK;
 }
+
+// ---------------------------------------------------------------------- mask overlaps between frames (detect.DetectEngine, instance_links)
+//   pc_instance_overlaps  the map of ranks pc_frame_instances leaves, histogrammed per pair of frames: for frame f and each lag l the number
+//                         of pixels that slot a of frame f shares with slot b of frame f + l + 1 -- what linking per-actor tubes by mask
+//                         overlap needs, and what a caller had to copy every map to the host for.  One 256-thread block per (frame, lag),
+//                         latency-bound as its siblings are.  Integer addition only -- per-wave LDS bins, then folded -- so the record is the
+//                         same bits in whatever order the adds land; no global atomics, nothing to zero.
+namespace {
+
+constexpr int MAXPAIRS = MAXSLOTS * MAXSLOTS;
+static_assert(NW * MAXPAIRS * 4 == 17424, "static LDS of instance_overlaps_kernel");
+
+struct OverlapK {
+    const uint8_t* imap; int32_t* out;
+    int F, H, W, f0, K, L;
+};
+
+// grid (nf, L): block (b, l) is frame f0 + b against frame f0 + b + l + 1.  A thread walks the groups of four consecutive pixels of the first
+// frame (the loads of four groups in flight); the partner's bytes of a group are read only where the first frame holds foreground.  The two
+// frames lie H * W bytes apart, so for odd H * W their groups sit differently in their dwords: each side goes through map_bytes on its own.
+// The thread keeps a count for the (a, b) pair it is in and flushes it into its wave's bins when the pair changes.
+__global__ __launch_bounds__(256) void instance_overlaps_kernel(const OverlapK p) {
+    __shared__ int bins[NW][MAXPAIRS];
+    const int tid = threadIdx.x, wv = tid >> 6, K = p.K, S = K + 1, cells = S * S;
+    const uint32_t HW = (uint32_t)p.H * (uint32_t)p.W, total4 = (HW + 3u) >> 2;
+    const size_t f = (size_t)p.f0 + blockIdx.x, g = f + blockIdx.y + 1;
+    int32_t* o = p.out + (f * (size_t)p.L + blockIdx.y) * (size_t)cells;
+    if (g >= (size_t)p.F) {                                          // no partner frame (the same in every thread): the lag's cells are zeros
+        for (int t = tid; t < cells; t += BT) o[t] = 0;
+        return;
+    }
+    const uint8_t* __restrict__ ia = p.imap + f * HW;
+    const uint8_t* __restrict__ ib = p.imap + g * HW;
+    for (int w = 0; w < NW; ++w)
+        for (int t = tid; t < cells; t += BT) bins[w][t] = 0;
+    __syncthreads();
+
+    int cur = -1, cnt = 0;                                           // the pair the thread is in; nothing to flush while cnt == 0
+    for (uint32_t g0 = tid; g0 < total4; g0 += BT * 4) {
+        uint32_t va[4], vb[4];
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+            const uint32_t gr = g0 + u * BT, px = gr << 2;
+            const bool in = gr < total4;
+            va[u] = map_bytes(ia + (in ? px : 0u), in ? (int)(HW - px < 4u ? HW - px : 4u) : 0);
+        }
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+            vb[u] = 0u;
+            if (va[u] == 0u) continue;                               // background (or a group past the frame's end): the partner is not read
+            const uint32_t px = (g0 + u * BT) << 2;
+            vb[u] = map_bytes(ib + px, (int)(HW - px < 4u ? HW - px : 4u));
+        }
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+            if (va[u] == 0u || vb[u] == 0u) continue;
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+                const int a = (int)((va[u] >> (8 * e)) & 0xffu), b = (int)((vb[u] >> (8 * e)) & 0xffu);
+                if (a == 0 || b == 0) continue;
+                const int pair = (a <= K ? a - 1 : K) * S + (b <= K ? b - 1 : K);
+                if (pair != cur) {
+                    if (cnt) atomicAdd(&bins[wv][cur], cnt);
+                    cur = pair; cnt = 0;
+                }
+                ++cnt;
+            }
+        }
+    }
+    if (cnt) atomicAdd(&bins[wv][cur], cnt);
+    __syncthreads();
+    for (int t = tid; t < cells; t += BT) {
+        int n = bins[0][t];
+#pragma unroll
+        for (int w = 1; w < NW; ++w) n += bins[w][t];
+        o[t] = n;
+    }
+}
+
+}  // namespace
+
+extern "C" int pc_instance_overlaps(const uint8_t* imap, int F, int H, int W, int f0, int nf, int K, int L, int32_t* out, pc_stream s) {
+    const char* who = "pc_instance_overlaps";
+    PC_CHECK_ARG(imap && out, "%s: null pointer", who);
+    PC_CHECK_ARG(F >= 1 && H >= 1 && W >= 1, "%s: F = %d frames of %d x %d are outside what a map holds", who, F, H, W);
+    PC_CHECK_ARG((int64_t)H * W < (1ll << 31), "%s: frames of %d x %d pixels are beyond the 2^31 a frame may hold", who, H, W);
+    PC_CHECK_ARG(f0 >= 0 && nf >= 1 && (int64_t)f0 + nf <= F, "%s: frames f0 = %d, nf = %d outside the %d of the map", who, f0, nf, F);
+    PC_CHECK_ARG(K >= 1 && K <= 32, "%s: K = %d outside 1..32", who, K);
+    PC_CHECK_ARG(L >= 1 && L <= PC_LINK_MAX_LAGS, "%s: L = %d outside 1..%d", who, L, PC_LINK_MAX_LAGS);
+    PC_CHECK_ARG((uintptr_t)out % 4 == 0, "%s: out must be 4-byte aligned", who);
+    OverlapK k;
+    k.imap = imap; k.out = out;
+    k.F = F; k.H = H; k.W = W; k.f0 = f0; k.K = K; k.L = L;
+    hipLaunchKernelGGL(instance_overlaps_kernel, dim3((unsigned)nf, (unsigned)L), dim3(BT), 0, (hipStream_t)s, k);
+    PC_CHECK_LAUNCH(who);
+    return PC_OK;
+}

@@ -26,6 +26,10 @@ Instance scores.  With instance_scores=True one pc_frame_probs launch behind eac
 merged logit (uint16, video order; the merge is one device function for mask and probability) until the video's last clip, where one
 pc_instance_scores launch behind pc_frame_instances reduces it per instance: every instance, and with it every per-actor tube, carries the mean
 probability of its own pixels instead of the frame's.
+
+Instance links.  Box IoU swaps two actors whose boxes overlap as soon as their area ranks change.  With instance_links=L one
+pc_instance_overlaps launch behind pc_frame_instances counts, for every frame and each of the L frame distances, the pixels every instance
+shares with every instance of the later frame; link_instance_tubes_by_mask links by the mask IoU that follows from them.
 """
 from types import SimpleNamespace
 
@@ -80,6 +84,50 @@ def link_instance_tubes(inst_kept, inst_boxes, inst_areas, frame_scores, iou_min
     score the float64 mean of frame_scores over the tube's detected frames -- or, with inst_scores [F,K] (Detection.inst_scores), the float64
     mean of the scores of the tube's own instances over those frames; the linking is the same either way.  iou_min = 0.3 is an API default,
     not a measured quantity."""
+    return _link_instances("link_instance_tubes", inst_kept, inst_boxes, inst_areas, frame_scores, iou_min, max_gap, min_len, inst_scores,
+                           lambda boxes, areas: lambda tb, t, r: box_iou(tb["box"], boxes[t, r]))
+
+
+def link_instance_tubes_by_mask(inst_kept, inst_boxes, inst_areas, frame_scores, overlaps, inst_flags=None, iou_min=0.3, max_gap=0, min_len=1,
+                                inst_scores=None):
+    """link_instance_tubes with the MASK IoU as its measure: the same greedy, deterministic procedure, order, max_gap / min_len / score rules
+    and return tuples; only what is compared differs.  overlaps int32 [F, L, K + 1, K + 1] (Detection.inst_overlaps: overlaps[f, l, a, b] the
+    pixels slot a of frame f shares with slot b of frame f + l + 1).  Between a tube's last detected instance (frame tl, rank ra) and the
+    candidate (t, rb): inter = overlaps[tl, t - tl - 1, slot(tl, ra), slot(t, rb)], IoU = inter / (area_a + area_b - inter) in float64, 0
+    when that denominator is 0.  slot(f, r) = r, except in a frame whose inst_flags bit 0 is set (overflow: its map is 255 on all
+    foreground and its one substituted instance holds the frame's count): there it is K.  Slot K of any other frame is foreground no
+    instance holds and links nothing.  max_gap > L - 1: ValueError, no record exists for that lag."""
+    who = "link_instance_tubes_by_mask"
+    ov = np.asarray(overlaps)
+    kept = np.asarray(inst_kept).reshape(-1)
+    F = kept.size
+    if F == 0:
+        return []
+    K = np.asarray(inst_boxes).reshape(F, -1, 4).shape[1]
+    if ov.ndim != 4 or ov.shape[0] != F or ov.shape[1] < 1 or ov.shape[2:] != (K + 1, K + 1):
+        raise ValueError("%s: overlaps %s, expected [%d, L, %d, %d]" % (who, ov.shape, F, K + 1, K + 1))
+    if max_gap > ov.shape[1] - 1:
+        raise ValueError("%s: max_gap = %r needs the overlaps of %d lags, the record holds %d" % (who, max_gap, max_gap + 1, ov.shape[1]))
+    over = np.zeros(F, bool)
+    if inst_flags is not None:
+        flags = np.asarray(inst_flags).reshape(-1)
+        if flags.size != F:
+            raise ValueError("%s: %d flags for %d frames" % (who, flags.size, F))
+        over = (flags & 1) != 0
+
+    def measure(boxes, areas):
+        def mask_iou(tb, t, r):
+            tl, ra = tb["last"], tb["rank"]
+            inter = int(ov[tl, t - tl - 1, K if over[tl] else ra, K if over[t] else r])
+            union = int(areas[tl, ra]) + int(areas[t, r]) - inter
+            return float(inter) / float(union) if union != 0 else 0.0
+        return mask_iou
+    return _link_instances(who, inst_kept, inst_boxes, inst_areas, frame_scores, iou_min, max_gap, min_len, inst_scores, measure)
+
+
+def _link_instances(who, inst_kept, inst_boxes, inst_areas, frame_scores, iou_min, max_gap, min_len, inst_scores, make_measure):
+    """The loop of link_instance_tubes and link_instance_tubes_by_mask.  make_measure(boxes, areas) -> measure(tube, t, r): how well the
+    instance of rank r in frame t continues the tube (a dict with its last detected frame `last`, that instance's `rank` and `box`)."""
     kept = np.asarray(inst_kept).reshape(-1)
     F = kept.size
     if F == 0:
@@ -88,14 +136,15 @@ def link_instance_tubes(inst_kept, inst_boxes, inst_areas, frame_scores, iou_min
     areas = np.asarray(inst_areas).reshape(F, -1)
     scores = np.asarray(frame_scores, np.float64).reshape(-1)
     if not (areas.shape[1] == boxes.shape[1] and scores.size == F) or kept.max() > boxes.shape[1]:
-        raise ValueError("link_instance_tubes: %d frames, boxes %s, areas %s, %d scores" % (F, boxes.shape, areas.shape, scores.size))
+        raise ValueError("%s: %d frames, boxes %s, areas %s, %d scores" % (who, F, boxes.shape, areas.shape, scores.size))
     if inst_scores is not None:
         inst_scores = np.asarray(inst_scores, np.float64).reshape(F, -1)
         if inst_scores.shape[1] != boxes.shape[1]:
-            raise ValueError("link_instance_tubes: inst_scores %s against boxes %s" % (inst_scores.shape, boxes.shape))
+            raise ValueError("%s: inst_scores %s against boxes %s" % (who, inst_scores.shape, boxes.shape))
     if not 0.0 <= iou_min <= 1.0 or max_gap < 0 or min_len < 1:
-        raise ValueError("link_instance_tubes: 0 <= iou_min <= 1, max_gap >= 0, min_len >= 1, got %r, %r, %r" % (iou_min, max_gap, min_len))
-    tubes, live = [], []                                  # a tube: dict(t0, frames {t: rank}, last box, last t)
+        raise ValueError("%s: 0 <= iou_min <= 1, max_gap >= 0, min_len >= 1, got %r, %r, %r" % (who, iou_min, max_gap, min_len))
+    measure = make_measure(boxes, areas)
+    tubes, live = [], []                                  # a tube: dict(t0, frames {t: rank}, last box, last rank, last t)
     for t in range(F):
         n = int(kept[t])
         taken = [False] * n
@@ -104,19 +153,19 @@ def link_instance_tubes(inst_kept, inst_boxes, inst_areas, frame_scores, iou_min
             best, best_iou = -1, -1.0
             for r in range(n):
                 if not taken[r]:
-                    v = box_iou(tb["box"], boxes[t, r])
+                    v = measure(tb, t, r)
                     if v >= iou_min and v > best_iou:
                         best, best_iou = r, v
             if best >= 0:
                 taken[best] = True
                 tb["frames"][t] = best
-                tb["box"], tb["last"] = boxes[t, best], t
+                tb["box"], tb["rank"], tb["last"] = boxes[t, best], best, t
             if t - tb["last"] <= max_gap:
                 still.append(tb)
         live = still
         for r in range(n):
             if not taken[r]:
-                tb = dict(t0=t, frames={t: r}, box=boxes[t, r], last=t)
+                tb = dict(t0=t, frames={t: r}, box=boxes[t, r], rank=r, last=t)
                 tubes.append(tb)
                 live.append(tb)
     out = []
@@ -181,22 +230,42 @@ class Detection:
     With DetectEngine(instance_scores=True) also inst_scores float64 [F, K], the mean probability over the instance's own pixels (zeros from
     inst_kept on; the one instance of an overflow frame: over all of the frame's foreground), other_score float64 [F], that mean over the
     foreground no kept instance holds (0 when there is none), and probs: the device 16-bit [F, H, W] probability map, uint16 steps of
-    1 / 65535.  All None without the option."""
+    1 / 65535.  All None without the option.
 
-    def __init__(self, label, class_score, class_scores, counts, boxes, frame_scores, masks, views=None, inst=None, imap=None, scores=None, probs=None):
+    With DetectEngine(instance_links=L) also inst_overlaps int32 [F, L, K + 1, K + 1]: inst_overlaps[f, l, a, b] the pixels that slot a of
+    frame f shares with slot b of frame f + l + 1 (slot r < K: the instance of rank r; slot K: all other foreground, and ALL foreground of a
+    frame whose overflow flag is set; zeros where frame f + l + 1 does not exist).  None without the option."""
+
+    def __init__(self, label, class_score, class_scores, counts, boxes, frame_scores, masks, views=None, inst=None, imap=None, scores=None, probs=None,
+                 inst_overlaps=None):
         self.label, self.class_score, self.class_scores = label, class_score, class_scores
         self.counts, self.boxes, self.frame_scores, self.masks, self.views = counts, boxes, frame_scores, masks, views
         self.inst_n, self.inst_kept, self.inst_flags, self.inst_areas, self.inst_boxes, self.inst_first = inst if inst is not None else (None,) * 6
         self.imap = imap
         self.inst_scores, self.other_score = scores if scores is not None else (None, None)
         self.probs = probs
+        if inst_overlaps is not None:
+            inst_overlaps = np.asarray(inst_overlaps)
+            K = None if self.inst_areas is None else int(np.asarray(self.inst_areas).shape[-1])
+            if K is None or inst_overlaps.ndim != 4 or inst_overlaps.shape[0] != len(self.counts) or inst_overlaps.shape[2:] != (K + 1, K + 1):
+                raise ValueError("Detection: inst_overlaps %s need instances and the shape [F, L, K + 1, K + 1]" % (inst_overlaps.shape,))
+        self.inst_overlaps = inst_overlaps
 
     def tubes(self, min_pixels=1, max_gap=0):
         return link_tubes(self.counts, self.boxes, self.frame_scores, min_pixels, max_gap)
 
-    def instance_tubes(self, iou_min=0.3, max_gap=0, min_len=1):
+    def instance_tubes(self, iou_min=0.3, max_gap=0, min_len=1, link="box"):
+        """The per-actor tubes: link="box" by box IoU (link_instance_tubes), link="mask" by mask IoU from inst_overlaps
+        (link_instance_tubes_by_mask; max_gap at most L - 1)."""
+        if link not in ("box", "mask"):
+            raise ValueError("instance_tubes: link = %r, \"box\" or \"mask\"" % (link,))
         if self.inst_kept is None:
             raise ValueError("instance_tubes: the detection holds no instances (DetectEngine(instances=K))")
+        if link == "mask":
+            if self.inst_overlaps is None:
+                raise ValueError("instance_tubes: link=\"mask\" needs the overlaps of DetectEngine(instance_links=L); the detection holds none")
+            return link_instance_tubes_by_mask(self.inst_kept, self.inst_boxes, self.inst_areas, self.frame_scores, self.inst_overlaps, self.inst_flags,
+                                               iou_min, max_gap, min_len, self.inst_scores)
         return link_instance_tubes(self.inst_kept, self.inst_boxes, self.inst_areas, self.frame_scores, iou_min, max_gap, min_len, self.inst_scores)
 
 
@@ -259,17 +328,28 @@ class DetectEngine(ClipEngine):
     instance_scores=True (needs instances > 0): one pc_frame_probs launch behind every pc_detect_frames* keeps the per-pixel probability of
     the video (16-bit [F,H,W], Detection.probs), one pc_instance_scores launch behind pc_frame_instances reduces it per instance into
     F * 3 * (K + 1) words behind the instance records: Detection.inst_scores / other_score.  The map of ranks is then made whether or not
-    instance_maps asks for it.  False: nothing of this, no buffer and no launch."""
+    instance_maps asks for it.  False: nothing of this, no buffer and no launch.
+
+    instance_links=L in 1..4 (needs instances > 0): one pc_instance_overlaps launch behind pc_frame_instances counts, for every frame and
+    each of the L frame distances, the pixels every instance shares with every instance of the later frame, into F * L * (K + 1)^2 words
+    behind the score words: Detection.inst_overlaps, and with it instance_tubes(link="mask").  The map of ranks is then made whether or not
+    instance_maps asks for it.  0: nothing of this, no buffer and no launch."""
 
     def __init__(self, bs=14, hw=224, num_classes=24, device="cuda:0", state=None, engine=None, capacity=256, seed=47, f_skip=2, pack=False,
                  masks=True, on_batch=None, tile=False, flip=False, views=None, instances=0, min_area=1, conn=8, instance_maps=False,
-                 instance_scores=False):
+                 instance_scores=False, instance_links=0):
         hw = engine.hw if engine is not None else hw
         self.inst_k, self.min_area, self.conn = check_instances(instances, min_area, conn, masks)
         self.instance_maps = bool(instance_maps) and self.inst_k > 0
         self.instance_scores = bool(instance_scores)
         if self.instance_scores and self.inst_k == 0:
             raise ValueError("DetectEngine: instance_scores=True needs instances > 0 (the scores are reduced over pc_frame_instances' map of ranks)")
+        self.instance_links = int(instance_links)
+        if not 0 <= self.instance_links <= ops.LINK_MAX_LAGS:
+            raise ValueError("DetectEngine: instance_links = %d outside 0..%d" % (self.instance_links, ops.LINK_MAX_LAGS))
+        if self.instance_links and self.inst_k == 0:
+            raise ValueError("DetectEngine: instance_links = %d needs instances > 0 (the overlaps are counted over pc_frame_instances' map of ranks)"
+                             % self.instance_links)
         if hw % 4:
             raise ValueError("DetectEngine: hw = %d must be a multiple of 4 (pc_detect_frames reads the logit rows 16 bytes at a time)" % hw)
         self._setup(bs, hw, num_classes, device, state, engine, capacity, seed, f_skip, pack, on_batch)
@@ -347,9 +427,11 @@ class DetectEngine(ClipEngine):
         rec.inst_words = F * (ops.INST_HDR + self.inst_k * ops.INST_WORDS) if self.inst_k else 0
         # With instance scores the F records of 3 (K + 1) words follow behind those.
         rec.score_words = F * ops.SCORE_WORDS * (self.inst_k + 1) if self.instance_scores else 0
-        rec.dev = torch.empty(F * ops.DETECT_REC_WORDS + self.C + 2 + rec.inst_words + rec.score_words, dtype=torch.int32, device=self.dev)
+        # With instance links the F records of L (K + 1)^2 words follow behind those.
+        rec.link_words = F * self.instance_links * (self.inst_k + 1) ** 2
+        rec.dev = torch.empty(F * ops.DETECT_REC_WORDS + self.C + 2 + rec.inst_words + rec.score_words + rec.link_words, dtype=torch.int32, device=self.dev)
         rec.mask = torch.empty(F, H, W, dtype=torch.uint8, device=self.dev) if self.masks else None
-        rec.imap = torch.empty(F, H, W, dtype=torch.uint8, device=self.dev) if self.instance_maps or self.instance_scores else None
+        rec.imap = torch.empty(F, H, W, dtype=torch.uint8, device=self.dev) if self.instance_maps or self.instance_scores or self.instance_links else None
         rec.prob = torch.empty(F, H, W, dtype=torch.int16, device=self.dev) if self.instance_scores else None
         rec.pin = None
         if views:
@@ -398,7 +480,10 @@ class DetectEngine(ClipEngine):
             ops.frame_instances(rec.mask, conn=self.conn, min_area=self.min_area, K=self.inst_k, inst=rec.dev[inst0:inst0 + rec.inst_words].view(rec.F, -1),
                                 imap=rec.imap, want_imap=False)
             if rec.prob is not None:
-                ops.instance_scores(rec.imap, rec.prob, self.inst_k, out=rec.dev[inst0 + rec.inst_words:].view(rec.F, -1))
+                ops.instance_scores(rec.imap, rec.prob, self.inst_k, out=rec.dev[inst0 + rec.inst_words:inst0 + rec.inst_words + rec.score_words].view(rec.F, -1))
+            if self.instance_links:
+                link0 = inst0 + rec.inst_words + rec.score_words
+                ops.instance_overlaps(rec.imap, self.inst_k, self.instance_links, out=rec.dev[link0:link0 + rec.link_words])
         rec.pin = self._stage(rec.dev.numel())
         rec.pin.copy_(rec.dev, non_blocking=True)
 
@@ -412,16 +497,19 @@ class DetectEngine(ClipEngine):
             counts, boxes, fscores, _rows = ops.decode_detect_records(words[:rec.F * ops.DETECT_REC_WORDS])
             cls0 = rec.F * ops.DETECT_REC_WORDS
             cls = words[cls0:cls0 + self.C + 2].copy().view(np.float32)
-            inst = scores = None
+            inst = scores = overlaps = None
             if self.inst_k:
                 inst0 = cls0 + self.C + 2
                 n, kept, _runs, flags, areas, ibox, first = ops.decode_instances(words[inst0:inst0 + rec.inst_words], self.inst_k)
                 inst = substitute_overflow(counts, boxes, self.min_area, (n, kept, flags, areas, ibox, first))
                 if self.instance_scores:
-                    sums, npix = ops.decode_instance_scores(words[inst0 + rec.inst_words:], self.inst_k)
+                    sums, npix = ops.decode_instance_scores(words[inst0 + rec.inst_words:inst0 + rec.inst_words + rec.score_words], self.inst_k)
                     scores = score_instances(sums, npix, inst[1], inst[2])
+                if self.instance_links:
+                    link0 = inst0 + rec.inst_words + rec.score_words
+                    overlaps = ops.decode_instance_overlaps(words[link0:link0 + rec.link_words], self.inst_k, self.instance_links)
             out.append(Detection(int(cls[self.C]), float(cls[self.C + 1]), cls[:self.C].copy(), counts, boxes, fscores, rec.mask,
-                                 list(rec.views) if rec.views else [(rec.h0, rec.w0, 0)], inst, rec.imap if self.instance_maps else None, scores, rec.prob))
+                                 list(rec.views) if rec.views else [(rec.h0, rec.w0, 0)], inst, rec.imap if self.instance_maps else None, scores, rec.prob, overlaps))
         return out
 
     def detect(self, frames_u8):

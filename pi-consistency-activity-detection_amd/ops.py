@@ -828,6 +828,39 @@ def decode_instance_scores(words, K):
     return (hi << 32) | lo, r[:, :, 2].copy()
 
 
+LINK_MAX_LAGS = 4                          # PC_LINK_MAX_LAGS of include/picons.h: the frame distances one overlap record covers
+
+
+def instance_overlaps(imap, K, L=1, f0=0, nf=None, out=None):
+    """pc_instance_overlaps: imap contiguous uint8 device [F,H,W] (frame_instances' map of ranks) -> out int32 [F, L, K + 1, K + 1]:
+    out[f, l, a, b] the pixels whose slot is a in frame f and b in frame f + l + 1 (slot K: all other foreground; zeros where that frame
+    does not exist), for the frames f0 .. f0 + nf - 1 (default: all from f0 on).  A given out is written in place -- only those frames -- a
+    fresh one is zero-filled first."""
+    if imap.dtype != torch.uint8 or imap.dim() != 3 or not imap.is_contiguous():
+        raise ValueError("instance_overlaps: contiguous uint8 [F,H,W] imap")
+    F, H, W = (int(v) for v in imap.shape)
+    K, L = int(K), int(L)
+    if not 1 <= K <= INST_MAX_K:
+        raise ValueError("instance_overlaps: K = %d outside 1..%d" % (K, INST_MAX_K))
+    if not 1 <= L <= LINK_MAX_LAGS:
+        raise ValueError("instance_overlaps: L = %d outside 1..%d" % (L, LINK_MAX_LAGS))
+    words = L * (K + 1) * (K + 1)
+    nf = F - int(f0) if nf is None else int(nf)
+    if out is None:
+        out = torch.zeros(F, L, K + 1, K + 1, dtype=torch.int32, device=imap.device)
+    elif out.dtype != torch.int32 or not out.is_contiguous() or out.numel() != F * words or out.device != imap.device:
+        raise ValueError("instance_overlaps: out must be a contiguous int32 device tensor [F, %d, %d, %d]" % (L, K + 1, K + 1))
+    capi.call("pc_instance_overlaps", ptr(imap), F, H, W, int(f0), nf, K, L, ptr(out), stream())
+    return out
+
+
+def decode_instance_overlaps(words, K, L):
+    """Host int32 records of F * L * (K + 1)^2 words (numpy or torch, any shape) -> int32 [F, L, K + 1, K + 1]."""
+    K, L = int(K), int(L)
+    r = np.ascontiguousarray(words.cpu().numpy() if torch.is_tensor(words) else words, dtype=np.int32)
+    return r.reshape(-1, L, K + 1, K + 1).copy()
+
+
 def video_class(scores, out=None):
     """pc_video_class: scores contiguous float32 device [n,C] -> float32 device [C + 2]: mean class scores, arg-max (as a float), its mean."""
     if scores.dtype != torch.float32 or scores.dim() != 2 or not scores.is_contiguous():

@@ -14,9 +14,13 @@ inst_tubes_i [T,3] = (t0, t1 inclusive, score) with inst_tube_boxes_i [sum of th
 --instance_maps also imap_i, the uint8 map of ranks [F,H,W] as it is (imap_shape_i).
 --instance_scores (needs --instances K > 0): a confidence per instance, inst_scores_i [F,K] the mean probability over the instance's own pixels
 and other_score_i [F] that over the foreground no kept instance holds; the scores of inst_tubes_i are then the means of their own instances'.
+--instance_links L (1..4, needs --instances K > 0): inst_overlaps_i int32 [F, L, K + 1, K + 1], the pixels slot a of frame f shares with slot b
+of frame f + l + 1, counted on the device; --link mask then links inst_tubes_i by mask IoU from them (--max-gap at most L - 1) instead of by
+box IoU (--link box, the default).
 
     python tools/detect.py --out detections.npz [--ckpt best_model.pth] [--synthetic 4 | video.npy ...] [--masks] [--pack] [--tile] [--flip]
                            [--max-gap 0] [--min-pixels 1] [--instances K] [--min_area 1] [--conn 8] [--instance_maps] [--instance_scores]
+                           [--instance_links L] [--link box|mask]
 """
 import argparse
 import os
@@ -50,9 +54,17 @@ def main():
     ap.add_argument("--conn", type=int, default=8, choices=(4, 8))
     ap.add_argument("--instance_maps", action="store_true", help="with --instances: also the uint8 map of ranks per frame")
     ap.add_argument("--instance_scores", action="store_true", help="with --instances: a confidence per instance and per instance tube")
+    ap.add_argument("--instance_links", type=int, default=0, help="with --instances: mask overlaps between frames up to L apart (pc_instance_overlaps)")
+    ap.add_argument("--link", default="box", choices=("box", "mask"), help="link the instance tubes by box IoU or, with --instance_links, by mask IoU")
     a = ap.parse_args()
     if a.instance_scores and a.instances <= 0:
         raise SystemExit("tools/detect.py: --instance_scores needs --instances K with K > 0 (the scores are reduced per instance)")
+    if a.instance_links and a.instances <= 0:
+        raise SystemExit("tools/detect.py: --instance_links needs --instances K with K > 0 (the overlaps are counted between instances)")
+    if a.link == "mask" and a.instance_links <= 0:
+        raise SystemExit("tools/detect.py: --link mask needs --instance_links L with L > 0 (the mask IoU comes from the overlaps)")
+    if a.link == "mask" and a.max_gap > a.instance_links - 1:
+        raise SystemExit("tools/detect.py: --link mask with --max-gap %d needs --instance_links %d or more" % (a.max_gap, a.max_gap + 1))
     if not torch.cuda.is_available():
         raise SystemExit("tools/detect.py needs a GPU: the hot path is HIP-only (no CPU fallback)")
     if a.ckpt:
@@ -70,7 +82,7 @@ def main():
         names = ["synthetic_%d" % i for i in range(n)]
     engine = detect.DetectEngine(bs=a.bs, hw=a.hw, num_classes=a.classes, state=state, pack=a.pack, masks=a.masks or a.instances > 0, tile=a.tile,
                                  flip=a.flip, instances=a.instances, min_area=a.min_area, conn=a.conn, instance_maps=a.instance_maps,
-                                 instance_scores=a.instance_scores)
+                                 instance_scores=a.instance_scores, instance_links=a.instance_links)
     engine.begin()
     for v in videos:
         engine.add_video(v)
@@ -85,13 +97,15 @@ def main():
             out.update({"masks_%d" % i: np.packbits(m), "mask_shape_%d" % i: np.array(m.shape, np.int64)})
         itubes = []
         if a.instances:
-            itubes = d.instance_tubes(max_gap=a.max_gap)
+            itubes = d.instance_tubes(max_gap=a.max_gap, link=a.link)
             out.update({"inst_n_%d" % i: d.inst_n, "inst_kept_%d" % i: d.inst_kept, "inst_flags_%d" % i: d.inst_flags, "inst_areas_%d" % i: d.inst_areas,
                         "inst_boxes_%d" % i: d.inst_boxes, "inst_first_%d" % i: d.inst_first,
                         "inst_tubes_%d" % i: np.array([(t0, t1, s) for t0, t1, _b, _a, s in itubes], np.float64).reshape(-1, 3),
                         "inst_tube_boxes_%d" % i: np.concatenate([t[2] for t in itubes] + [np.zeros((0, 4), np.int32)]).astype(np.int32)})
             if d.inst_scores is not None:
                 out.update({"inst_scores_%d" % i: d.inst_scores, "other_score_%d" % i: d.other_score})
+            if d.inst_overlaps is not None:
+                out["inst_overlaps_%d" % i] = d.inst_overlaps
             if d.imap is not None:
                 m = d.imap.cpu().numpy()
                 out.update({"imap_%d" % i: m, "imap_shape_%d" % i: np.array(m.shape, np.int64)})
