@@ -67,8 +67,8 @@ typedef void* pc_stream;            /* hipStream_t */
  * 106: pc_truth_frame_flags / pc_eval_clips_from_u8 / pc_video_vote;
  * 107: pc_clips_from_u8 / pc_detect_frames / pc_detect_frames_ws_bytes / pc_video_class; the entries pc_clips_from_u8_views / pc_detect_frames_views /
  * pc_detect_frames_views_ws_bytes came later and move nothing: no struct grew, no op's operands changed; so did pc_frame_instances with its
- * PC_INST_* constants, pc_frame_probs / pc_instance_scores with PC_PROB_ONE / PC_SCORE_WORDS, and pc_instance_overlaps with PC_LINK_MAX_LAGS:
- * came later, move nothing).  Descriptors must be zero-initialised by the caller:
+ * PC_INST_* constants, pc_frame_probs / pc_instance_scores with PC_PROB_ONE / PC_SCORE_WORDS, pc_instance_overlaps with PC_LINK_MAX_LAGS, and pc_mask_run_ws_bytes /
+ * pc_mask_run_index / pc_mask_runs with PC_RUN_WORDS: came later, move nothing).  Descriptors must be zero-initialised by the caller:
  * fields added later read as "old behaviour" when 0.  pc_version() returns the value the library was built with; the Python host
  * (capi.lib()) refuses a library whose version differs from the header it mirrors. */
 #define PC_VERSION 107
@@ -507,6 +507,30 @@ int     pc_instance_scores(const uint8_t* imap, const uint16_t* prob, int F, int
  * nf < 1, f0 + nf > F; K outside 1..32; L outside 1..PC_LINK_MAX_LAGS; out not 4-byte aligned. */
 #define PC_LINK_MAX_LAGS 4
 int     pc_instance_overlaps(const uint8_t* imap, int F, int H, int W, int f0, int nf, int K, int L, int32_t* out, pc_stream s);
+/* Masks and maps of ranks as row runs (csrc/maskruns.hip; picons_amd/detect.py: DetectEngine.mask_runs, MaskRuns).  map uint8 [F][H][W] (a
+ * frame may start at any byte address; frame offsets are 64-bit); only the frames f0 .. f0 + nf - 1, the RANGE, are read, and its rows are
+ * numbered r = (f - f0) * H + y.  A RUN is a maximal horizontal segment of pixels with the same NON-ZERO byte value: value 0 belongs to no
+ * run, two touching segments of different values are two runs.  For a 0 / 1 mask of pc_detect_frames* these are the foreground runs with
+ * value 1, for the imap of pc_frame_instances the runs of each rank (r + 1) and of 255.
+ * pc_mask_run_index writes the WHOLE of index int32 [nf * H + 1]: index[r] = the runs in the rows before row r of the range (raster order),
+ * index[nf * H] = the range's total.  ws: pc_mask_run_ws_bytes(nf, H) bytes, 4-byte aligned, contents irrelevant before the call and
+ * meaningless after it; nothing has to be zeroed.  Three launches: a count per row on a grid over bands of 32 rows (band sums into ws), one
+ * block that scans the band sums, one launch that adds them back.
+ * pc_mask_runs, with the index of the same map and range, writes runs uint32 [cap][PC_RUN_WORDS] in raster order: run index[r] + j is the
+ * j-th run of row r from the left,
+ *   runs[i][0] = r | value << 24        runs[i][1] = x0 | x1 << 16   (columns x0 .. x1 - 1: x1 half-open, at most 65535)
+ * A run with i >= cap is not written and no byte at or behind runs[cap] is touched; cap = 0 with a non-null runs is legal and writes
+ * nothing.  The true total is index[nf * H]: a buffer that is too small shows as total > cap, never as a corruption.  One launch on the
+ * grid of the count.
+ * No atomics of any kind, no floating point, nothing waits on another block, every loop's trip count fixed before it starts: bit-identical
+ * from run to run.  pc_mask_run_ws_bytes is host arithmetic: -1 for nf < 1, H < 1 or nf * H > 2^24.  Refusals of the two calls (PC_E_ARG
+ * before any HIP call, nothing allocated, enqueued on `s` only): null map / index / ws; null runs with cap > 0; cap < 0; F, H, W < 1;
+ * W > 65535; f0 < 0, nf < 1, f0 + nf > F; nf * H > 2^24 (the row field); nf * H * W >= 2^31 (a run count is an int32: a longer video is
+ * exported in ranges); index, runs or ws not 4-byte aligned. */
+#define PC_RUN_WORDS 2
+int64_t pc_mask_run_ws_bytes(int nf, int H);
+int     pc_mask_run_index(const uint8_t* map, int F, int H, int W, int f0, int nf, int32_t* index, void* ws, pc_stream s);
+int     pc_mask_runs(const uint8_t* map, int F, int H, int W, int f0, int nf, const int32_t* index, int64_t cap, uint32_t* runs, pc_stream s);
 /* cv2.resize on uint8 images [n][H][W][C] -> [n][Ho][Wo][C] (C <= 4), the calls of the reference's loaders:
  * datasets/jhmdb_dataloader.py:252 (frames, INTER_AREA 320x240 -> 256x256), :267,:281 (puppet masks, INTER_NEAREST),
  * :192,:208 and ucf_dataloader.py:165,171 (224 crop -> frame size, INTER_LINEAR; the identity at 224).  OpenCV's 8-bit

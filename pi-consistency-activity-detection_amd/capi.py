@@ -156,6 +156,9 @@ _SIGS = {
     "pc_frame_probs": (i32, [vp, i32, i32, i32, i32, C.POINTER(C.c_int32), i32, i32, C.POINTER(C.c_int32), i32, i32, vp, vp]),
     "pc_instance_scores": (i32, [vp, vp, i32, i32, i32, i32, i32, i32, vp, vp]),
     "pc_instance_overlaps": (i32, [vp, i32, i32, i32, i32, i32, i32, i32, vp, vp]),
+    "pc_mask_run_ws_bytes": (i64, [i32, i32]),
+    "pc_mask_run_index": (i32, [vp, i32, i32, i32, i32, i32, vp, vp, vp]),
+    "pc_mask_runs": (i32, [vp, i32, i32, i32, i32, i32, vp, i64, vp, vp]),
     "pc_resize_tables": (i64, [i32, i32, i32, i32, i32, vp, i64]),
     "pc_resize_u8": (i32, [vp, i32, i32, i32, i32, i32, i32, vp, i32, vp, vp]),
     "pc_fill": (i32, [vp, i64, f32, vp]),

@@ -30,6 +30,10 @@ probability of its own pixels instead of the frame's.
 Instance links.  Box IoU swaps two actors whose boxes overlap as soon as their area ranks change.  With instance_links=L one
 pc_instance_overlaps launch behind pc_frame_instances counts, for every frame and each of the L frame distances, the pixels every instance
 shares with every instance of the later frame; link_instance_tubes_by_mask links by the mask IoU that follows from them.
+
+Mask runs.  The masks (and the maps of ranks) stay on the device; DetectEngine.mask_runs, called after results(), brings those of a whole
+pass to the host as row runs -- pc_mask_run_index / pc_mask_runs per video, two host waits per call -- in MaskRuns objects: a frame of a
+few blobs is 1-2 KB instead of its H * W bytes.
 """
 from types import SimpleNamespace
 
@@ -269,6 +273,89 @@ class Detection:
         return link_instance_tubes(self.inst_kept, self.inst_boxes, self.inst_areas, self.frame_scores, iou_min, max_gap, min_len, self.inst_scores)
 
 
+RUN_RANGE_ROWS, RUN_RANGE_PIXELS = ops.RUN_MAX_ROWS, ops.RUN_MAX_PIXELS      # what one pc_mask_run_index / pc_mask_runs range may hold
+
+
+class MaskRuns:
+    """One video's mask (or map of ranks) as row runs, on the host.  shape = (F, H, W); runs uint32 [n, 2] in raster order over the whole
+    video: runs[i] = (row | value << 24, x0 | x1 << 16) with row = f * H + y, the columns x0 .. x1 - 1 and the pixels' byte value (1 for a
+    mask; rank + 1 or 255 for a map of ranks) -- the words pc_mask_runs writes; offsets int64 [F + 1]: frame f holds the runs
+    offsets[f] .. offsets[f + 1] - 1.  A run is a maximal horizontal segment of one non-zero value: value 0 belongs to no run."""
+
+    def __init__(self, shape, offsets, runs):
+        F, H, W = (int(v) for v in shape)
+        self.shape = (F, H, W)
+        self.offsets = np.ascontiguousarray(offsets, dtype=np.int64).reshape(-1)
+        runs = np.ascontiguousarray(runs)
+        if runs.dtype not in (np.uint32, np.int32):
+            raise ValueError("MaskRuns: runs must be 32-bit words, got %s" % runs.dtype)
+        self.runs = runs.view(np.uint32).reshape(-1, ops.RUN_WORDS)
+        if F < 1 or H < 1 or not 1 <= W <= 65535 or F * H > ops.RUN_MAX_ROWS:
+            raise ValueError("MaskRuns: %d frames of %d x %d: W <= 65535 and F * H <= 2^24 (the row field of a run)" % (F, H, W))
+        if self.offsets.size != F + 1 or self.offsets[0] != 0 or self.offsets[-1] != self.runs.shape[0] or (np.diff(self.offsets) < 0).any():
+            raise ValueError("MaskRuns: offsets %s do not split %d runs over %d frames" % (self.offsets.shape, self.runs.shape[0], F))
+
+    @classmethod
+    def from_dense(cls, array):
+        """The runs of a uint8 array [F, H, W] (or one frame [H, W]), encoded on the host: the format the device writes."""
+        a = np.asarray(array)
+        if a.dtype != np.uint8 or a.ndim not in (2, 3):
+            raise ValueError("MaskRuns.from_dense: uint8 [F, H, W] or [H, W], got %s %s" % (a.dtype, a.shape))
+        a = a.reshape((-1,) + a.shape[-2:])
+        F, H, W = a.shape
+        rows = np.zeros((F * H, W + 2), np.int16)                     # a zero in front of and behind every row
+        rows[:, 1:-1] = a.reshape(F * H, W)
+        change = rows[:, 1:] != rows[:, :-1]                          # change[r, x]: pixel x differs from pixel x - 1 (x = W: the zero behind)
+        sr, sx = np.nonzero(change[:, :-1] & (rows[:, 1:-1] != 0))    # starts: non-zero and unlike the pixel to the left
+        er, ex = np.nonzero(change[:, 1:] & (rows[:, 1:-1] != 0))     # ends: non-zero and unlike the pixel to the right; the j-th end closes the j-th start
+        runs = np.empty((sr.size, ops.RUN_WORDS), np.uint32)
+        runs[:, 0] = sr.astype(np.uint32) | (rows[sr, sx + 1].astype(np.uint32) << 24)
+        runs[:, 1] = sx.astype(np.uint32) | ((ex + 1).astype(np.uint32) << 16)
+        offsets = np.searchsorted(sr, np.arange(F + 1, dtype=np.int64) * H).astype(np.int64)
+        return cls((F, H, W), offsets, runs)
+
+    @property
+    def nbytes(self):
+        return int(self.runs.nbytes + self.offsets.nbytes)
+
+    def frame(self, f):
+        """-> (y, x0, x1, value) int32 arrays of frame f's runs, raster order; x1 half-open."""
+        F, H, _W = self.shape
+        f = int(f)
+        if not 0 <= f < F:
+            raise ValueError("MaskRuns.frame: frame %d outside 0..%d" % (f, F - 1))
+        r = self.runs[self.offsets[f]:self.offsets[f + 1]]
+        return ((r[:, 0] & 0xffffff).astype(np.int32) - f * H, (r[:, 1] & 0xffff).astype(np.int32), (r[:, 1] >> 16).astype(np.int32),
+                (r[:, 0] >> 24).astype(np.int32))
+
+    def areas(self):
+        """-> int64 [F]: the pixels of every frame's runs, the sum of x1 - x0."""
+        length = (self.runs[:, 1] >> 16).astype(np.int64) - (self.runs[:, 1] & 0xffff).astype(np.int64)
+        csum = np.concatenate([np.zeros(1, np.int64), np.cumsum(length, dtype=np.int64)])
+        return csum[self.offsets[1:]] - csum[self.offsets[:-1]]
+
+    def dense(self, f=None):
+        """-> uint8 [H, W] of frame f, or [F, H, W] of the whole video."""
+        F, H, W = self.shape
+        if f is None:
+            return ops.decode_mask_runs(self.runs, F, H, W)
+        f = int(f)
+        if not 0 <= f < F:
+            raise ValueError("MaskRuns.dense: frame %d outside 0..%d" % (f, F - 1))
+        r = self.runs[self.offsets[f]:self.offsets[f + 1]].copy()
+        r[:, 0] -= np.uint32(f * H)
+        return ops.decode_mask_runs(r, 1, H, W)[0]
+
+
+def run_ranges(F, H, W):
+    """The frame ranges (f0, nf) in which a video of F frames of H x W goes through pc_mask_run_index / pc_mask_runs: as few as keep
+    nf * H * W below 2^31 and nf * H within 2^24."""
+    per = min(RUN_RANGE_PIXELS // (H * W), RUN_RANGE_ROWS // H)
+    if per < 1:
+        raise ValueError("mask_runs: one frame of %d x %d is beyond what a range holds" % (H, W))
+    return [(f0, min(per, F - f0)) for f0 in range(0, F, per)]
+
+
 def check_instances(instances, min_area, conn, masks):
     """The instance arguments of DetectEngine -> (K, min_area, conn) as ints, or ValueError."""
     K, min_area, conn = int(instances), int(min_area), int(conn)
@@ -362,6 +449,7 @@ class DetectEngine(ClipEngine):
         # upload staging: two page-locked slots, so that the host fills one while the copy stream still reads the other (EvalEngine has one:
         # it waits for every video's flags).  A slot is filled again once the upload of two videos ago has left it.
         self.up_pin, self.up_done, self.up_slot = [None, None], [None, None], 0
+        self.run_pins = [None, None]         # page-locked staging of mask_runs: per-frame offsets, runs
         self._clear()
 
     def _clear(self):
@@ -511,6 +599,78 @@ class DetectEngine(ClipEngine):
             out.append(Detection(int(cls[self.C]), float(cls[self.C + 1]), cls[:self.C].copy(), counts, boxes, fscores, rec.mask,
                                  list(rec.views) if rec.views else [(rec.h0, rec.w0, 0)], inst, rec.imap if self.instance_maps else None, scores, rec.prob, overlaps))
         return out
+
+    def mask_runs(self, which="masks", videos=None):
+        """The masks (which="masks") or the maps of ranks (which="imap": needs instance_maps=True) of the last pass as row runs -> [MaskRuns],
+        one per video in arrival order, or per index in `videos`.  Called after results(); it changes nothing results() returned and can be
+        called again.  Two host waits per call, however many videos: every video's runs are counted (pc_mask_run_index; a video of 2^31
+        pixels or more in several frame ranges) and the per-frame offsets gathered into page-locked memory -- first wait --, then one buffer
+        of exactly the pass's runs is filled (pc_mask_runs per range) and leaves in one asynchronous copy -- second wait.  Every refusal is a
+        ValueError before anything is enqueued."""
+        if which not in ("masks", "imap"):
+            raise ValueError("mask_runs: which = %r, \"masks\" or \"imap\"" % (which,))
+        if which == "masks" and not self.masks:
+            raise ValueError("mask_runs: the engine keeps no masks (masks=False)")
+        if which == "imap" and not self.instance_maps:
+            raise ValueError("mask_runs: the engine keeps no maps of ranks (instances=K with instance_maps=True)")
+        if not self.videos or any(rec.pin is None for rec in self.videos):
+            raise ValueError("mask_runs: no finished pass (call it after results())")
+        picks = list(range(len(self.videos))) if videos is None else [int(v) for v in videos]
+        for v in picks:
+            if not 0 <= v < len(self.videos):
+                raise ValueError("mask_runs: video %d outside the %d of the pass" % (v, len(self.videos)))
+        jobs = []                                                     # (map, f0, nf, first word of its offsets in the staging)
+        words = 0
+        for v in picks:
+            rec = self.videos[v]
+            if rec.F * rec.H > ops.RUN_MAX_ROWS:
+                raise ValueError("mask_runs: video %d has %d rows, more than the 2^24 a run's row field numbers" % (v, rec.F * rec.H))
+            for f0, nf in run_ranges(rec.F, rec.H, rec.W):
+                jobs.append((rec.mask if which == "masks" else rec.imap, f0, nf, words))
+                words += nf + 1
+        stream = torch.cuda.current_stream(self.dev)
+        # ---- phase 1: the index of every range; its entries at the frame starts and the total (index[::H]) to the host
+        off_dev = torch.empty(words, dtype=torch.int32, device=self.dev)
+        off_pin = self._run_stage(0, words)
+        indexes = []
+        for m, f0, nf, w0 in jobs:
+            index = ops.mask_run_index(m, f0, nf)
+            off_dev[w0:w0 + nf + 1] = index[::int(m.shape[1])]
+            indexes.append(index)
+        off_pin.copy_(off_dev, non_blocking=True)
+        stream.synchronize()
+        offs = off_pin.numpy().astype(np.int64)
+        # ---- phase 2: one buffer of exactly the runs, filled range by range, one copy
+        starts = np.zeros(len(jobs) + 1, np.int64)
+        for j, (_m, _f0, nf, w0) in enumerate(jobs):
+            starts[j + 1] = starts[j] + offs[w0 + nf]
+        total = int(starts[-1])
+        run_dev = torch.empty(total, ops.RUN_WORDS, dtype=torch.int32, device=self.dev)
+        for j, (m, f0, nf, _w0) in enumerate(jobs):
+            ops.mask_runs(m, indexes[j], f0, nf, runs=run_dev[int(starts[j]):int(starts[j + 1])])
+        run_pin = self._run_stage(1, total * ops.RUN_WORDS)
+        run_pin.copy_(run_dev.view(-1), non_blocking=True)
+        stream.synchronize()
+        words_host = run_pin.numpy().view(np.uint32).reshape(-1, ops.RUN_WORDS)
+        out, j = [], 0
+        for v in picks:
+            rec = self.videos[v]
+            ranges = run_ranges(rec.F, rec.H, rec.W)
+            runs = words_host[int(starts[j]):int(starts[j + len(ranges)])].copy()          # the staging is used again by the next call
+            offsets = np.zeros(rec.F + 1, np.int64)
+            for k, (f0, nf) in enumerate(ranges):
+                w0, lo = jobs[j + k][3], int(starts[j + k] - starts[j])
+                offsets[f0 + 1:f0 + nf + 1] = lo + offs[w0 + 1:w0 + nf + 1]
+                runs[lo:lo + int(offs[w0 + nf]), 0] += np.uint32(f0 * rec.H)                 # rows of the range -> rows of the video
+            out.append(MaskRuns((rec.F, rec.H, rec.W), offsets, runs))
+            j += len(ranges)
+        return out
+
+    def _run_stage(self, slot, words):
+        """`words` int32 of page-locked memory for mask_runs (slot 0: offsets, 1: runs), kept between calls and grown when too small."""
+        if self.run_pins[slot] is None or self.run_pins[slot].numel() < words:
+            self.run_pins[slot] = torch.empty(max(words, 1024), dtype=torch.int32).pin_memory()
+        return self.run_pins[slot][:words]
 
     def detect(self, frames_u8):
         """One video on its own: begin(), add_video, results()[0]."""

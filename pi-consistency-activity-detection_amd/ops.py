@@ -861,6 +861,78 @@ def decode_instance_overlaps(words, K, L):
     return r.reshape(-1, L, K + 1, K + 1).copy()
 
 
+RUN_WORDS = 2                              # PC_RUN_WORDS of include/picons.h: a run is (row | value << 24, x0 | x1 << 16)
+RUN_MAX_ROWS, RUN_MAX_PIXELS = 1 << 24, (1 << 31) - 1      # what one range of pc_mask_run_index / pc_mask_runs may hold
+
+
+def _run_range(who, map, f0, nf):
+    """The map and frame range of mask_run_index / mask_runs -> (F, H, W, f0, nf), or ValueError."""
+    if not torch.is_tensor(map) or map.dtype != torch.uint8 or map.dim() != 3 or not map.is_contiguous():
+        raise ValueError("%s: contiguous uint8 [F,H,W] map" % who)
+    F, H, W = (int(v) for v in map.shape)
+    f0 = int(f0)
+    nf = F - f0 if nf is None else int(nf)
+    if f0 < 0 or nf < 1 or f0 + nf > F:
+        raise ValueError("%s: frames f0 = %d, nf = %d outside the %d of the map" % (who, f0, nf, F))
+    if H < 1 or not 1 <= W <= 65535 or nf * H > RUN_MAX_ROWS or nf * H * W > RUN_MAX_PIXELS:
+        raise ValueError("%s: %d frames of %d x %d: W <= 65535, nf * H <= 2^24 and nf * H * W < 2^31 (export a longer video in ranges)" % (who, nf, H, W))
+    return F, H, W, f0, nf
+
+
+def mask_run_index(map, f0=0, nf=None, index=None):
+    """pc_mask_run_index: map contiguous uint8 device [F,H,W] -> index int32 device [nf * H + 1] for the frames f0 .. f0 + nf - 1 (default: all
+    from f0 on): index[r] the row runs (maximal horizontal segments of one non-zero byte value) in the rows before row r = (f - f0) * H + y,
+    index[nf * H] their total.  A given index is written in place, all of it."""
+    F, H, W, f0, nf = _run_range("mask_run_index", map, f0, nf)
+    if index is None:
+        index = torch.empty(nf * H + 1, dtype=torch.int32, device=map.device)
+    elif index.dtype != torch.int32 or not index.is_contiguous() or index.numel() != nf * H + 1 or index.device != map.device:
+        raise ValueError("mask_run_index: index must be a contiguous int32 device tensor [%d]" % (nf * H + 1))
+    ws = torch.empty(capi.lib().pc_mask_run_ws_bytes(nf, H) // 4, dtype=torch.int32, device=map.device)
+    capi.call("pc_mask_run_index", ptr(map), F, H, W, f0, nf, ptr(index), ptr(ws), stream())
+    return index
+
+
+def mask_runs(map, index, f0=0, nf=None, cap=None, runs=None):
+    """pc_mask_runs: map and the index mask_run_index made for the same range -> runs int32 device [cap, 2] (uint32 words: int32 is the dtype
+    every torch build can allocate and copy; .cpu().numpy().view(np.uint32) on the host) in raster order: (row | value << 24, x0 | x1 << 16).
+    cap=None: the range's total is read from the index -- ONE host wait -- and the tensor holds exactly the runs.  A given cap: no wait; runs
+    from cap on are not written (compare index[-1] with cap).  A given runs tensor [cap, 2] is written in place."""
+    F, H, W, f0, nf = _run_range("mask_runs", map, f0, nf)
+    if not torch.is_tensor(index) or index.dtype != torch.int32 or not index.is_contiguous() or index.numel() != nf * H + 1 or index.device != map.device:
+        raise ValueError("mask_runs: index must be a contiguous int32 device tensor [%d]" % (nf * H + 1))
+    if cap is None:
+        cap = int(index[-1].item()) if runs is None else runs.numel() // RUN_WORDS
+    cap = int(cap)
+    if cap < 0:
+        raise ValueError("mask_runs: cap = %d below 0" % cap)
+    if runs is None:
+        runs = torch.empty(cap, RUN_WORDS, dtype=torch.int32, device=map.device)
+    elif runs.dtype != torch.int32 or not runs.is_contiguous() or runs.numel() != cap * RUN_WORDS or runs.device != map.device:
+        raise ValueError("mask_runs: runs must be a contiguous int32 device tensor [%d, %d]" % (cap, RUN_WORDS))
+    capi.call("pc_mask_runs", ptr(map), F, H, W, f0, nf, ptr(index), cap, ptr(runs), stream())
+    return runs
+
+
+def decode_mask_runs(runs, nf, H, W):
+    """Host runs [n, 2] (numpy or torch, int32 or uint32 words) with rows numbered from 0 over nf frames of H rows -> numpy uint8 [nf, H, W]:
+    every run's value on its pixels, 0 elsewhere.  ValueError for a run outside the frames."""
+    nf, H, W = int(nf), int(H), int(W)
+    r = np.ascontiguousarray(runs.cpu().numpy() if torch.is_tensor(runs) else runs)
+    if r.dtype not in (np.int32, np.uint32) or r.size % RUN_WORDS:
+        raise ValueError("decode_mask_runs: runs must be 32-bit words [n, %d], got %s %s" % (RUN_WORDS, r.dtype, r.shape))
+    r = r.view(np.uint32).reshape(-1, RUN_WORDS)
+    row, val = (r[:, 0] & 0xffffff).astype(np.int64), (r[:, 0] >> 24).astype(np.int16)
+    x0, x1 = (r[:, 1] & 0xffff).astype(np.int64), (r[:, 1] >> 16).astype(np.int64)
+    if r.shape[0] and (row.max() >= nf * H or x1.max() > W or (x0 >= x1).any() or (val == 0).any()):
+        raise ValueError("decode_mask_runs: a run outside %d frames of %d x %d, empty, or of value 0" % (nf, H, W))
+    # a step up at x0 and down at x1, summed along the row: runs of one row do not overlap, so each (row, x0) and each (row, x1) occurs once
+    d = np.zeros((nf * H, W + 1), np.int16)
+    d[row, x0] += val
+    d[row, x1] -= val
+    return np.cumsum(d[:, :W], axis=1, dtype=np.int16).astype(np.uint8).reshape(nf, H, W)
+
+
 def video_class(scores, out=None):
     """pc_video_class: scores contiguous float32 device [n,C] -> float32 device [C + 2]: mean class scores, arg-max (as a float), its mean."""
     if scores.dtype != torch.float32 or scores.dim() != 2 or not scores.is_contiguous():

@@ -17,10 +17,15 @@ and other_score_i [F] that over the foreground no kept instance holds; the score
 --instance_links L (1..4, needs --instances K > 0): inst_overlaps_i int32 [F, L, K + 1, K + 1], the pixels slot a of frame f shares with slot b
 of frame f + l + 1, counted on the device; --link mask then links inst_tubes_i by mask IoU from them (--max-gap at most L - 1) instead of by
 box IoU (--link box, the default).
+--mask_runs (implies masks on the device): the masks as ROW RUNS made on the device (DetectEngine.mask_runs: two host waits for the whole
+pass, a frame of a few blobs is 1-2 KB): mask_runs_i uint32 [n,2] = (row | value << 24, x0 | x1 << 16) with row = f * H + y and x1 half-open,
+mask_run_offsets_i int64 [F + 1] (frame f holds the runs offsets[f] .. offsets[f + 1] - 1) and mask_shape_i; detect.MaskRuns(shape, offsets,
+runs).dense() gives the uint8 masks back.  With --instance_maps also imap_runs_i / imap_run_offsets_i (value: rank + 1, or 255), and imap_i
+is then not written raw.  Runs are for blob masks: a noisy mask of density 0.5 holds about W / 4 runs of 8 bytes a row, more than its bytes.
 
     python tools/detect.py --out detections.npz [--ckpt best_model.pth] [--synthetic 4 | video.npy ...] [--masks] [--pack] [--tile] [--flip]
                            [--max-gap 0] [--min-pixels 1] [--instances K] [--min_area 1] [--conn 8] [--instance_maps] [--instance_scores]
-                           [--instance_links L] [--link box|mask]
+                           [--instance_links L] [--link box|mask] [--mask_runs]
 """
 import argparse
 import os
@@ -56,6 +61,7 @@ def main():
     ap.add_argument("--instance_scores", action="store_true", help="with --instances: a confidence per instance and per instance tube")
     ap.add_argument("--instance_links", type=int, default=0, help="with --instances: mask overlaps between frames up to L apart (pc_instance_overlaps)")
     ap.add_argument("--link", default="box", choices=("box", "mask"), help="link the instance tubes by box IoU or, with --instance_links, by mask IoU")
+    ap.add_argument("--mask_runs", action="store_true", help="the masks (with --instance_maps: and the maps of ranks) as row runs made on the device")
     a = ap.parse_args()
     if a.instance_scores and a.instances <= 0:
         raise SystemExit("tools/detect.py: --instance_scores needs --instances K with K > 0 (the scores are reduced per instance)")
@@ -80,14 +86,19 @@ def main():
         n = a.synthetic or 4
         videos = [v[0] for v in synthetic.make_eval_videos_u8(n, num_classes=a.classes, hw=a.hw)]
         names = ["synthetic_%d" % i for i in range(n)]
-    engine = detect.DetectEngine(bs=a.bs, hw=a.hw, num_classes=a.classes, state=state, pack=a.pack, masks=a.masks or a.instances > 0, tile=a.tile,
+    engine = detect.DetectEngine(bs=a.bs, hw=a.hw, num_classes=a.classes, state=state, pack=a.pack, masks=a.masks or a.mask_runs or a.instances > 0, tile=a.tile,
                                  flip=a.flip, instances=a.instances, min_area=a.min_area, conn=a.conn, instance_maps=a.instance_maps,
                                  instance_scores=a.instance_scores, instance_links=a.instance_links)
     engine.begin()
     for v in videos:
         engine.add_video(v)
     out = {"names": np.array(names), "tile": np.bool_(a.tile), "flip": np.bool_(a.flip)}
-    for i, (name, d) in enumerate(zip(names, engine.results())):
+    dets = engine.results()
+    if a.mask_runs:
+        for key, which in (("mask", "masks"),) + ((("imap", "imap"),) if a.instances and a.instance_maps else ()):
+            for i, r in enumerate(engine.mask_runs(which)):
+                out.update({"%s_runs_%d" % (key, i): r.runs, "%s_run_offsets_%d" % (key, i): r.offsets, "%s_shape_%d" % (key, i): np.array(r.shape, np.int64)})
+    for i, (name, d) in enumerate(zip(names, dets)):
         tubes = d.tubes(a.min_pixels, a.max_gap)
         out.update({"label_%d" % i: np.int32(d.label), "class_scores_%d" % i: d.class_scores, "counts_%d" % i: d.counts, "boxes_%d" % i: d.boxes,
                     "frame_scores_%d" % i: d.frame_scores, "views_%d" % i: np.array(d.views, np.int32).reshape(-1, 3),
@@ -106,7 +117,7 @@ def main():
                 out.update({"inst_scores_%d" % i: d.inst_scores, "other_score_%d" % i: d.other_score})
             if d.inst_overlaps is not None:
                 out["inst_overlaps_%d" % i] = d.inst_overlaps
-            if d.imap is not None:
+            if d.imap is not None and not a.mask_runs:
                 m = d.imap.cpu().numpy()
                 out.update({"imap_%d" % i: m, "imap_shape_%d" % i: np.array(m.shape, np.int64)})
         print("%s: %d frames, class %d (%.4f), %d frames detected, %d tube(s)%s%s" % (
