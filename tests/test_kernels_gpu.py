@@ -571,6 +571,28 @@ def test_em_routing_fwd_bwd(C_, npos, pscale):
     assert not bad, "rel err (gpu vs fp64, cpu-fp32 vs fp64): %s" % report
 
 
+def test_em_routing_bwd_adds_onto_nonzero_parameter_gradients():
+    """pc_em_routing_bwd ADDS dW / dbeta_u / dbeta_a to what it finds (the drop-in's plan leaves out the zero fill in front of it): the block
+    partials are reduced in a fixed order and meet the old value in ONE float32 add, so onto random old values the result is old + (the result onto
+    zeros) bit for bit."""
+    g = torch.Generator().manual_seed(11)
+    B, C_, npos = 32, 21, 20
+    x = torch.cat([torch.randn(npos, B * 16, generator=g), torch.rand(npos, B, generator=g)], 1).to(DEV)
+    W = (torch.randn(B, C_, 4, 4, generator=g) * 0.5).to(DEV)
+    bu = torch.randn(C_, 16, generator=g).to(DEV); ba = torch.randn(C_, generator=g).to(DEV)
+    dout = torch.randn(npos, C_ * 17, generator=g).to(DEV)
+    state = ops.em_state(npos, DEV)
+    ops.em_fwd(x, W, bu, ba, npos, B, C_, state=state)
+    fresh = [torch.zeros(B, C_, 4, 4, device=DEV), torch.zeros(C_, 16, device=DEV), torch.zeros(C_, device=DEV)]
+    dx0 = ops.em_bwd(x, W, bu, ba, dout, npos, B, C_, *fresh, state=state)
+    old = [torch.randn(t.shape, generator=g).to(DEV) for t in fresh]
+    got = [t.clone() for t in old]
+    dx1 = ops.em_bwd(x, W, bu, ba, dout, npos, B, C_, *got, state=state)
+    assert torch.equal(dx0, dx1)
+    for name, gt, o, f in zip(("dW", "dbeta_u", "dbeta_a"), got, old, fresh):
+        assert f.abs().max().item() > 0 and torch.equal(gt, o + f), name
+
+
 @pytest.mark.parametrize("seeds", ["act", "both"])
 def test_em_routing_bwd_at_reference_init_scale(seeds):
     """The reference's own initialisation (PrimaryCaps weights N(0, 0.1), ConvCaps.weights randn) gives poses of std ~13 and
@@ -818,6 +840,46 @@ def test_collapsed_tail_kernels_vs_torch():
     F.conv_transpose3d(F.conv_transpose3d(xr, W4.detach(), b4.detach(), stride=2, padding=1, output_padding=1) * cs.view(N, Co, 1, 1, 1),
                        Wp.detach(), bp.detach(), padding=1).backward(dout)
     close(uncl(dx), xr.grad, what="collapsed dgrad")
+
+
+@pytest.mark.parametrize("form", ["atomic", "ws"])
+def test_tail_grads_accumulate_onto_nonzero_outputs(form):
+    """pc_tail_grads (fp32 atomics) and pc_tail_grads_ws (ordered block partials) with accum = 1, as the drop-in's plan calls them: all four
+    outputs start from random values and must end at old + gradient (float64 autograd of upsample4 -> Dropout3d -> smooth), the shape of
+    test_collapsed_tail_kernels_vs_torch."""
+    g = torch.Generator().manual_seed(14)
+    N, Ci, Co, taps, J = 2, 8, 12, 27, 27
+    W4 = (torch.randn(Ci, Co, 3, 3, 3, generator=g) * 0.2); b4 = torch.randn(Co, generator=g)
+    Wp = (torch.randn(Co, 1, 3, 3, 3, generator=g) * 0.2); bp = torch.randn(1, generator=g)
+    cs = (torch.rand(N, Co, generator=g) < 0.5).float() * 2
+    x = torch.randn(N, Ci, 2, 3, 4, generator=g)
+    r = [t.double().requires_grad_(True) for t in (W4, b4, Wp, bp)]
+    out = F.conv_transpose3d(F.conv_transpose3d(x.double(), r[0], r[1], stride=2, padding=1, output_padding=1) * cs.double().view(N, Co, 1, 1, 1),
+                             r[2], r[3], padding=1)
+    dout = torch.randn(out.shape, generator=g)
+    out.backward(dout.double())
+    dev = lambda t: t.detach().contiguous().to(DEV)
+    W4g, b4g, csg, Wpg = dev(W4), dev(b4), dev(cs), dev(Wp)
+    othw = tuple(out.shape[2:])
+    dproj = ops.tapsum_bwd(dev(dout[:, 0]))
+    sums = torch.empty(N, 32, device=DEV)
+    capi.call("pc_tail_colsum", ops.ptr(dproj), N, int(np.prod(othw)), ops.ptr(sums), ops.stream())
+    G = torch.zeros(N, Ci, taps, 32, device=DEV)
+    xg = cl(x)
+    for n in range(N):
+        ops.conv_wgrad(desc.wgrad(1, (2, 3, 4), Ci, Ci, othw, 32, 32, (3, 3, 3), (2, 2, 2), (1, 1, 1)), xg[n], dproj[n], G[n])
+    old = [torch.randn(s, generator=g) for s in ((Ci, Co, taps), (Co,), (Co, J), (1,))]
+    dW4, db4, dWp, dbp = [dev(t) for t in old]
+    args = [ops.ptr(G), ops.ptr(sums), ops.ptr(W4g), ops.ptr(b4g), ops.ptr(csg), ops.ptr(Wpg), N, Ci, Co, taps, J, 13,
+            ops.ptr(dW4), ops.ptr(db4), ops.ptr(dWp), ops.ptr(dbp), 1]
+    if form == "ws":
+        part = torch.full((int(capi.lib().pc_tail_grads_ws_floats(N, Ci, Co)),), float("nan"), device=DEV)
+        capi.call("pc_tail_grads_ws", *args, ops.ptr(part), ops.stream())
+    else:
+        capi.call("pc_tail_grads", *args, ops.stream())
+    for name, got, o, ref in (("dW4", dW4, old[0], r[0].grad.reshape(Ci, Co, taps)), ("db4", db4, old[1], r[1].grad),
+                              ("dWp", dWp, old[2], r[2].grad.reshape(Co, J)), ("dbp", dbp, old[3], r[3].grad)):
+        close(got, o.double() + ref, what="%s (%s, accum)" % (name, form))
 
 
 def test_merged_tail_vs_torch():
