@@ -67,8 +67,8 @@ typedef void* pc_stream;            /* hipStream_t */
  * 106: pc_truth_frame_flags / pc_eval_clips_from_u8 / pc_video_vote;
  * 107: pc_clips_from_u8 / pc_detect_frames / pc_detect_frames_ws_bytes / pc_video_class; the entries pc_clips_from_u8_views / pc_detect_frames_views /
  * pc_detect_frames_views_ws_bytes came later and move nothing: no struct grew, no op's operands changed; so did pc_frame_instances with its
- * PC_INST_* constants, pc_frame_probs / pc_instance_scores with PC_PROB_ONE / PC_SCORE_WORDS, pc_instance_overlaps with PC_LINK_MAX_LAGS, and pc_mask_run_ws_bytes /
- * pc_mask_run_index / pc_mask_runs with PC_RUN_WORDS: came later, move nothing).  Descriptors must be zero-initialised by the caller:
+ * PC_INST_* constants, pc_frame_probs / pc_instance_scores with PC_PROB_ONE / PC_SCORE_WORDS, pc_instance_overlaps with PC_LINK_MAX_LAGS, pc_mask_run_ws_bytes /
+ * pc_mask_run_index / pc_mask_runs with PC_RUN_WORDS, and pc_map_crosstab / pc_map_crosstab_ws_bytes with PC_CROSS_MAX_SLOTS: came later, move nothing).  Descriptors must be zero-initialised by the caller:
  * fields added later read as "old behaviour" when 0.  pc_version() returns the value the library was built with; the Python host
  * (capi.lib()) refuses a library whose version differs from the header it mirrors. */
 #define PC_VERSION 107
@@ -531,6 +531,24 @@ int     pc_instance_overlaps(const uint8_t* imap, int F, int H, int W, int f0, i
 int64_t pc_mask_run_ws_bytes(int nf, int H);
 int     pc_mask_run_index(const uint8_t* map, int F, int H, int W, int f0, int nf, int32_t* index, void* ws, pc_stream s);
 int     pc_mask_runs(const uint8_t* map, int F, int H, int W, int f0, int nf, const int32_t* index, int64_t cap, uint32_t* runs, pc_stream s);
+/* A map of a pass against a truth map (csrc/crosstab.hip; picons_amd/detect.py: DetectEngine.score).  pred and truth are two DIFFERENT
+ * contiguous uint8 buffers [F][H][W] (a frame may start at any byte address on either side; frame offsets are 64-bit).  The SLOT of a pred
+ * byte v is 0 for v = 0 (background), v for 1 <= v <= P, and P + 1 for anything above P ("other foreground": the 255 of a map of ranks, or
+ * any value beyond); the slot of a truth byte is the same with A.  ANY non-zero truth byte is foreground -- deliberately unlike
+ * pc_seg_frame_counts, whose intersection needs the truth value 1 (pred + gt == 2).
+ * pc_map_crosstab writes, for each of the frames f0 .. f0 + nf - 1 and no others, EVERY cell of `out` int32 [F][P + 2][A + 2]:
+ * out[f][p][a] = the pixels of frame f with pred slot p and truth slot a, cell [0][0] included, so the cells of a frame sum to H * W.
+ * Nothing has to be zeroed in front of the call; the prior contents of out and ws are irrelevant.  ws: pc_map_crosstab_ws_bytes(nf, H, W,
+ * P, A) bytes, 8-byte aligned, meaningless after the call.  Two launches: bpf blocks per frame (a function of H * W alone, at most 64)
+ * leave one partial table each in ws, then one block per frame adds them in block order and writes [0][0] as H * W minus the rest.
+ * Integer LDS atomics only (per-wave bins, folded at the end), no global atomics, no floating point, nothing waits on another block:
+ * bit-identical from run to run.  pc_map_crosstab_ws_bytes is host arithmetic: -1 for nf, H or W < 1, H * W >= 2^31, P or A outside
+ * 1..PC_CROSS_MAX_SLOTS.  Refusals of the call (PC_E_ARG before any HIP call): null pred, truth, out or ws; F, H, W < 1; H * W >= 2^31;
+ * f0 < 0, nf < 1, f0 + nf > F; P or A outside 1..PC_CROSS_MAX_SLOTS; out not 4-byte aligned; ws not 8-byte aligned. */
+#define PC_CROSS_MAX_SLOTS 32
+int     pc_map_crosstab(const uint8_t* pred, const uint8_t* truth, int F, int H, int W, int f0, int nf, int P, int A, int32_t* out, void* ws,
+                        pc_stream s);
+int64_t pc_map_crosstab_ws_bytes(int nf, int H, int W, int P, int A);
 /* cv2.resize on uint8 images [n][H][W][C] -> [n][Ho][Wo][C] (C <= 4), the calls of the reference's loaders:
  * datasets/jhmdb_dataloader.py:252 (frames, INTER_AREA 320x240 -> 256x256), :267,:281 (puppet masks, INTER_NEAREST),
  * :192,:208 and ucf_dataloader.py:165,171 (224 crop -> frame size, INTER_LINEAR; the identity at 224).  OpenCV's 8-bit

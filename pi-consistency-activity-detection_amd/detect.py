@@ -34,13 +34,20 @@ shares with every instance of the later frame; link_instance_tubes_by_mask links
 Mask runs.  The masks (and the maps of ranks) stay on the device; DetectEngine.mask_runs, called after results(), brings those of a whole
 pass to the host as row runs -- pc_mask_run_index / pc_mask_runs per video, two host waits per call -- in MaskRuns objects: a frame of a
 few blobs is 1-2 KB instead of its H * W bytes.
+
+Score.  DetectEngine.score(truths, labels), called after results(), measures a pass against truth masks: one pc_map_crosstab launch per video
+cross-tabulates its mask (or map of ranks) with the truth on the device, all tables leave in one copy -- one host wait per call -- and the
+host turns them into the evaluator's own f-mAP / v-mAP tables (crosstab_counts, accumulate_video) and a per-instance IoU against truth
+actors (instance_actor_iou), in VideoScore / PassScore objects.  Unlike evalstep.EvalEngine, whose protocol is the centre crop, the truth is
+taken on the FULL frame, so a tiled or mirrored pass can be scored; and the class vote is the detection's, over all clips of the video,
+where EvalEngine votes over the clips that hold truth.
 """
 from types import SimpleNamespace
 
 import numpy as np
 import torch
 
-from . import ops
+from . import evalmetrics, ops
 from .evalstep import ClipEngine, _as_u8, centre_crop, clip_starts, ring_place
 
 PIN_CHUNK_WORDS = 1 << 18          # page-locked staging of the records, 1 MiB at a time
@@ -356,6 +363,96 @@ def run_ranges(F, H, W):
     return [(f0, min(per, F - f0)) for f0 in range(0, F, per)]
 
 
+# ---------------------------------------------------------------------- a pass against truth (tests/test_detect_score_cpu.py)
+def crosstab_counts(table):
+    """Tables int32 [F, P + 2, A + 2] of pc_map_crosstab -> int64 [F, 3] = (inter, union, gt) per frame: the pixels that are foreground on both
+    sides, on either side, and in the truth -- the triple pc_seg_frame_counts leaves when the truth is in {0, 1}."""
+    t = np.asarray(table).astype(np.int64)
+    if t.ndim != 3 or t.shape[1] < 2 or t.shape[2] < 2:
+        raise ValueError("crosstab_counts: tables [F, P + 2, A + 2], got %s" % (t.shape,))
+    out = np.empty((t.shape[0], 3), np.int64)
+    out[:, 0] = t[:, 1:, 1:].sum(axis=(1, 2))
+    out[:, 1] = t.sum(axis=(1, 2)) - t[:, 0, 0]
+    out[:, 2] = t[:, :, 1:].sum(axis=(1, 2))
+    return out
+
+
+def accumulate_video(counts, label, acc):
+    """map_accumulate_kernel (csrc/evalmetrics.hip) on the host: one video's counts [F, 3] = (inter, union, gt) into the tables of an
+    evalmetrics.MapAccumulator built with device="cpu".  Only frames with gt != 0 count, for the frame tables and for the video's sums; per
+    threshold k the float64 ratio inter / union is compared (>=) with the float32 k / 20 widened to float64; video_hits is touched only when
+    the summed union is positive; n_vids[label] += 1.  A video without any truth pixel is the caller's to skip (EvalEngine.add_video
+    returning 0): it is not passed here."""
+    c = np.asarray(counts).astype(np.int64).reshape(-1, 3)
+    label = int(label)
+    if not 0 <= label < acc.n_classes:
+        raise ValueError("accumulate_video: label %d outside [0, %d)" % (label, acc.n_classes))
+    fh, vh, nfr, nv = (t.numpy() for t in (acc.frame_hits, acc.video_hits, acc.n_frames, acc.n_vids))      # views: the adds land in the tensors
+    on = c[:, 2] != 0
+    inter, union = c[on, 0], c[on, 1]
+    thr = (np.arange(evalmetrics.N_THR, dtype=np.float32) / np.float32(20.0)).astype(np.float64)
+    ratio = inter.astype(np.float64) / union.astype(np.float64)        # union >= gt > 0 on these frames
+    fh[label] += (ratio[:, None] >= thr[None, :]).sum(axis=0).astype(np.int32)
+    vi, vu = int(inter.sum()), int(union.sum())
+    if vu > 0:
+        vh[label] += (np.float64(vi) / np.float64(vu) >= thr).astype(np.int32)
+    nfr[label] += int(on.sum())
+    nv[label] += 1
+
+
+def instance_actor_iou(table):
+    """Tables int32 [F, P + 2, A + 2] -> float64 [F, P, A]: the IoU of the pixels of pred slot r + 1 (the instance of rank r) with those of
+    truth slot a + 1 (actor a + 1): inter / (row sum + column sum - inter), 0.0 where that denominator is 0."""
+    t = np.asarray(table).astype(np.int64)
+    if t.ndim != 3 or t.shape[1] < 3 or t.shape[2] < 3:
+        raise ValueError("instance_actor_iou: tables [F, P + 2, A + 2], got %s" % (t.shape,))
+    inter = t[:, 1:-1, 1:-1]
+    den = t.sum(axis=2)[:, 1:-1, None] + t.sum(axis=1)[:, None, 1:-1] - inter
+    return np.where(den != 0, inter.astype(np.float64) / np.maximum(den, 1).astype(np.float64), 0.0)
+
+
+class VideoScore:
+    """One video of a pass against its truth.  table int32 [F, P + 2, A + 2] (pc_map_crosstab); counts int64 [F, 3] = (inter, union, gt);
+    frame_iou float64 [F], NaN where the frame holds no truth; video_iou: summed inter / summed union over the frames with truth, NaN for a
+    skipped video; label the true class, predicted the detection's, correct whether they agree; skipped: the video holds no truth pixel and
+    entered no table (as EvalEngine skips it)."""
+
+    def __init__(self, table, label, predicted):
+        self.table = table
+        self.counts = crosstab_counts(table)
+        self.label, self.predicted = int(label), int(predicted)
+        on = self.counts[:, 2] != 0
+        self.skipped = not bool(on.any())
+        self.correct = not self.skipped and self.label == self.predicted
+        self.frame_iou = np.full(self.counts.shape[0], np.nan, np.float64)
+        self.frame_iou[on] = self.counts[on, 0].astype(np.float64) / self.counts[on, 1].astype(np.float64)
+        self.video_iou = float("nan") if self.skipped else float(np.float64(self.counts[on, 0].sum()) / np.float64(self.counts[on, 1].sum()))
+
+    def instance_iou(self):
+        """-> float64 [F, P, A]: instance_actor_iou of the table."""
+        return instance_actor_iou(self.table)
+
+
+class PassScore:
+    """A pass against truth.  result: the dict of evalmetrics.MapAccumulator.result() (the keys of EvalEngine.results()); videos: the
+    VideoScore of every scored video in order; n_skipped: how many of them held no truth."""
+
+    def __init__(self, result, videos):
+        self.result, self.videos = result, list(videos)
+        self.n_skipped = sum(1 for v in self.videos if v.skipped)
+
+
+def score_pass(tables, labels, predicted, n_classes):
+    """The host side of DetectEngine.score: per-video tables, true and predicted classes -> PassScore."""
+    acc = evalmetrics.MapAccumulator(n_classes, device="cpu")
+    videos = [VideoScore(t, l, p) for t, l, p in zip(tables, labels, predicted)]
+    for v in videos:
+        if not v.skipped:
+            accumulate_video(v.counts, v.label, acc)
+            acc.n_correct += int(v.correct)
+    return PassScore(acc.result(), videos)
+
+
 def check_instances(instances, min_area, conn, masks):
     """The instance arguments of DetectEngine -> (K, min_area, conn) as ints, or ValueError."""
     K, min_area, conn = int(instances), int(min_area), int(conn)
@@ -450,6 +547,9 @@ class DetectEngine(ClipEngine):
         # it waits for every video's flags).  A slot is filled again once the upload of two videos ago has left it.
         self.up_pin, self.up_done, self.up_slot = [None, None], [None, None], 0
         self.run_pins = [None, None]         # page-locked staging of mask_runs: per-frame offsets, runs
+        # score: two page-locked slots the truths go up through (as up_pin), the tables' staging and the kernel's workspace; all made by the first call
+        self.tr_pin, self.tr_done, self.tr_slot = [None, None], [None, None], 0
+        self.score_pin = self.score_ws = None
         self._clear()
 
     def _clear(self):
@@ -671,6 +771,102 @@ class DetectEngine(ClipEngine):
         if self.run_pins[slot] is None or self.run_pins[slot].numel() < words:
             self.run_pins[slot] = torch.empty(max(words, 1024), dtype=torch.int32).pin_memory()
         return self.run_pins[slot][:words]
+
+    def score(self, truths, labels, actors=1, which="masks", videos=None):
+        """The last pass against truth masks -> PassScore.  truths[i]: uint8 [F,H,W] or [F,H,W,1] (numpy, host tensor or device tensor) for
+        the i-th video of the pass, or of `videos`; any non-zero byte is truth, a byte 1..actors is that actor.  labels[i]: its class id.
+        which="masks": the video's mask, P = 1; which="imap" (needs instance_maps=True): its map of ranks, P = K.  Called after results(); it
+        changes nothing results() returned and can be called again.  Per video one upload through page-locked staging on the copy stream
+        (the host waits at most for its own upload of two videos ago, never for the compute stream) and one pc_map_crosstab launch; all
+        tables leave in one asynchronous copy and the call has ONE wait on the compute stream, after which the host does the rest
+        (score_pass).  Unlike EvalEngine the truth is taken on the full frame, not inside the centre crop, and `correct` compares with the
+        detection's class, voted over all clips of the video, where EvalEngine votes over the clips that hold truth.  Every refusal is a
+        ValueError before anything is enqueued."""
+        if which not in ("masks", "imap"):
+            raise ValueError("score: which = %r, \"masks\" or \"imap\"" % (which,))
+        if which == "masks" and not self.masks:
+            raise ValueError("score: the engine keeps no masks (masks=False)")
+        if which == "imap" and not self.instance_maps:
+            raise ValueError("score: the engine keeps no maps of ranks (instances=K with instance_maps=True)")
+        if not self.videos or any(rec.pin is None for rec in self.videos):
+            raise ValueError("score: no finished pass (call it after results())")
+        try:
+            A = int(actors)
+        except (TypeError, ValueError):
+            raise ValueError("score: actors = %r is not a number" % (actors,)) from None
+        if A != actors or not 1 <= A <= ops.CROSS_MAX_SLOTS:
+            raise ValueError("score: actors = %r outside 1..%d" % (actors, ops.CROSS_MAX_SLOTS))
+        picks = list(range(len(self.videos))) if videos is None else [int(v) for v in videos]
+        for v in picks:
+            if not 0 <= v < len(self.videos):
+                raise ValueError("score: video %d outside the %d of the pass" % (v, len(self.videos)))
+        truths, labels = list(truths), list(labels)
+        if not (len(truths) == len(labels) == len(picks)):
+            raise ValueError("score: %d truths and %d labels for %d videos" % (len(truths), len(labels), len(picks)))
+        P = 1 if which == "masks" else self.inst_k
+        jobs, labs, words, ws_need = [], [], 0, 0                       # (record, truth, first word of its tables)
+        for v, truth, label in zip(picks, truths, labels):
+            rec = self.videos[v]
+            t = _as_u8(truth, "score: truth of video %d" % v)
+            if t.dim() == 4 and t.shape[3] == 1:
+                t = t.reshape(t.shape[:3])
+            if tuple(t.shape) != (rec.F, rec.H, rec.W):
+                raise ValueError("score: truth of video %d has shape %s, expected (%d, %d, %d) or (%d, %d, %d, 1)"
+                                 % (v, tuple(truth.shape), rec.F, rec.H, rec.W, rec.F, rec.H, rec.W))
+            try:
+                lab = int(label)
+            except (TypeError, ValueError):
+                raise ValueError("score: label %r is not a class id" % (label,)) from None
+            if lab != label or not 0 <= lab < self.C:
+                raise ValueError("score: label %r outside [0, %d)" % (label, self.C))
+            jobs.append((rec, t, words))
+            labs.append(lab)
+            words += rec.F * (P + 2) * (A + 2)
+            ws_need = max(ws_need, ops.map_crosstab_ws_bytes(rec.F, rec.H, rec.W, P, A))
+        if not jobs:
+            return score_pass([], [], [], self.C)
+        main = torch.cuda.current_stream(self.dev)
+        if self.score_ws is None or self.score_ws.numel() < ws_need:
+            self.score_ws = torch.empty(ws_need, dtype=torch.uint8, device=self.dev)
+        tab_dev = torch.empty(words, dtype=torch.int32, device=self.dev)
+        for rec, t, w0 in jobs:
+            n = rec.F * (P + 2) * (A + 2)
+            ops.map_crosstab(rec.mask if which == "masks" else rec.imap, self._truth_to_device(t, main), P, A,
+                             out=tab_dev[w0:w0 + n].view(rec.F, P + 2, A + 2), ws=self.score_ws)
+        if self.score_pin is None or self.score_pin.numel() < words:
+            self.score_pin = torch.empty(max(words, 1024), dtype=torch.int32).pin_memory()
+        self.score_pin[:words].copy_(tab_dev, non_blocking=True)
+        main.synchronize()                                           # the call's one wait on the compute stream
+        host = self.score_pin[:words].numpy()
+        tables = [ops.decode_map_crosstab(host[w0:w0 + rec.F * (P + 2) * (A + 2)], P, A) for rec, _t, w0 in jobs]      # copies: the staging is used again
+        predicted = []
+        for rec, _t, _w0 in jobs:
+            cls0 = rec.F * ops.DETECT_REC_WORDS
+            predicted.append(int(rec.pin.numpy()[cls0:cls0 + self.C + 2].copy().view(np.float32)[self.C]))
+        return score_pass(tables, labs, predicted, self.C)
+
+    def _truth_to_device(self, t, main):
+        """A truth [F,H,W] on the device, contiguous, ordered in front of what `main` runs next.  A host truth goes through one of two
+        page-locked slots on the copy stream; the host waits only for the upload that used the slot two truths ago."""
+        if t.is_cuda:
+            return t.to(self.dev).contiguous()
+        slot = self.tr_slot
+        self.tr_slot ^= 1
+        if self.tr_done[slot] is not None:
+            self.tr_done[slot].synchronize()                          # an upload on the copy stream: never the compute stream
+        n = t.numel()
+        if self.tr_pin[slot] is None or self.tr_pin[slot].numel() < n:
+            self.tr_pin[slot] = torch.empty(n, dtype=torch.uint8).pin_memory()
+        stage = self.tr_pin[slot][:n].view(t.shape)
+        stage.copy_(t)
+        with torch.cuda.stream(self.copy_stream):                    # allocated where it is written; the compute stream's use is recorded below
+            d = torch.empty(t.shape, dtype=torch.uint8, device=self.dev)
+            d.copy_(stage, non_blocking=True)
+            self.tr_done[slot] = torch.cuda.Event()
+            self.tr_done[slot].record(self.copy_stream)
+        main.wait_event(self.tr_done[slot])
+        d.record_stream(main)
+        return d
 
     def detect(self, frames_u8):
         """One video on its own: begin(), add_video, results()[0]."""

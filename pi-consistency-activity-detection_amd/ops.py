@@ -933,6 +933,55 @@ def decode_mask_runs(runs, nf, H, W):
     return np.cumsum(d[:, :W], axis=1, dtype=np.int16).astype(np.uint8).reshape(nf, H, W)
 
 
+CROSS_MAX_SLOTS = 32                       # PC_CROSS_MAX_SLOTS of include/picons.h: the pred values P and the truth values A with a slot of their own
+
+
+def map_crosstab_ws_bytes(nf, H, W, P, A):
+    """pc_map_crosstab_ws_bytes (host arithmetic): the bytes of workspace one map_crosstab call over nf frames of H x W takes."""
+    n = int(capi.lib().pc_map_crosstab_ws_bytes(int(nf), int(H), int(W), int(P), int(A)))
+    if n < 0:
+        raise ValueError("map_crosstab_ws_bytes: nf = %d frames of %d x %d with P = %d, A = %d: nf, H, W >= 1, H * W < 2^31, P and A in 1..%d"
+                         % (nf, H, W, P, A, CROSS_MAX_SLOTS))
+    return n
+
+
+def map_crosstab(pred, truth, P, A, f0=0, nf=None, out=None, ws=None):
+    """pc_map_crosstab: pred and truth contiguous uint8 device [F,H,W], two different buffers -> out int32 [F, P + 2, A + 2]: out[f, p, a] the
+    pixels of frame f with pred slot p (0 background, v for a byte 1..P, P + 1 for any byte above P) and truth slot a (the same with A),
+    cell [0, 0] included, for the frames f0 .. f0 + nf - 1 (default: all from f0 on).  A given out is written in place -- only those frames
+    -- a fresh one is zero-filled first.  ws: uint8 device scratch of at least map_crosstab_ws_bytes(nf, H, W, P, A) bytes, made when None."""
+    for name, t in (("pred", pred), ("truth", truth)):
+        if not torch.is_tensor(t) or t.dtype != torch.uint8 or t.dim() != 3 or not t.is_contiguous():
+            raise ValueError("map_crosstab: contiguous uint8 [F,H,W] %s" % name)
+    if pred.shape != truth.shape or pred.device != truth.device:
+        raise ValueError("map_crosstab: pred %s and truth %s must have one shape and lie on one device" % (tuple(pred.shape), tuple(truth.shape)))
+    F, H, W = (int(v) for v in pred.shape)
+    P, A, f0 = int(P), int(A), int(f0)
+    if not 1 <= P <= CROSS_MAX_SLOTS or not 1 <= A <= CROSS_MAX_SLOTS:
+        raise ValueError("map_crosstab: P = %d, A = %d outside 1..%d" % (P, A, CROSS_MAX_SLOTS))
+    nf = F - f0 if nf is None else int(nf)
+    if f0 < 0 or nf < 1 or f0 + nf > F:
+        raise ValueError("map_crosstab: frames f0 = %d, nf = %d outside the %d of the map" % (f0, nf, F))
+    if out is None:
+        out = torch.zeros(F, P + 2, A + 2, dtype=torch.int32, device=pred.device)
+    elif out.dtype != torch.int32 or not out.is_contiguous() or out.numel() != F * (P + 2) * (A + 2) or out.device != pred.device:
+        raise ValueError("map_crosstab: out must be a contiguous int32 device tensor [F, %d, %d]" % (P + 2, A + 2))
+    need = map_crosstab_ws_bytes(nf, H, W, P, A)
+    if ws is None:
+        ws = torch.empty(need, dtype=torch.uint8, device=pred.device)
+    elif ws.dtype != torch.uint8 or not ws.is_contiguous() or ws.numel() < need or ws.device != pred.device:
+        raise ValueError("map_crosstab: ws must be a contiguous uint8 device tensor of at least %d bytes" % need)
+    capi.call("pc_map_crosstab", ptr(pred), ptr(truth), F, H, W, f0, nf, P, A, ptr(out), ptr(ws), stream())
+    return out
+
+
+def decode_map_crosstab(words, P, A):
+    """Host int32 tables of F * (P + 2) * (A + 2) words (numpy or torch, any shape) -> int32 [F, P + 2, A + 2]."""
+    P, A = int(P), int(A)
+    r = np.ascontiguousarray(words.cpu().numpy() if torch.is_tensor(words) else words, dtype=np.int32)
+    return r.reshape(-1, P + 2, A + 2).copy()
+
+
 def video_class(scores, out=None):
     """pc_video_class: scores contiguous float32 device [n,C] -> float32 device [C + 2]: mean class scores, arg-max (as a float), its mean."""
     if scores.dtype != torch.float32 or scores.dim() != 2 or not scores.is_contiguous():

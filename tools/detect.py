@@ -22,10 +22,16 @@ pass, a frame of a few blobs is 1-2 KB): mask_runs_i uint32 [n,2] = (row | value
 mask_run_offsets_i int64 [F + 1] (frame f holds the runs offsets[f] .. offsets[f + 1] - 1) and mask_shape_i; detect.MaskRuns(shape, offsets,
 runs).dense() gives the uint8 masks back.  With --instance_maps also imap_runs_i / imap_run_offsets_i (value: rank + 1, or 255), and imap_i
 is then not written raw.  Runs are for blob masks: a noisy mask of density 0.5 holds about W / 4 runs of 8 bytes a row, more than its bytes.
+--truth t0.npy ... (one uint8 [F,H,W] or [F,H,W,1] file per video, any non-zero byte is truth) with --labels l0 ... (implies masks on the
+device): the pass scored against them on the device (DetectEngine.score: one pc_map_crosstab launch per video, one host wait): f-mAP and
+v-mAP at 0.2 and 0.5 and the accuracy are printed, and score_table_i int32 [F, 3, 3] (pred slot x truth slot), score_counts_i [F, 3] =
+(inter, union, gt), score_label_i and the arrays of the result (score_fmAP [20], score_vmAP [20], score_frame_ious, score_video_ious,
+score_n_tot_frames, score_n_vids, score_n_correct, score_accuracy) are stored.  The truth is taken on the full frame, not inside the centre
+crop as evalstep.EvalEngine takes it.  With --synthetic the truth and label of synthetic.make_eval_videos_u8 are used (--score).
 
     python tools/detect.py --out detections.npz [--ckpt best_model.pth] [--synthetic 4 | video.npy ...] [--masks] [--pack] [--tile] [--flip]
                            [--max-gap 0] [--min-pixels 1] [--instances K] [--min_area 1] [--conn 8] [--instance_maps] [--instance_scores]
-                           [--instance_links L] [--link box|mask] [--mask_runs]
+                           [--instance_links L] [--link box|mask] [--mask_runs] [--truth t0.npy ... --labels l0 ... | --score]
 """
 import argparse
 import os
@@ -62,7 +68,14 @@ def main():
     ap.add_argument("--instance_links", type=int, default=0, help="with --instances: mask overlaps between frames up to L apart (pc_instance_overlaps)")
     ap.add_argument("--link", default="box", choices=("box", "mask"), help="link the instance tubes by box IoU or, with --instance_links, by mask IoU")
     ap.add_argument("--mask_runs", action="store_true", help="the masks (with --instance_maps: and the maps of ranks) as row runs made on the device")
+    ap.add_argument("--truth", nargs="+", default=None, help="one .npy of uint8 truth [F,H,W] or [F,H,W,1] per video: score the pass against them")
+    ap.add_argument("--labels", nargs="+", type=int, default=None, help="with --truth: one class id per video")
+    ap.add_argument("--score", action="store_true", help="with synthetic videos: score the pass against their own truth and labels")
     a = ap.parse_args()
+    if (a.truth is None) != (a.labels is None) or (a.truth is not None and not (len(a.truth) == len(a.labels) == len(a.videos))):
+        raise SystemExit("tools/detect.py: --truth and --labels go together, one of each per video file")
+    if a.score and a.videos:
+        raise SystemExit("tools/detect.py: --score is for the synthetic videos; give --truth and --labels for video files")
     if a.instance_scores and a.instances <= 0:
         raise SystemExit("tools/detect.py: --instance_scores needs --instances K with K > 0 (the scores are reduced per instance)")
     if a.instance_links and a.instances <= 0:
@@ -82,11 +95,14 @@ def main():
     names = list(a.videos)
     if names:
         videos = [np.load(n) for n in names]
+        truths, labels = ([np.load(t) for t in a.truth], list(a.labels)) if a.truth else (None, None)
     else:
         n = a.synthetic or 4
-        videos = [v[0] for v in synthetic.make_eval_videos_u8(n, num_classes=a.classes, hw=a.hw)]
+        made = synthetic.make_eval_videos_u8(n, num_classes=a.classes, hw=a.hw)
+        videos = [v[0] for v in made]
+        truths, labels = ([v[1] for v in made], [v[2] for v in made]) if a.score else (None, None)
         names = ["synthetic_%d" % i for i in range(n)]
-    engine = detect.DetectEngine(bs=a.bs, hw=a.hw, num_classes=a.classes, state=state, pack=a.pack, masks=a.masks or a.mask_runs or a.instances > 0, tile=a.tile,
+    engine = detect.DetectEngine(bs=a.bs, hw=a.hw, num_classes=a.classes, state=state, pack=a.pack, masks=a.masks or a.mask_runs or a.instances > 0 or truths is not None, tile=a.tile,
                                  flip=a.flip, instances=a.instances, min_area=a.min_area, conn=a.conn, instance_maps=a.instance_maps,
                                  instance_scores=a.instance_scores, instance_links=a.instance_links)
     engine.begin()
@@ -98,6 +114,17 @@ def main():
         for key, which in (("mask", "masks"),) + ((("imap", "imap"),) if a.instances and a.instance_maps else ()):
             for i, r in enumerate(engine.mask_runs(which)):
                 out.update({"%s_runs_%d" % (key, i): r.runs, "%s_run_offsets_%d" % (key, i): r.offsets, "%s_shape_%d" % (key, i): np.array(r.shape, np.int64)})
+    if truths is not None:
+        ps = engine.score(truths, labels)
+        r = ps.result
+        with np.errstate(invalid="ignore", divide="ignore"):          # printed: the mean over the classes that hold a video (the stored fmAP / vmAP are
+            fm = np.nanmean(r["frame_ious"] / r["n_tot_frames"], axis=0)  # the evaluator's, NaN as soon as one class holds none)
+            vm = np.nanmean(r["video_ious"] / r["n_vids"], axis=0)
+        print("score against truth (classes with a video): f-mAP@0.2 %.4f  f-mAP@0.5 %.4f  v-mAP@0.2 %.4f  v-mAP@0.5 %.4f  accuracy %.4f  (%d videos, %d without truth)"
+              % (fm[4], fm[10], vm[4], vm[10], r["accuracy"], len(ps.videos), ps.n_skipped))
+        out.update({"score_" + k: np.asarray(v) for k, v in r.items()})
+        for i, v in enumerate(ps.videos):
+            out.update({"score_table_%d" % i: v.table, "score_counts_%d" % i: v.counts, "score_label_%d" % i: np.int32(v.label)})
     for i, (name, d) in enumerate(zip(names, dets)):
         tubes = d.tubes(a.min_pixels, a.max_gap)
         out.update({"label_%d" % i: np.int32(d.label), "class_scores_%d" % i: d.class_scores, "counts_%d" % i: d.counts, "boxes_%d" % i: d.boxes,
