@@ -68,7 +68,8 @@ typedef void* pc_stream;            /* hipStream_t */
  * 107: pc_clips_from_u8 / pc_detect_frames / pc_detect_frames_ws_bytes / pc_video_class; the entries pc_clips_from_u8_views / pc_detect_frames_views /
  * pc_detect_frames_views_ws_bytes came later and move nothing: no struct grew, no op's operands changed; so did pc_frame_instances with its
  * PC_INST_* constants, pc_frame_probs / pc_instance_scores with PC_PROB_ONE / PC_SCORE_WORDS, pc_instance_overlaps with PC_LINK_MAX_LAGS, pc_mask_run_ws_bytes /
- * pc_mask_run_index / pc_mask_runs with PC_RUN_WORDS, and pc_map_crosstab / pc_map_crosstab_ws_bytes with PC_CROSS_MAX_SLOTS: came later, move nothing).  Descriptors must be zero-initialised by the caller:
+ * pc_mask_run_index / pc_mask_runs with PC_RUN_WORDS, pc_map_crosstab / pc_map_crosstab_ws_bytes with PC_CROSS_MAX_SLOTS, and pc_resample_tables / pc_detect_frames_scaled_ws_bytes /
+ * pc_detect_frames_scaled: came later, move nothing).  Descriptors must be zero-initialised by the caller:
  * fields added later read as "old behaviour" when 0.  pc_version() returns the value the library was built with; the Python host
  * (capi.lib()) refuses a library whose version differs from the header it mirrors. */
 #define PC_VERSION 107
@@ -549,6 +550,38 @@ int     pc_mask_runs(const uint8_t* map, int F, int H, int W, int f0, int nf, co
 int     pc_map_crosstab(const uint8_t* pred, const uint8_t* truth, int F, int H, int W, int f0, int nf, int P, int A, int32_t* out, void* ws,
                         pc_stream s);
 int64_t pc_map_crosstab_ws_bytes(int nf, int H, int W, int P, int A);
+/* Detection on a resized working frame, results at native size (csrc/detectscale.hip; picons_amd/detect.py: DetectEngine.set_working_frame).
+ * The views are crops of an Hs x Ws WORKING frame; mask, box, score and probability stand on the H x W NATIVE frame.
+ * pc_resample_tables is HOST arithmetic with pc_resize_tables' call shape: it returns the word count 2 * (H + W) and writes `tab` if `cap`
+ * words suffice; PC_E_ARG (-1) for a size < 1 or 2 * max(H, W) >= 2^24.  Layout: rows [H][2], then columns [W][2], each pair (i0, the bits
+ * of the float32 w1).  For destination index d of D from a source of length L (rows: L = Hs, D = H; columns: L = Ws, D = W), half-pixel
+ * centres (cv2.INTER_LINEAR / align_corners=False), exact in 64-bit integers: num = (2d + 1) * L - D, den = 2D, i0 = floor(num / den),
+ * r = num - i0 * den; if i0 < 0: i0 = 0, r = 0; if i0 >= L - 1: i0 = L - 1, r = 0; w1 = (float)r / (float)den -- both exact in float32, the
+ * division rounded once.  L == D gives i0 = d, w1 = 0: the identity.
+ * pc_detect_frames_scaled: logits, views (crops of the Hs x Ws frame), view_stride, starts, n <= 32, f_skip, row0 are pc_detect_frames_views'
+ * with (H, W) replaced by (Hs, Ws); dev_tab is the DEVICE copy of pc_resample_tables(Hs, Ws, H, W).
+ *   1. Per working pixel the merged logit M and its cover count are pc_detect_frames_views' (csrc/viewmerge.h), bit for bit.
+ *   2. Per native pixel (y, x) of the addressed frames, with (iy, wy1) = row pair y, (ix, wx1) = column pair x, wx0 = 1.0f - wx1,
+ *      wy0 = 1.0f - wy1:   top = wx1 == 0 ? M[iy][ix] : M[iy][ix] * wx0 + M[iy][ix + 1] * wx1;   bot: the same on row iy + 1, formed only if
+ *      wy1 != 0;   v = wy1 == 0 ? top : top * wy0 + bot * wy1.  Every product and sum is one fp32 round-to-nearest operation (no fma).  A tap
+ *      of zero weight is not read: -0.0 and NaN pass through an identity resample, a NaN or an uncovered pixel under a zero weight poisons
+ *      nothing.  The pixel is COVERED iff every tap that is read has cover count >= 1; an uncovered pixel is background, probability 0.
+ *   3. From v on everything is pc_detect_frames_views': seg_positive, the whole frame of mask uint8 [F][H][W] (may be null), the half-open
+ *      box in native coordinates, the score (fp32 sigmoid of v, summed in double: thread, wave, block partial in `ws`, a second launch adds the
+ *      partials in block order), the 8-word record with rec[6] = row0 + c * V, the frame rules (f >= F neither read nor written, a frame not
+ *      addressed untouched, nothing zeroed in front).  If `prob` is not null the same launch writes uint16 [F][H][W] with pc_frame_probs'
+ *      conversion of v (NaN and uncovered: 0).
+ * Three launches: the merge leaves M and the cover counts of the launch's n * 8 frames in `ws` (each logit fetched once), the resample walks
+ * the native frame in groups of four pixels, the records kernel adds the partials.  No atomics of any kind: bit-identical from run to run,
+ * with or without mask / prob.  ws: pc_detect_frames_scaled_ws_bytes(n, Hs, Ws, H, W) bytes, 8-byte aligned, contents irrelevant before and
+ * meaningless after = pc_detect_frames_views_ws_bytes(n, H, W) + 16 + n * 8 * roundup4(Hs * Ws) * 5 (host-only; -1 for n outside 1..32, a
+ * size < 1, Hs * Ws or H * W >= 2^31, 2 * max(H, W) >= 2^24).  Refusals (PC_E_ARG before any HIP call): pc_detect_frames_views' list on the
+ * working frame, a null dev_tab, H or W < 1, H * W >= 2^31, 2 * max(H, W) >= 2^24, prob not 2-byte aligned. */
+int64_t pc_resample_tables(int Hs, int Ws, int H, int W, int32_t* tab, int64_t cap);
+int64_t pc_detect_frames_scaled_ws_bytes(int n, int Hs, int Ws, int H, int W);
+int     pc_detect_frames_scaled(const float* logits, int F, int H, int W, int Hs, int Ws, int S, const int32_t* views, int V, int view_stride,
+                                const int32_t* starts, int n, int f_skip, int row0, const int32_t* dev_tab, uint8_t* mask, uint16_t* prob,
+                                int32_t* rec, void* ws, pc_stream s);
 /* cv2.resize on uint8 images [n][H][W][C] -> [n][Ho][Wo][C] (C <= 4), the calls of the reference's loaders:
  * datasets/jhmdb_dataloader.py:252 (frames, INTER_AREA 320x240 -> 256x256), :267,:281 (puppet masks, INTER_NEAREST),
  * :192,:208 and ucf_dataloader.py:165,171 (224 crop -> frame size, INTER_LINEAR; the identity at 224).  OpenCV's 8-bit

@@ -1,7 +1,8 @@
 // What the mask and the probability map of a multi-view detection share, so that they can never disagree about what was merged:
 //   merge_group4   the merged logits of four consecutive full-frame pixels (pc_detect_frames_views' rule: the views that cover a pixel in table
 //                  order, the first value as it is, the others added with __fadd_rn, one __fdiv_rn by the count when more than one covers)
-// Called by detect_frames_views_kernel (mask, box, score) and frame_probs_kernel (the uint16 probability) of detect.hip.
+// Called by detect_frames_views_kernel (mask, box, score) and frame_probs_kernel (the uint16 probability) of detect.hip, and by
+// merge_plane_kernel of detectscale.hip (the merged plane of a working frame, resampled to native size behind it).
 #pragma once
 #include "common.h"
 #include "clipgeom.h"

@@ -41,6 +41,11 @@ host turns them into the evaluator's own f-mAP / v-mAP tables (crosstab_counts, 
 actors (instance_actor_iou), in VideoScore / PassScore objects.  Unlike evalstep.EvalEngine, whose protocol is the centre crop, the truth is
 taken on the FULL frame, so a tiled or mirrored pass can be scored; and the class vote is the detection's, over all clips of the video,
 where EvalEngine votes over the clips that hold truth.
+
+Working frame.  The crops are cut at the video's own pixel scale unless DetectEngine.set_working_frame((Hs, Ws), interpolation) is called: then
+every video is resized on the device to Hs x Ws (pc_resize_u8: cv2.resize restated), the views are crops of that working frame, and
+pc_detect_frames_scaled merges them there and resamples the merged logits bilinearly to every native pixel in front of the threshold, the
+box, the score and the probability -- masks, records, instances, runs and score() stand in native coordinates at native size as before.
 """
 from types import SimpleNamespace
 
@@ -52,6 +57,7 @@ from .evalstep import ClipEngine, _as_u8, centre_crop, clip_starts, ring_place
 
 PIN_CHUNK_WORDS = 1 << 18          # page-locked staging of the records, 1 MiB at a time
 MAX_VIEWS = ops.MAX_VIEWS          # views of one video (one launch cuts, one merges, all of them)
+INTERPOLATIONS = {"nearest": 0, "linear": 1, "area": 3}      # set_working_frame: the cv2 flags ops.resize_u8 takes
 
 
 # ---------------------------------------------------------------------- pure host functions (tests/test_detect_cpu.py)
@@ -229,7 +235,8 @@ class Detection:
     """One video's detections.  label / class_score / class_scores [C]: the arg-max of the mean class scores of its clips, that mean, all means;
     counts [F] positive pixels, boxes [F, 4] = x0, y0, x1, y1 (half-open, full-frame coordinates, zeros for an empty frame) and frame_scores [F]
     (mean sigmoid over the positive pixels) per frame; masks: device uint8 [F, H, W] or None; views: the (h0, w0, flip) the video was seen
-    through.
+    through; work: None, or (Hs, Ws, interpolation) when the video was resized to a working frame (DetectEngine.set_working_frame) -- the
+    views are then in WORKING-frame coordinates, everything else in native ones.
 
     With DetectEngine(instances=K) also the frame's connected components of at least min_area pixels, ranked by area (ties: the first pixel in
     raster order): inst_n [F] how many there are, inst_kept [F] = min(inst_n, K) how many are held, inst_flags [F] (bit 0: the frame had more
@@ -246,6 +253,8 @@ class Detection:
     With DetectEngine(instance_links=L) also inst_overlaps int32 [F, L, K + 1, K + 1]: inst_overlaps[f, l, a, b] the pixels that slot a of
     frame f shares with slot b of frame f + l + 1 (slot r < K: the instance of rank r; slot K: all other foreground, and ALL foreground of a
     frame whose overflow flag is set; zeros where frame f + l + 1 does not exist).  None without the option."""
+
+    work = None                          # set by DetectEngine.results() behind the constructor, whose parameter list is pinned
 
     def __init__(self, label, class_score, class_scores, counts, boxes, frame_scores, masks, views=None, inst=None, imap=None, scores=None, probs=None,
                  inst_overlaps=None):
@@ -517,7 +526,10 @@ class DetectEngine(ClipEngine):
     instance_links=L in 1..4 (needs instances > 0): one pc_instance_overlaps launch behind pc_frame_instances counts, for every frame and
     each of the L frame distances, the pixels every instance shares with every instance of the later frame, into F * L * (K + 1)^2 words
     behind the score words: Detection.inst_overlaps, and with it instance_tubes(link="mask").  The map of ranks is then made whether or not
-    instance_maps asks for it.  0: nothing of this, no buffer and no launch."""
+    instance_maps asks for it.  0: nothing of this, no buffer and no launch.
+
+    set_working_frame((Hs, Ws), interpolation): videos added from then on are resized on the device to Hs x Ws, cut and run there, and
+    detected at native size through pc_detect_frames_scaled (below)."""
 
     def __init__(self, bs=14, hw=224, num_classes=24, device="cuda:0", state=None, engine=None, capacity=256, seed=47, f_skip=2, pack=False,
                  masks=True, on_batch=None, tile=False, flip=False, views=None, instances=0, min_area=1, conn=8, instance_maps=False,
@@ -542,6 +554,8 @@ class DetectEngine(ClipEngine):
         self.multi = self.tile or self.flip or views is not None
         self.ws = torch.empty(ops.detect_frames_ws_bytes(min(bs, 32), self.hw), dtype=torch.uint8, device=self.dev)
         self.ws_views = None                 # the merge's partials: sized for the first video's frame, grown only for a larger one
+        self.work = None                     # set_working_frame: (Hs, Ws, interpolation) for the videos to come, None for the video's own scale
+        self.ws_scaled = None                # pc_detect_frames_scaled's partials and merged plane, grown only for a larger video
         self.pins = []                       # page-locked chunks the records of a pass are copied into
         # upload staging: two page-locked slots, so that the host fills one while the copy stream still reads the other (EvalEngine has one:
         # it waits for every video's flags).  A slot is filled again once the upload of two videos ago has left it.
@@ -566,6 +580,36 @@ class DetectEngine(ClipEngine):
         self.pin_off += words
         return self.pins[self.pin_i][o:o + words]
 
+    def set_working_frame(self, size=None, interpolation="area"):
+        """size = (Hs, Ws), ints of at least hw: every video added from now on is resized on the device to Hs x Ws with cv2.resize's
+        arithmetic (interpolation "nearest", "linear" or "area": one pc_resize_u8 per video on the compute stream, skipped when the video has
+        that size already), its views are crops of that working frame -- so a video smaller than hw, or one whose tiles at its own scale
+        would be too many, can be taken -- and one pc_detect_frames_scaled launch per video segment merges the views on the working frame and
+        resamples the merged logits bilinearly to every native pixel in front of the threshold, the box, the score and the probability
+        map.  Masks, maps of ranks, probabilities, boxes and instances stay native [F, H, W]; Detection.views are in working coordinates
+        and Detection.work = (Hs, Ws, interpolation).  Each video keeps the working size it was added under.  size=None: the video's own
+        scale again, today's launches.  ValueError for anything else; nothing changes then."""
+        if size is None:
+            self.work = None
+            return
+        try:
+            Hs, Ws = size
+        except (TypeError, ValueError):
+            raise ValueError("set_working_frame: size = %r, (Hs, Ws) or None" % (size,)) from None
+        for v in (Hs, Ws):
+            if isinstance(v, bool) or not isinstance(v, (int, np.integer)):
+                raise ValueError("set_working_frame: size = %r, two ints" % (size,))
+        Hs, Ws = int(Hs), int(Ws)
+        if Hs < self.hw or Ws < self.hw or Hs * Ws >= 1 << 31:
+            raise ValueError("set_working_frame: a working frame of %d x %d is smaller than the %d x %d crop (or holds 2^31 pixels)" % (Hs, Ws, self.hw, self.hw))
+        if not isinstance(interpolation, str) or interpolation not in INTERPOLATIONS:
+            raise ValueError("set_working_frame: interpolation = %r, one of %s" % (interpolation, ", ".join(sorted(INTERPOLATIONS))))
+        self.work = (Hs, Ws, interpolation)
+
+    def _frame(self, H, W):
+        """The frame the views of an H x W video are cut from: the working frame if one is set, else its own."""
+        return (H, W) if self.work is None else self.work[:2]
+
     # ------------------------------------------------------------------ the pass
     def check_video(self, frames):
         """Refuse (ValueError) a video the engine cannot take, before anything is enqueued or changed.  -> (frames, clip starts, row0, next row)."""
@@ -573,14 +617,17 @@ class DetectEngine(ClipEngine):
         if v.dim() != 4 or v.shape[3] != 3 or v.shape[0] < 1:
             raise ValueError("frames: shape %s, expected (F, H, W, 3)" % (tuple(v.shape),))
         F, H, W = (int(s) for s in v.shape[:3])
-        if H < self.hw or W < self.hw:
+        if self.work is None and (H < self.hw or W < self.hw):
             raise ValueError("frames of %d x %d are smaller than the %d x %d crop" % (H, W, self.hw, self.hw))
+        if self.work is not None and (H < 1 or W < 1 or ops.detect_frames_scaled_ws_bytes(1, self.work[0], self.work[1], H, W) < 0):
+            raise ValueError("frames of %d x %d cannot be resampled from a working frame of %d x %d" % ((H, W) + self.work[:2]))
         starts = clip_starts(F, np.ones(F, np.int32), self.f_skip)        # every clip with a real frame: each frame belongs to exactly one
-        row0, pos = ring_place(self.pos, len(starts) * len(self.video_views(H, W) or (0,)), self.capacity, self.bs)
+        row0, pos = ring_place(self.pos, len(starts) * len(self.video_views(*self._frame(H, W)) or (0,)), self.capacity, self.bs)
         return v, starts, row0, pos
 
     def video_views(self, H, W):
-        """The views of an H x W video, None for the centre crop alone on today's path.  ValueError for views the engine cannot take."""
+        """The views of a video cut from H x W frames (its working frame, if one is set), None for the centre crop alone.  ValueError for
+        views the engine cannot take."""
         if not self.multi:
             return None
         views = make_views(H, W, self.hw, self.tile, self.flip) if self.view_list is None else check_views(self.view_list, H, W, self.hw)
@@ -596,8 +643,8 @@ class DetectEngine(ClipEngine):
         clips join the batches.  -> the index of the video in results()."""
         v, starts, row0, pos = self.check_video(frames_u8)
         F, H, W = (int(s) for s in v.shape[:3])
-        h0, w0 = centre_crop(H, W, self.hw)
-        views = self.video_views(H, W)
+        h0, w0 = centre_crop(*self._frame(H, W), self.hw)           # crop and views: of the working frame, if one is set
+        views = self.video_views(*self._frame(H, W))
         slot = self.up_slot
         self.up_slot ^= 1
         if self.up_done[slot] is not None:
@@ -606,7 +653,7 @@ class DetectEngine(ClipEngine):
         dv, _none, entry = self._upload(v)
         self.up_pin[slot] = self.pin                                  # (grown, if the video was larger than the slot)
         rec = SimpleNamespace(video=dv, truth=None, entry=entry, F=F, H=H, W=W, h0=h0, w0=w0, ready=torch.cuda.Event(), waited=False,
-                              starts=starts, rows=len(starts) * len(views or (0,)), done=0, views=views)
+                              starts=starts, rows=len(starts) * len(views or (0,)), done=0, views=views, work=self.work, wvideo=None)
         rec.ready.record(self.copy_stream)
         self.up_done[slot] = rec.ready
         # records [F][8] and the class vector [C + 2] side by side: one copy to the host takes both.  Every frame below F belongs to one clip,
@@ -622,7 +669,11 @@ class DetectEngine(ClipEngine):
         rec.imap = torch.empty(F, H, W, dtype=torch.uint8, device=self.dev) if self.instance_maps or self.instance_scores or self.instance_links else None
         rec.prob = torch.empty(F, H, W, dtype=torch.int16, device=self.dev) if self.instance_scores else None
         rec.pin = None
-        if views:
+        if rec.work:
+            need = ops.detect_frames_scaled_ws_bytes(min(self.bs // len(views or (0,)), 32), rec.work[0], rec.work[1], H, W)
+            if self.ws_scaled is None or self.ws_scaled.numel() < need:
+                self.ws_scaled = torch.empty(need, dtype=torch.uint8, device=self.dev)
+        elif views:
             need = ops.detect_frames_views_ws_bytes(min(self.bs, 32), H, W)
             if self.ws_views is None or self.ws_views.numel() < need:
                 self.ws_views = torch.empty(need, dtype=torch.uint8, device=self.dev)
@@ -633,11 +684,33 @@ class DetectEngine(ClipEngine):
     def _cut(self, rec, first, k, slot, seg):
         # view v of the segment's clip c at slot v * seg + c: this launch's clips start at `slot`.  The centre crop is the one view at stride seg.
         per, views = self.per, rec.views or [(rec.h0, rec.w0, 0)]
-        ops.clips_from_u8_views(rec.video, views, self.hw, rec.starts[first:first + k], self.f_skip, view_stride=seg,
+        video = rec.video
+        if rec.work:
+            if rec.wvideo is None:                                    # the video's first cut, behind rec.ready on this stream: its one resize
+                Hs, Ws, interp = rec.work
+                rec.wvideo = video if (Hs, Ws) == (rec.H, rec.W) else ops.resize_u8(video, Hs, Ws, INTERPOLATIONS[interp])
+            video = rec.wvideo
+        ops.clips_from_u8_views(video, views, self.hw, rec.starts[first:first + k], self.f_skip, view_stride=seg,
                                 out=self.img[slot * per * 4:(slot + (len(views) - 1) * seg + k) * per * 4])
+
+    def _release(self, v):
+        super()._release(v)
+        v.wvideo = None                                               # made and read on the compute stream alone
 
     def _collect(self, rec, first, n, slot):
         per, hw, W8 = self.per, self.hw, ops.DETECT_REC_WORDS
+        if rec.work:
+            # one launch: the views (the centre crop as the one view) merged on the working frame, resampled to native size, and the
+            # probability map with them
+            views = rec.views or [(rec.h0, rec.w0, 0)]
+            V = len(views)
+            for q in range(0, n, 32):
+                k = min(32, n - q)
+                ops.detect_frames_scaled(self.out[(slot + q) * per:(slot + q + (V - 1) * n + k) * per].view(-1, 8, hw, hw), views,
+                                         rec.starts[first + q:first + q + k], rec.F, rec.H, rec.W, rec.work[0], rec.work[1], self.f_skip, view_stride=n,
+                                         row0=rec.row0 + (first + q) * V, mask=rec.mask, prob=rec.prob, rec=rec.dev[:rec.F * W8].view(rec.F, W8),
+                                         ws=self.ws_scaled, want_mask=False)
+            return
         if rec.views:
             V = len(rec.views)
             for q in range(0, n, 32):
@@ -698,6 +771,8 @@ class DetectEngine(ClipEngine):
                     overlaps = ops.decode_instance_overlaps(words[link0:link0 + rec.link_words], self.inst_k, self.instance_links)
             out.append(Detection(int(cls[self.C]), float(cls[self.C + 1]), cls[:self.C].copy(), counts, boxes, fscores, rec.mask,
                                  list(rec.views) if rec.views else [(rec.h0, rec.w0, 0)], inst, rec.imap if self.instance_maps else None, scores, rec.prob, overlaps))
+            if rec.work:
+                out[-1].work = tuple(rec.work)
         return out
 
     def mask_runs(self, which="masks", videos=None):

@@ -720,6 +720,60 @@ def detect_frames_views(logits, views, starts, F, H, W, f_skip=2, view_stride=No
     return mask, rec
 
 
+_RESAMPLE_TABS = {}
+
+
+def resample_tables(Hs, Ws, H, W, device):
+    """pc_resample_tables(Hs, Ws, H, W) on the device: int32 [2 * (H + W)], rows [H][2] then columns [W][2] of (first tap, float32 bits of the
+    second tap's weight) that take a working frame of Hs x Ws back to the native H x W.  Host arithmetic in the library, cached per sizes and
+    device."""
+    key = (int(Hs), int(Ws), int(H), int(W), str(torch.device(device)))
+    tab = _RESAMPLE_TABS.get(key)
+    if tab is None:
+        need = capi.lib().pc_resample_tables(key[0], key[1], key[2], key[3], None, 0)
+        if need < 0:
+            capi.check(int(need))
+        host = np.zeros(int(need), np.int32)
+        got = capi.lib().pc_resample_tables(key[0], key[1], key[2], key[3], C.c_void_p(host.ctypes.data), int(need))
+        assert got == need
+        tab = _RESAMPLE_TABS[key] = torch.from_numpy(host).to(device)
+    return tab
+
+
+def detect_frames_scaled_ws_bytes(n, Hs, Ws, H, W):
+    return int(capi.lib().pc_detect_frames_scaled_ws_bytes(int(n), int(Hs), int(Ws), int(H), int(W)))
+
+
+def detect_frames_scaled(logits, views, starts, F, H, W, Hs, Ws, f_skip=2, view_stride=None, row0=0, mask=None, prob=None, rec=None, ws=None,
+                         want_mask=True):
+    """pc_detect_frames_scaled: detect_frames_views for views (h0, w0, flip) that are crops of an Hs x Ws WORKING frame, the merged logits
+    resampled bilinearly to every pixel of the native H x W frame in front of the threshold, the box, the score and the probability.
+    -> (mask uint8 [F,H,W] or None, rec int32 [F,8]) as detect_frames_views, in native coordinates; prob: a 16-bit integer device tensor
+    [F,H,W] the same launch fills as frame_probs would (only the frames the clips address), or None for none."""
+    if logits.dtype != torch.float32 or not logits.is_contiguous():
+        raise ValueError("detect_frames_scaled: contiguous float32 logits")
+    tab, V = _view_table(views, "detect_frames_scaled")
+    st, n = _starts_table(starts)
+    S = int(logits.shape[-1])
+    stride = n if view_stride is None else int(view_stride)
+    if stride < n:
+        raise ValueError("detect_frames_scaled: view_stride = %d below the %d clips" % (stride, n))
+    if int(logits.shape[-2]) != S or logits.numel() < ((V - 1) * stride + n) * 8 * S * S:
+        raise ValueError("detect_frames_scaled: logits %s do not hold %d views of %d clips of 8 x %d x %d at stride %d" % (tuple(logits.shape), V, n, S, S, stride))
+    F, H, W, Hs, Ws = int(F), int(H), int(W), int(Hs), int(Ws)
+    need = detect_frames_scaled_ws_bytes(n, Hs, Ws, H, W)
+    if need < 0:
+        raise ValueError("detect_frames_scaled: %d clips, working frame %d x %d, native frame %d x %d" % (n, Hs, Ws, H, W))
+    mask, rec, ws = _detect_buffers("detect_frames_scaled", logits.device, F, H, W, mask, rec, ws, want_mask,
+                                    "detect_frames_scaled_ws_bytes(n, Hs, Ws, H, W)", need)
+    if prob is not None:
+        prob = _prob_tensor("detect_frames_scaled", prob, F, H, W, logits.device)
+    dev_tab = resample_tables(Hs, Ws, H, W, logits.device)
+    capi.call("pc_detect_frames_scaled", ptr(logits), F, H, W, Hs, Ws, S, tab, V, stride, st, n, int(f_skip), int(row0), ptr(dev_tab), ptr(mask),
+              ptr(prob), ptr(rec), ptr(ws), stream())
+    return mask, rec
+
+
 def decode_detect_records(rec):
     """Host int32 [F,8] records (numpy or torch) -> (counts int32 [F], boxes int32 [F,4] = x0, y0, x1, y1, frame_scores float32 [F], rows int32 [F])."""
     r = np.ascontiguousarray(rec.cpu().numpy() if torch.is_tensor(rec) else rec, dtype=np.int32).reshape(-1, DETECT_REC_WORDS)

@@ -28,10 +28,15 @@ v-mAP at 0.2 and 0.5 and the accuracy are printed, and score_table_i int32 [F, 3
 (inter, union, gt), score_label_i and the arrays of the result (score_fmAP [20], score_vmAP [20], score_frame_ious, score_video_ious,
 score_n_tot_frames, score_n_vids, score_n_correct, score_accuracy) are stored.  The truth is taken on the full frame, not inside the centre
 crop as evalstep.EvalEngine takes it.  With --synthetic the truth and label of synthetic.make_eval_videos_u8 are used (--score).
+--frame_size Hs Ws [--interp area|linear|nearest]: every video is resized on the device to an Hs x Ws working frame (cv2.resize's arithmetic;
+the JHMDB loader's is 256 256 area), cut and run there, and detected at its NATIVE size (DetectEngine.set_working_frame: the merged logits
+resampled bilinearly to every native pixel in front of the threshold).  Everything stored stays in native coordinates but views_i, which are
+crops of the working frame; work_i int32 [3] = (Hs, Ws, cv2 interpolation flag) records it.  A video smaller than hw is then taken.
 
     python tools/detect.py --out detections.npz [--ckpt best_model.pth] [--synthetic 4 | video.npy ...] [--masks] [--pack] [--tile] [--flip]
                            [--max-gap 0] [--min-pixels 1] [--instances K] [--min_area 1] [--conn 8] [--instance_maps] [--instance_scores]
                            [--instance_links L] [--link box|mask] [--mask_runs] [--truth t0.npy ... --labels l0 ... | --score]
+                           [--frame_size Hs Ws [--interp area|linear|nearest]]
 """
 import argparse
 import os
@@ -71,6 +76,8 @@ def main():
     ap.add_argument("--truth", nargs="+", default=None, help="one .npy of uint8 truth [F,H,W] or [F,H,W,1] per video: score the pass against them")
     ap.add_argument("--labels", nargs="+", type=int, default=None, help="with --truth: one class id per video")
     ap.add_argument("--score", action="store_true", help="with synthetic videos: score the pass against their own truth and labels")
+    ap.add_argument("--frame_size", nargs=2, type=int, default=None, metavar=("Hs", "Ws"), help="resize every video to this working frame on the device; results stay at native size")
+    ap.add_argument("--interp", default="area", choices=sorted(detect.INTERPOLATIONS), help="with --frame_size: cv2.resize's interpolation")
     a = ap.parse_args()
     if (a.truth is None) != (a.labels is None) or (a.truth is not None and not (len(a.truth) == len(a.labels) == len(a.videos))):
         raise SystemExit("tools/detect.py: --truth and --labels go together, one of each per video file")
@@ -105,6 +112,11 @@ def main():
     engine = detect.DetectEngine(bs=a.bs, hw=a.hw, num_classes=a.classes, state=state, pack=a.pack, masks=a.masks or a.mask_runs or a.instances > 0 or truths is not None, tile=a.tile,
                                  flip=a.flip, instances=a.instances, min_area=a.min_area, conn=a.conn, instance_maps=a.instance_maps,
                                  instance_scores=a.instance_scores, instance_links=a.instance_links)
+    if a.frame_size:
+        try:
+            engine.set_working_frame(tuple(a.frame_size), a.interp)
+        except ValueError as e:
+            raise SystemExit("tools/detect.py: --frame_size: %s" % e)
     engine.begin()
     for v in videos:
         engine.add_video(v)
@@ -130,6 +142,8 @@ def main():
         out.update({"label_%d" % i: np.int32(d.label), "class_scores_%d" % i: d.class_scores, "counts_%d" % i: d.counts, "boxes_%d" % i: d.boxes,
                     "frame_scores_%d" % i: d.frame_scores, "views_%d" % i: np.array(d.views, np.int32).reshape(-1, 3),
                     "tubes_%d" % i: np.array([(t0, t1, s) for t0, t1, _b, s in tubes], np.float64).reshape(-1, 3)})
+        if d.work is not None:
+            out["work_%d" % i] = np.array([d.work[0], d.work[1], detect.INTERPOLATIONS[d.work[2]]], np.int32)
         if a.masks:
             m = d.masks.cpu().numpy()
             out.update({"masks_%d" % i: np.packbits(m), "mask_shape_%d" % i: np.array(m.shape, np.int64)})
