@@ -69,7 +69,8 @@ typedef void* pc_stream;            /* hipStream_t */
  * pc_detect_frames_views_ws_bytes came later and move nothing: no struct grew, no op's operands changed; so did pc_frame_instances with its
  * PC_INST_* constants, pc_frame_probs / pc_instance_scores with PC_PROB_ONE / PC_SCORE_WORDS, pc_instance_overlaps with PC_LINK_MAX_LAGS, pc_mask_run_ws_bytes /
  * pc_mask_run_index / pc_mask_runs with PC_RUN_WORDS, pc_map_crosstab / pc_map_crosstab_ws_bytes with PC_CROSS_MAX_SLOTS, and pc_resample_tables / pc_detect_frames_scaled_ws_bytes /
- * pc_detect_frames_scaled: came later, move nothing).  Descriptors must be zero-initialised by the caller:
+ * pc_detect_frames_scaled, and pc_clip_hop_starts / pc_clip_planes_bytes / pc_clip_planes / pc_detect_frames_planes_ws_bytes /
+ * pc_detect_frames_planes with PC_PLANES_MAX_FRAMES: came later, move nothing).  Descriptors must be zero-initialised by the caller:
  * fields added later read as "old behaviour" when 0.  pc_version() returns the value the library was built with; the Python host
  * (capi.lib()) refuses a library whose version differs from the header it mirrors. */
 #define PC_VERSION 107
@@ -582,6 +583,43 @@ int64_t pc_detect_frames_scaled_ws_bytes(int n, int Hs, int Ws, int H, int W);
 int     pc_detect_frames_scaled(const float* logits, int F, int H, int W, int Hs, int Ws, int S, const int32_t* views, int V, int view_stride,
                                 const int32_t* starts, int n, int f_skip, int row0, const int32_t* dev_tab, uint8_t* mask, uint16_t* prob,
                                 int32_t* rec, void* ws, pc_stream s);
+/* Overlapping clips in time, merged per frame (csrc/cliphop.hip, the rule in csrc/cliphop.h; picons_amd/detect.py: DetectEngine.set_clip_hop).
+ * span = 8 * f_skip; hop is a multiple of f_skip in [f_skip, span] (f_skip <= 2^20).  Windows start at m * hop; window m is kept iff m == 0 or
+ * (m - 1) * hop + span < F.  Clip starts are m * hop + j for every kept window and every phase j < f_skip with m * hop + j < F, in that
+ * order; the clip with start s has index (s / hop) * f_skip + s % hop.  Frame f lies in the windows lo = max(0, ceil((f - span + 1) / hop))
+ * .. hi = min(f / hop, windows - 1): at least 1, at most M = ceil(span / hop) <= 8, with pairwise distinct m % M.  hop == span is the cut of
+ * pc_detect_frames*: every frame in one window.
+ * pc_clip_hop_starts is HOST arithmetic: it returns the clip count and writes `starts` if it is not null and `cap` entries suffice;
+ * PC_E_ARG (-1) for F < 1 or a bad f_skip / hop.
+ * pc_clip_planes: logits, views (crops of the Hs x Ws frame: the working frame, or the native one), view_stride, starts, n <= 32 are
+ * pc_detect_frames_views'.  Frame k of clip c goes to slot (starts[c] / hop) % M of frame starts[c] + k * f_skip in plane float32
+ * [M][F][pstride], pstride = Hs * Ws rounded up to 4: the merged logit of pc_detect_frames_views (csrc/viewmerge.h) bit for bit, 0.0f where no
+ * view covers, in 16-byte stores, each logit fetched once.  cover uint8 [pstride], the views that cover each pixel -- the same for every
+ * clip of a video --, is written if it is not null.  A frame >= F is neither read nor written; a (slot, frame) the launch does not address
+ * is not touched; two clips of one launch never address the same one, so there are no atomics, nothing is zeroed and the order of a
+ * video's launches does not matter.  pc_clip_planes_bytes (host-only; -1 for a size < 1, Hs * Ws >= 2^31, a bad f_skip / hop) =
+ * M * F * pstride * 4 + pstride: the planes, then the cover.  Refusals (PC_E_ARG before any HIP call): null logits, views, starts or plane;
+ * pc_detect_frames_views' checks of F, Hs, Ws, S, V, n, view_stride, f_skip, views and negative starts; a bad hop; a start below F that is
+ * no clip start of the rule; logits or plane not 16-byte, cover not 4-byte aligned; a cover together with starts[0] >= F.
+ * pc_detect_frames_planes: for each of the frames f0 .. f0 + nf - 1 (nf <= PC_PLANES_MAX_FRAMES) and no others, steps 2 and 3 of
+ * pc_detect_frames_scaled with M[y][x] the mean of the frame's plane value over the windows lo .. hi in ascending order -- the first value as
+ * it is, the others added in fp32 round-to-nearest, one fp32 division by the count when it is above 1 -- and the cover byte that of the
+ * video.  A slot no window filled is never read.  dev_tab: the device copy of pc_resample_tables(Hs, Ws, H, W), the identity for equal
+ * sizes, where every output is the unscaled path's bit for bit.  rec[6] = row0 + V * (lo * f_skip + f % f_skip), the score row of the first
+ * clip that holds the frame; rec[7] = 0.  mask and prob may be null; the records are the same either way.  Two launches, no atomics.
+ * ws: pc_detect_frames_planes_ws_bytes(nf, H, W) bytes (host-only; -1 for nf outside 1..PC_PLANES_MAX_FRAMES, a size < 1, H * W >= 2^31),
+ * 8-byte aligned, contents irrelevant before and meaningless after.  Refusals (PC_E_ARG before any HIP call): null plane, cover, dev_tab, rec
+ * or ws; F < 1; a size < 1; Hs * Ws or H * W >= 2^31; 2 * max(H, W) >= 2^24; V outside 1..32; a bad hop; f0 < 0, nf outside
+ * 1..PC_PLANES_MAX_FRAMES, f0 + nf > F; row0 < 0 or row0 + V * clips > INT_MAX; plane not 16-byte, cover, dev_tab or rec not 4-byte, ws not
+ * 8-byte, prob not 2-byte aligned. */
+#define PC_PLANES_MAX_FRAMES 256
+int64_t pc_clip_hop_starts(int F, int f_skip, int hop, int32_t* starts, int64_t cap);
+int64_t pc_clip_planes_bytes(int F, int Hs, int Ws, int f_skip, int hop);
+int     pc_clip_planes(const float* logits, int F, int Hs, int Ws, int S, const int32_t* views, int V, int view_stride, const int32_t* starts, int n,
+                       int f_skip, int hop, float* plane, uint8_t* cover, pc_stream s);
+int64_t pc_detect_frames_planes_ws_bytes(int nf, int H, int W);
+int     pc_detect_frames_planes(const float* plane, const uint8_t* cover, int F, int H, int W, int Hs, int Ws, int V, int f_skip, int hop, int f0,
+                                int nf, int row0, const int32_t* dev_tab, uint8_t* mask, uint16_t* prob, int32_t* rec, void* ws, pc_stream s);
 /* cv2.resize on uint8 images [n][H][W][C] -> [n][Ho][Wo][C] (C <= 4), the calls of the reference's loaders:
  * datasets/jhmdb_dataloader.py:252 (frames, INTER_AREA 320x240 -> 256x256), :267,:281 (puppet masks, INTER_NEAREST),
  * :192,:208 and ucf_dataloader.py:165,171 (224 crop -> frame size, INTER_LINEAR; the identity at 224).  OpenCV's 8-bit

@@ -165,6 +165,11 @@ _SIGS = {
     "pc_detect_frames_scaled_ws_bytes": (i64, [i32, i32, i32, i32, i32]),
     "pc_detect_frames_scaled": (i32, [vp, i32, i32, i32, i32, i32, i32, C.POINTER(C.c_int32), i32, i32, C.POINTER(C.c_int32), i32, i32, i32, vp, vp, vp, vp,
                                       vp, vp]),
+    "pc_clip_hop_starts": (i64, [i32, i32, i32, vp, i64]),
+    "pc_clip_planes_bytes": (i64, [i32, i32, i32, i32, i32]),
+    "pc_clip_planes": (i32, [vp, i32, i32, i32, i32, C.POINTER(C.c_int32), i32, i32, C.POINTER(C.c_int32), i32, i32, i32, vp, vp, vp]),
+    "pc_detect_frames_planes_ws_bytes": (i64, [i32, i32, i32]),
+    "pc_detect_frames_planes": (i32, [vp, vp, i32, i32, i32, i32, i32, i32, i32, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp]),
     "pc_resize_tables": (i64, [i32, i32, i32, i32, i32, vp, i64]),
     "pc_resize_u8": (i32, [vp, i32, i32, i32, i32, i32, i32, vp, i32, vp, vp]),
     "pc_fill": (i32, [vp, i64, f32, vp]),

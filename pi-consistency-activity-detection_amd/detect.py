@@ -46,6 +46,12 @@ Working frame.  The crops are cut at the video's own pixel scale unless DetectEn
 every video is resized on the device to Hs x Ws (pc_resize_u8: cv2.resize restated), the views are crops of that working frame, and
 pc_detect_frames_scaled merges them there and resamples the merged logits bilinearly to every native pixel in front of the threshold, the
 box, the score and the probability -- masks, records, instances, runs and score() stand in native coordinates at native size as before.
+
+Clip hop.  A video is cut into windows of 8 * f_skip frames that start every 8 * f_skip frames, so every frame is decided by one forward,
+unless DetectEngine.set_clip_hop(hop) is called: then the windows start every `hop` frames (clip_starts_hop), a frame lies in up to
+ceil(8 * f_skip / hop) of them, pc_clip_planes keeps the merged logits of every (window, frame) on the device until the video's last clip has
+run, and pc_detect_frames_planes averages the windows that hold a frame in front of the resample, the threshold, the box, the score and the
+probability.  Everything behind mask, probability and record -- instances, scores, links, runs, score() -- works on them unchanged.
 """
 from types import SimpleNamespace
 
@@ -199,6 +205,17 @@ def _link_instances(who, inst_kept, inst_boxes, inst_areas, frame_scores, iou_mi
     return out
 
 
+def clip_starts_hop(F, f_skip, hop):
+    """The clip starts of a video of F frames cut into overlapping windows (csrc/cliphop.h, restated; tests/test_clip_hop_cpu.py holds the
+    two to each other): windows of span = 8 * f_skip frames start every `hop` frames, hop a multiple of f_skip in [f_skip, span]; window i
+    is kept iff i == 0 or i - hop + span < F (stop behind the first window that reaches the video's end); the starts are i + j for every
+    kept window and phase j < f_skip with i + j < F, in that order.  hop == span: evalstep.clip_starts(F, ones, f_skip)."""
+    span = 8 * f_skip
+    if F < 1 or not 1 <= f_skip <= 1 << 20 or hop % f_skip or not f_skip <= hop <= span:      # (2^20: the library's bound on f_skip)
+        raise ValueError("clip_starts_hop: F = %r, f_skip = %r, hop = %r (F >= 1, hop a multiple of f_skip in [f_skip, 8 * f_skip])" % (F, f_skip, hop))
+    return [i + j for i in range(0, F, hop) if i == 0 or i - hop + span < F for j in range(f_skip) if i + j < F]
+
+
 def _tile_offsets(L, hw):
     nt = -(-L // hw)
     return [0] if nt == 1 else [(i * (L - hw)) // (nt - 1) for i in range(nt)]
@@ -236,7 +253,8 @@ class Detection:
     counts [F] positive pixels, boxes [F, 4] = x0, y0, x1, y1 (half-open, full-frame coordinates, zeros for an empty frame) and frame_scores [F]
     (mean sigmoid over the positive pixels) per frame; masks: device uint8 [F, H, W] or None; views: the (h0, w0, flip) the video was seen
     through; work: None, or (Hs, Ws, interpolation) when the video was resized to a working frame (DetectEngine.set_working_frame) -- the
-    views are then in WORKING-frame coordinates, everything else in native ones.
+    views are then in WORKING-frame coordinates, everything else in native ones; hop: None, or the distance between two windows when the
+    video was cut into overlapping clips (DetectEngine.set_clip_hop) -- class_scores are then the mean over the rows of ALL its clips.
 
     With DetectEngine(instances=K) also the frame's connected components of at least min_area pixels, ranked by area (ties: the first pixel in
     raster order): inst_n [F] how many there are, inst_kept [F] = min(inst_n, K) how many are held, inst_flags [F] (bit 0: the frame had more
@@ -255,6 +273,7 @@ class Detection:
     frame whose overflow flag is set; zeros where frame f + l + 1 does not exist).  None without the option."""
 
     work = None                          # set by DetectEngine.results() behind the constructor, whose parameter list is pinned
+    hop = None                           # likewise
 
     def __init__(self, label, class_score, class_scores, counts, boxes, frame_scores, masks, views=None, inst=None, imap=None, scores=None, probs=None,
                  inst_overlaps=None):
@@ -529,7 +548,13 @@ class DetectEngine(ClipEngine):
     instance_maps asks for it.  0: nothing of this, no buffer and no launch.
 
     set_working_frame((Hs, Ws), interpolation): videos added from then on are resized on the device to Hs x Ws, cut and run there, and
-    detected at native size through pc_detect_frames_scaled (below)."""
+    detected at native size through pc_detect_frames_scaled (below).
+
+    set_clip_hop(hop): videos added from then on are cut into overlapping windows that start every `hop` frames and every frame is
+    detected from the mean of the windows that hold it (below)."""
+
+    hop = None                           # set_clip_hop: the distance between two windows for the videos to come, None for today's cut
+    ws_planes = None                     # pc_detect_frames_planes' partials, grown only for a larger frame
 
     def __init__(self, bs=14, hw=224, num_classes=24, device="cuda:0", state=None, engine=None, capacity=256, seed=47, f_skip=2, pack=False,
                  masks=True, on_batch=None, tile=False, flip=False, views=None, instances=0, min_area=1, conn=8, instance_maps=False,
@@ -606,6 +631,28 @@ class DetectEngine(ClipEngine):
             raise ValueError("set_working_frame: interpolation = %r, one of %s" % (interpolation, ", ".join(sorted(INTERPOLATIONS))))
         self.work = (Hs, Ws, interpolation)
 
+    def set_clip_hop(self, hop=None):
+        """hop: an int, a multiple of f_skip in [f_skip, 8 * f_skip): every video added from now on is cut into windows of 8 * f_skip frames
+        that start every `hop` frames (clip_starts_hop), so a frame lies in up to ceil(8 * f_skip / hop) clips.  Behind each forward one
+        pc_clip_planes launch per video segment (instead of pc_detect_frames* and pc_frame_probs) keeps the merged logits of the clips'
+        frames in the video's slot planes -- M * F * pstride * 4 + pstride bytes, M = ceil(8 * f_skip / hop), pstride the pixels of the
+        frame the views are cut from rounded up to 4, held until the video's last clip has run --, and behind that clip
+        pc_detect_frames_planes averages per frame the windows that hold it, in window order, in front of the resample (the identity
+        without a working frame), the threshold, the box, the score and the probability.  Masks, records, instances, scores, links, runs and
+        score() are made from that as before; the class is voted over the rows of ALL the video's clips, which now overlap.  Each video
+        keeps the hop it was added under (Detection.hop).  hop=None or 8 * f_skip: today's cut and today's launches.  ValueError for
+        anything else; nothing changes then."""
+        span = 8 * self.f_skip
+        if hop is None:
+            self.hop = None
+            return
+        if isinstance(hop, bool) or not isinstance(hop, (int, np.integer)):
+            raise ValueError("set_clip_hop: hop = %r, an int or None" % (hop,))
+        hop = int(hop)
+        if hop % self.f_skip or not self.f_skip <= hop <= span:
+            raise ValueError("set_clip_hop: hop = %d, a multiple of f_skip = %d in [%d, %d]" % (hop, self.f_skip, self.f_skip, span))
+        self.hop = None if hop == span else hop
+
     def _frame(self, H, W):
         """The frame the views of an H x W video are cut from: the working frame if one is set, else its own."""
         return (H, W) if self.work is None else self.work[:2]
@@ -621,8 +668,17 @@ class DetectEngine(ClipEngine):
             raise ValueError("frames of %d x %d are smaller than the %d x %d crop" % (H, W, self.hw, self.hw))
         if self.work is not None and (H < 1 or W < 1 or ops.detect_frames_scaled_ws_bytes(1, self.work[0], self.work[1], H, W) < 0):
             raise ValueError("frames of %d x %d cannot be resampled from a working frame of %d x %d" % ((H, W) + self.work[:2]))
-        starts = clip_starts(F, np.ones(F, np.int32), self.f_skip)        # every clip with a real frame: each frame belongs to exactly one
-        row0, pos = ring_place(self.pos, len(starts) * len(self.video_views(*self._frame(H, W)) or (0,)), self.capacity, self.bs)
+        width = len(self.video_views(*self._frame(H, W)) or (0,))
+        if self.hop is None:
+            starts = clip_starts(F, np.ones(F, np.int32), self.f_skip)    # every clip with a real frame: each frame belongs to exactly one
+        else:
+            starts = clip_starts_hop(F, self.f_skip, self.hop)            # overlapping windows: a frame belongs to up to ceil(span / hop) clips
+            if len(starts) * width > self.capacity - self.bs:
+                raise ValueError("a video of %d frames takes %d clips at hop = %d, %d rows of the tables: more than capacity - bs = %d - %d"
+                                 % (F, len(starts), self.hop, len(starts) * width, self.capacity, self.bs))
+            if ops.clip_planes_bytes(F, *self._frame(H, W), self.f_skip, self.hop) < 0 or ops.detect_frames_planes_ws_bytes(1, H, W) < 0:
+                raise ValueError("frames of %d x %d cannot be detected at hop = %d" % (H, W, self.hop))
+        row0, pos = ring_place(self.pos, len(starts) * width, self.capacity, self.bs)
         return v, starts, row0, pos
 
     def video_views(self, H, W):
@@ -669,7 +725,15 @@ class DetectEngine(ClipEngine):
         rec.imap = torch.empty(F, H, W, dtype=torch.uint8, device=self.dev) if self.instance_maps or self.instance_scores or self.instance_links else None
         rec.prob = torch.empty(F, H, W, dtype=torch.int16, device=self.dev) if self.instance_scores else None
         rec.pin = None
-        if rec.work:
+        rec.hop, rec.planes = self.hop, None
+        if rec.hop:
+            # the slot planes and the cover of the frame the views are cut from, in one allocation, until the video's last clip has run;
+            # every (slot, frame) that is read has been written by a launch: nothing is filled
+            rec.planes = torch.empty(ops.clip_planes_bytes(F, *self._frame(H, W), self.f_skip, rec.hop), dtype=torch.uint8, device=self.dev)
+            need = ops.detect_frames_planes_ws_bytes(min(F, ops.PLANES_MAX_FRAMES), H, W)
+            if self.ws_planes is None or self.ws_planes.numel() < need:
+                self.ws_planes = torch.empty(need, dtype=torch.uint8, device=self.dev)
+        elif rec.work:
             need = ops.detect_frames_scaled_ws_bytes(min(self.bs // len(views or (0,)), 32), rec.work[0], rec.work[1], H, W)
             if self.ws_scaled is None or self.ws_scaled.numel() < need:
                 self.ws_scaled = torch.empty(need, dtype=torch.uint8, device=self.dev)
@@ -699,6 +763,17 @@ class DetectEngine(ClipEngine):
 
     def _collect(self, rec, first, n, slot):
         per, hw, W8 = self.per, self.hw, ops.DETECT_REC_WORDS
+        if rec.hop:
+            # one launch: the views (the centre crop as the one view) merged on the frame they are cut from, into the video's slot planes;
+            # the cover bytes with the video's first launch.  Mask, records and probability wait for the last clip (_finish).
+            views = rec.views or [(rec.h0, rec.w0, 0)]
+            V = len(views)
+            Hs, Ws = rec.work[:2] if rec.work else (rec.H, rec.W)
+            for q in range(0, n, 32):
+                k = min(32, n - q)
+                ops.clip_planes(self.out[(slot + q) * per:(slot + q + (V - 1) * n + k) * per].view(-1, 8, hw, hw), views, rec.starts[first + q:first + q + k],
+                                rec.F, Hs, Ws, self.f_skip, rec.hop, view_stride=n, planes=rec.planes, cover=first + q == 0)
+            return
         if rec.work:
             # one launch: the views (the centre crop as the one view) merged on the working frame, resampled to native size, and the
             # probability map with them
@@ -735,6 +810,14 @@ class DetectEngine(ClipEngine):
         """The video's class from its score rows, its instances from its masks (every frame has been written by now, on this stream); records,
         class vector and instances on their way to the host."""
         cls0 = rec.F * ops.DETECT_REC_WORDS
+        if rec.hop:
+            # every clip's frames lie in the slot planes: per frame the mean of the windows that hold it -> mask, probability and records
+            Hs, Ws = rec.work[:2] if rec.work else (rec.H, rec.W)
+            for f0 in range(0, rec.F, ops.PLANES_MAX_FRAMES):
+                ops.detect_frames_planes(rec.planes, rec.F, rec.H, rec.W, Hs, Ws, self._width(rec), self.f_skip, rec.hop, f0,
+                                         min(ops.PLANES_MAX_FRAMES, rec.F - f0), row0=rec.row0, mask=rec.mask, prob=rec.prob,
+                                         rec=rec.dev[:cls0].view(rec.F, ops.DETECT_REC_WORDS), ws=self.ws_planes, want_mask=False)
+            rec.planes = None                                         # written and read on the compute stream alone: the allocator may reuse them
         ops.video_class(self.scores[rec.row0:rec.row0 + rec.rows], out=rec.dev[cls0:cls0 + self.C + 2].view(torch.float32))
         if self.inst_k:
             inst0 = cls0 + self.C + 2
@@ -773,6 +856,8 @@ class DetectEngine(ClipEngine):
                                  list(rec.views) if rec.views else [(rec.h0, rec.w0, 0)], inst, rec.imap if self.instance_maps else None, scores, rec.prob, overlaps))
             if rec.work:
                 out[-1].work = tuple(rec.work)
+            if rec.hop:
+                out[-1].hop = rec.hop
         return out
 
     def mask_runs(self, which="masks", videos=None):

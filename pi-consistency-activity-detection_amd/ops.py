@@ -774,6 +774,94 @@ def detect_frames_scaled(logits, views, starts, F, H, W, Hs, Ws, f_skip=2, view_
     return mask, rec
 
 
+PLANES_MAX_FRAMES = 256     # PC_PLANES_MAX_FRAMES of include/picons.h: the frames of one pc_detect_frames_planes range
+
+
+def clip_hop_starts(F, f_skip, hop):
+    """pc_clip_hop_starts: the clip starts of a video of F frames cut into windows of 8 * f_skip frames every `hop` frames (host arithmetic
+    in the library; csrc/cliphop.h states the rule) -> list of ints.  ValueError for F < 1 or a hop that is no multiple of f_skip in
+    [f_skip, 8 * f_skip]."""
+    F, f_skip, hop = int(F), int(f_skip), int(hop)
+    need = int(capi.lib().pc_clip_hop_starts(F, f_skip, hop, None, 0))
+    if need < 0:
+        raise ValueError("clip_hop_starts: F = %d, f_skip = %d, hop = %d" % (F, f_skip, hop))
+    host = np.zeros(need, np.int32)
+    got = capi.lib().pc_clip_hop_starts(F, f_skip, hop, C.c_void_p(host.ctypes.data), need)
+    assert got == need
+    return host.tolist()
+
+
+def clip_planes_bytes(F, Hs, Ws, f_skip, hop):
+    """pc_clip_planes_bytes: the bytes of a video's slot planes float32 [M][F][pstride] and, behind them, its cover bytes [pstride]; -1 for
+    sizes or a hop the library does not take."""
+    return int(capi.lib().pc_clip_planes_bytes(int(F), int(Hs), int(Ws), int(f_skip), int(hop)))
+
+
+def clip_plane_views(planes, F, Hs, Ws, f_skip, hop):
+    """The two parts of a clip_planes buffer -> (plane float32 [M, F, pstride], cover uint8 [pstride]), views of `planes`."""
+    need = clip_planes_bytes(F, Hs, Ws, f_skip, hop)
+    if need < 0:
+        raise ValueError("clip_planes: %d frames of %d x %d, f_skip = %d, hop = %d" % (F, Hs, Ws, f_skip, hop))
+    if planes.dtype != torch.uint8 or not planes.is_contiguous() or planes.numel() < need:
+        raise ValueError("clip_planes: planes must be a contiguous uint8 device tensor of clip_planes_bytes(F, Hs, Ws, f_skip, hop) = %d bytes" % need)
+    ps = (int(Hs) * int(Ws) + 3) // 4 * 4
+    M = (need - ps) // (4 * int(F) * ps)
+    return planes[:need - ps].view(torch.float32).view(M, int(F), ps), planes[need - ps:need]
+
+
+def clip_planes(logits, views, starts, F, Hs, Ws, f_skip, hop, view_stride=None, planes=None, cover=True):
+    """pc_clip_planes: the logits, views and starts of detect_frames_views for n <= 32 clips of one video cut at `hop` -> `planes`, a uint8
+    device tensor of clip_planes_bytes(F, Hs, Ws, f_skip, hop): frame k of clip c as the merged logits of the Hs x Ws frame in slot
+    (starts[c] / hop) % M of frame starts[c] + k * f_skip.  cover=True: the launch also writes the cover bytes (a video's first launch).  A
+    given buffer is written in place -- only the (slot, frame) pairs the clips address; a fresh one is NOT filled."""
+    if logits.dtype != torch.float32 or not logits.is_contiguous():
+        raise ValueError("clip_planes: contiguous float32 logits")
+    tab, V = _view_table(views, "clip_planes")
+    st, n = _starts_table(starts)
+    S = int(logits.shape[-1])
+    stride = n if view_stride is None else int(view_stride)
+    if stride < n:
+        raise ValueError("clip_planes: view_stride = %d below the %d clips" % (stride, n))
+    if int(logits.shape[-2]) != S or logits.numel() < ((V - 1) * stride + n) * 8 * S * S:
+        raise ValueError("clip_planes: logits %s do not hold %d views of %d clips of 8 x %d x %d at stride %d" % (tuple(logits.shape), V, n, S, S, stride))
+    F, Hs, Ws, f_skip, hop = int(F), int(Hs), int(Ws), int(f_skip), int(hop)
+    need = clip_planes_bytes(F, Hs, Ws, f_skip, hop)
+    if need < 0:
+        raise ValueError("clip_planes: %d frames of %d x %d, f_skip = %d, hop = %d" % (F, Hs, Ws, f_skip, hop))
+    if planes is None:
+        planes = torch.empty(need, dtype=torch.uint8, device=logits.device)
+    elif planes.device != logits.device:
+        raise ValueError("clip_planes: planes must be on the logits' device")
+    plane, cov = clip_plane_views(planes, F, Hs, Ws, f_skip, hop)
+    capi.call("pc_clip_planes", ptr(logits), F, Hs, Ws, S, tab, V, stride, st, n, f_skip, hop, ptr(plane), ptr(cov) if cover else None, stream())
+    return planes
+
+
+def detect_frames_planes_ws_bytes(nf, H, W):
+    return int(capi.lib().pc_detect_frames_planes_ws_bytes(int(nf), int(H), int(W)))
+
+
+def detect_frames_planes(planes, F, H, W, Hs, Ws, V, f_skip, hop, f0=0, nf=None, row0=0, mask=None, prob=None, rec=None, ws=None, want_mask=True):
+    """pc_detect_frames_planes: the buffer clip_planes filled for every clip of a video -> the frames f0 .. f0 + nf - 1 (nf at most
+    PLANES_MAX_FRAMES; default: the rest of the video) detected at native size from the mean of the windows that hold each frame.
+    -> (mask uint8 [F,H,W] or None, rec int32 [F,8]) as detect_frames_scaled, rec[:, 6] = row0 + V * (the first clip that holds the frame);
+    prob as there.  Given tensors are written in place -- only the frames of the range -- fresh ones are zero-filled first."""
+    F, H, W, Hs, Ws, f0 = int(F), int(H), int(W), int(Hs), int(Ws), int(f0)
+    nf = F - f0 if nf is None else int(nf)
+    plane, cov = clip_plane_views(planes, F, Hs, Ws, f_skip, hop)
+    need = detect_frames_planes_ws_bytes(nf, H, W)
+    if need < 0 or f0 < 0 or f0 + nf > F:
+        raise ValueError("detect_frames_planes: frames %d .. %d + %d of %d (a range holds 1..%d), native frame %d x %d" % (f0, f0, nf, F, PLANES_MAX_FRAMES, H, W))
+    mask, rec, ws = _detect_buffers("detect_frames_planes", planes.device, F, H, W, mask, rec, ws, want_mask, "detect_frames_planes_ws_bytes(nf, H, W)",
+                                    need)
+    if prob is not None:
+        prob = _prob_tensor("detect_frames_planes", prob, F, H, W, planes.device)
+    dev_tab = resample_tables(Hs, Ws, H, W, planes.device)
+    capi.call("pc_detect_frames_planes", ptr(plane), ptr(cov), F, H, W, Hs, Ws, int(V), int(f_skip), int(hop), f0, nf, int(row0), ptr(dev_tab), ptr(mask),
+              ptr(prob), ptr(rec), ptr(ws), stream())
+    return mask, rec
+
+
 def decode_detect_records(rec):
     """Host int32 [F,8] records (numpy or torch) -> (counts int32 [F], boxes int32 [F,4] = x0, y0, x1, y1, frame_scores float32 [F], rows int32 [F])."""
     r = np.ascontiguousarray(rec.cpu().numpy() if torch.is_tensor(rec) else rec, dtype=np.int32).reshape(-1, DETECT_REC_WORDS)

@@ -32,11 +32,14 @@ crop as evalstep.EvalEngine takes it.  With --synthetic the truth and label of s
 the JHMDB loader's is 256 256 area), cut and run there, and detected at its NATIVE size (DetectEngine.set_working_frame: the merged logits
 resampled bilinearly to every native pixel in front of the threshold).  Everything stored stays in native coordinates but views_i, which are
 crops of the working frame; work_i int32 [3] = (Hs, Ws, cv2 interpolation flag) records it.  A video smaller than hw is then taken.
+--hop N: the clips of a video start every N frames instead of every 16 (DetectEngine.set_clip_hop: N a multiple of f_skip = 2 in 2..16), a
+frame lies in up to 16 / N of them, and mask, box, score and probability come from the mean of their merged logits; hop_i records it.  The
+class is voted over all the overlapping clips.  The effect on f-mAP / v-mAP is not measured.
 
     python tools/detect.py --out detections.npz [--ckpt best_model.pth] [--synthetic 4 | video.npy ...] [--masks] [--pack] [--tile] [--flip]
                            [--max-gap 0] [--min-pixels 1] [--instances K] [--min_area 1] [--conn 8] [--instance_maps] [--instance_scores]
                            [--instance_links L] [--link box|mask] [--mask_runs] [--truth t0.npy ... --labels l0 ... | --score]
-                           [--frame_size Hs Ws [--interp area|linear|nearest]]
+                           [--frame_size Hs Ws [--interp area|linear|nearest]] [--hop N]
 """
 import argparse
 import os
@@ -78,6 +81,7 @@ def main():
     ap.add_argument("--score", action="store_true", help="with synthetic videos: score the pass against their own truth and labels")
     ap.add_argument("--frame_size", nargs=2, type=int, default=None, metavar=("Hs", "Ws"), help="resize every video to this working frame on the device; results stay at native size")
     ap.add_argument("--interp", default="area", choices=sorted(detect.INTERPOLATIONS), help="with --frame_size: cv2.resize's interpolation")
+    ap.add_argument("--hop", type=int, default=None, help="cut overlapping clips that start every N frames and average the clips that hold a frame (a multiple of 2 in 2..16; 16: today's cut)")
     a = ap.parse_args()
     if (a.truth is None) != (a.labels is None) or (a.truth is not None and not (len(a.truth) == len(a.labels) == len(a.videos))):
         raise SystemExit("tools/detect.py: --truth and --labels go together, one of each per video file")
@@ -117,6 +121,11 @@ def main():
             engine.set_working_frame(tuple(a.frame_size), a.interp)
         except ValueError as e:
             raise SystemExit("tools/detect.py: --frame_size: %s" % e)
+    if a.hop is not None:
+        try:
+            engine.set_clip_hop(a.hop)
+        except ValueError as e:
+            raise SystemExit("tools/detect.py: --hop: %s" % e)
     engine.begin()
     for v in videos:
         engine.add_video(v)
@@ -144,6 +153,8 @@ def main():
                     "tubes_%d" % i: np.array([(t0, t1, s) for t0, t1, _b, s in tubes], np.float64).reshape(-1, 3)})
         if d.work is not None:
             out["work_%d" % i] = np.array([d.work[0], d.work[1], detect.INTERPOLATIONS[d.work[2]]], np.int32)
+        if d.hop is not None:
+            out["hop_%d" % i] = np.int32(d.hop)
         if a.masks:
             m = d.masks.cpu().numpy()
             out.update({"masks_%d" % i: np.packbits(m), "mask_shape_%d" % i: np.array(m.shape, np.int64)})
