@@ -30,7 +30,7 @@ import _bootstrap  # noqa: E402,F401
 import numpy as np  # noqa: E402
 import torch  # noqa: E402
 
-from picons_amd import evalmetrics, synthetic  # noqa: E402
+from picons_amd import evalmetrics, synthetic, trainstate  # noqa: E402
 
 
 def _videos(n_classes, hw=224):
@@ -96,7 +96,7 @@ def iou(split, argv=None, hw=224, on_engine=None):
     for saved_wts in files:
         model_names.append(saved_wts)
         if use_engine:
-            engine.load_state(torch.load(saved_wts, map_location="cpu"))
+            engine.load_state(trainstate.model_state_of(torch.load(saved_wts, map_location="cpu")))
             print('loaded weights from previous run: ', saved_wts)
             r = engine.evaluate(_videos_u8(n_classes, jhmdb, hw), pack=pack)
         else:

@@ -15,6 +15,13 @@ New behaviour is switched by environment variables only, so the CLI is unchanged
   PICONS_FUSED=0         use the nn.Module + autograd path (model called twice, torch.optim.Adam) instead of
                          the fused step engine (default 1: picons_amd.step.StepEngine, both passes batched)
   PICONS_HW=<px>         frame size (default 224, the only size the reference accepts)
+  PICONS_TRAIN_STATE=<path>   after every epoch (behind the scheduler step) rank 0 writes the whole training state to <path>
+                         (picons_amd.trainstate: model, Adam moments per tensor as torch.optim.Adam.state_dict() has them, scheduler, epoch, best
+                         losses and checkpoint paths, the host RNG states of every rank, the arguments), atomically.  Unset: no such file
+  PICONS_RESUME=<path>   continue the run that wrote <path> at its next epoch, in its checkpoint directory, bit for bit as if it had
+                         not stopped (same --bs / data / world; either PICONS_FUSED path continues the other's file).  Epoch boundaries
+                         only: the position inside an epoch and DataLoader worker state are not saved
+  PICONS_EPOCHS_THIS_RUN=<n>  stop cleanly after n epochs of this invocation (for time-limited job slots; --epochs stays the run's length)
   RANK / WORLD_SIZE / LOCAL_RANK / MASTER_*   data parallel over the GPUs of one node (torchrun)
 """
 import argparse
@@ -36,7 +43,7 @@ from utils.losses import SpreadLoss, DiceLoss, weighted_mse_loss  # noqa: E402
 from utils.metrics import get_accuracy, IOU2  # noqa: E402
 from utils.helpers import measure_pixelwise_var_v2, measure_pixelwise_gradient  # noqa: E402
 from utils import ramp_ups  # noqa: E402
-from picons_amd import dist as pdist, step as pstep, synthetic, valstep as pval  # noqa: E402
+from picons_amd import dist as pdist, step as pstep, synthetic, trainstate, valstep as pval  # noqa: E402
 
 NUM_CLASSES = 24
 DATASET = "ucf101"
@@ -310,6 +317,63 @@ def parse_args(argv=None):
     ]).parse_args(argv)
 
 
+def _host(x):
+    """A state_dict-like structure with every tensor on the host."""
+    if torch.is_tensor(x):
+        return x.detach().cpu()
+    if isinstance(x, dict):
+        return {k: _host(v) for k, v in x.items()}
+    if isinstance(x, (list, tuple)):
+        return type(x)(_host(v) for v in x)
+    return x
+
+
+def _abs(path):
+    """Paths go into a training state absolute: the run that resumes it may start in another working directory."""
+    return None if path is None else os.path.abspath(path)
+
+
+def _run_meta(world, hw, fused):
+    return dict(num_classes=NUM_CLASSES, hw=hw, dataset=DATASET, world=world, fused=fused)
+
+
+def write_train_state(path, args, meta, rank, epoch, model, optimizer, scheduler, engine, best):
+    """PICONS_TRAIN_STATE: called by every rank behind an epoch's scheduler step (the RNG states of all ranks are gathered); rank 0 writes."""
+    mine = (torch.get_rng_state(), torch.cuda.get_rng_state())
+    gathered = [mine]
+    if meta["world"] > 1:
+        gathered = [None] * meta["world"]
+        torch.distributed.all_gather_object(gathered, mine)
+    if rank != 0:
+        return
+    if engine is not None:
+        ts = engine.train_state()
+        model_state, opt_state = ts["model"], ts["optimizer"]
+        opt_state["param_groups"] = _host(optimizer.state_dict()["param_groups"])       # the learning rate lives in the torch optimiser
+    else:
+        model_state, opt_state = _host(model.state_dict()), _host(optimizer.state_dict())
+    trainstate.save(path, {"format": trainstate.FORMAT, "version": trainstate.VERSION, "model": model_state, "optimizer": opt_state,
+                           "scheduler": _host(scheduler.state_dict()), "epoch": epoch, "best": dict(best),
+                           "rng": trainstate.rng_state([g[0] for g in gathered], [g[1] for g in gathered]),
+                           "args": dict(vars(args)), "meta": dict(meta)})
+
+
+def restore_train_state(state, model, optimizer, scheduler, engine, reducer):
+    """PICONS_RESUME, on every rank: model, optimiser (fused: the engine's moments and step count, and the torch optimiser's param_groups
+    alone), scheduler.  The RNG states are put back by the caller, last, behind everything that draws while the run is set up."""
+    model.load_state_dict(state["model"])
+    if engine is not None:
+        engine.load_train_state(state)
+        sd = optimizer.state_dict()
+        sd["param_groups"] = [dict(g, params=mine["params"]) for g, mine in zip(state["optimizer"]["param_groups"], sd["param_groups"])]
+        optimizer.load_state_dict(sd)
+        if reducer is not None:
+            pdist.check_replicas_agree(engine.P)
+    else:
+        optimizer.load_state_dict(state["optimizer"])
+    scheduler.load_state_dict(state["scheduler"])
+
+
 def run(args):
     global model, criterion_cls, criterion_seg_1, criterion_seg_2
     if args.loc_loss != 'dice':
@@ -327,6 +391,18 @@ def run(args):
     mode = os.environ.get("PICONS_SYNTHETIC", "1")          # read only: the process environment is not written to
     if mode not in ("0", "1", "u8"):
         raise RuntimeError("PICONS_SYNTHETIC=%r: expected 0 (the caller's datasets), 1 or u8" % mode)
+    state_path, resume_path = os.environ.get("PICONS_TRAIN_STATE"), os.environ.get("PICONS_RESUME")
+    epochs_this_run = int(os.environ.get("PICONS_EPOCHS_THIS_RUN", "0"))
+    meta = _run_meta(world, hw, fused)
+    resumed = None
+    if resume_path:
+        resumed = trainstate.load(resume_path)
+        diffs = trainstate.check_compatible(resumed, meta, args)
+        if diffs and rank == 0:
+            print(trainstate.arg_warning(diffs), file=sys.stderr)
+        if resumed["epoch"] >= args.epochs:
+            print("PICONS_RESUME=%s: epoch %d of --epochs %d is finished, nothing left to train" % (resume_path, resumed["epoch"], args.epochs))
+            return None
     if args.bs < 2:
         raise RuntimeError("--bs %d: each train loader takes bs // 2 clips per batch, so bs must be at least 2" % args.bs)
     if mode == "0":
@@ -364,10 +440,20 @@ def run(args):
         val_engine = engine.val_engine(args.bs)           # validates the step engine's own weights (validation batches hold args.bs clips)
     save_path = os.path.join('train_log_wts', args.exp_id)
     model_save_dir = os.path.join(save_path, time.strftime('%m-%d-%H-%M'))
-    os.makedirs(model_save_dir, exist_ok=True)
     prev_best_val_loss = prev_best_train_loss = 10000
     prev_val_path = prev_train_path = None
-    for e in range(1, args.epochs + 1):
+    first_epoch = 1
+    if resumed is not None:
+        restore_train_state(resumed, model, optimizer, scheduler, engine, reducer)
+        b = resumed["best"]
+        prev_best_val_loss, prev_best_train_loss, prev_val_path, prev_train_path = b["val_loss"], b["train_loss"], b["val_path"], b["train_path"]
+        model_save_dir = b["save_dir"]                 # the run goes on where it started: delete-previous-best keeps working
+        first_epoch = resumed["epoch"] + 1
+        print("resumed %s: epoch %d finished, lr %g, continuing in %s" % (resume_path, resumed["epoch"], optimizer.param_groups[0]['lr'], model_save_dir))
+    os.makedirs(model_save_dir, exist_ok=True)
+    if resumed is not None:
+        trainstate.set_rng_state(resumed["rng"], rank)
+    for e in range(first_epoch, args.epochs + 1):
         train_loss = train(args, model, labeled_loader, unlabeled_loader, optimizer, e, save_path, None, ramp_wt, engine, reducer)
         if engine is not None:
             model.load_state_dict(engine.state_dict())           # the checkpoints below are written from `model`
@@ -393,6 +479,13 @@ def run(args):
                 os.remove(prev_train_path)
             prev_train_path = p
         scheduler.step(train_loss)
+        if state_path:
+            write_train_state(state_path, args, meta, rank, e, model, optimizer, scheduler, engine,
+                              dict(val_loss=prev_best_val_loss, train_loss=prev_best_train_loss, val_path=_abs(prev_val_path),
+                                   train_path=_abs(prev_train_path), save_dir=_abs(model_save_dir)))
+        if epochs_this_run > 0 and e - first_epoch + 1 >= epochs_this_run and e < args.epochs:
+            print("PICONS_EPOCHS_THIS_RUN=%d: stopping after epoch %d of %d" % (epochs_this_run, e, args.epochs))
+            break
     return train_loss
 
 

@@ -16,7 +16,7 @@ import numpy as np
 import torch
 import torch.nn as nn
 
-from . import capi, ops, spec, synthetic
+from . import capi, ops, spec, synthetic, trainstate
 from .plan import Plan
 
 
@@ -132,7 +132,7 @@ class CapsNet(nn.Module):
             print("WARNING: pretrained trunk %r not found; PICONS_SYNTHETIC is set, the I3D trunk keeps its random initialisation" % pt_path,
                   file=sys.stderr)
         if pt_path and os.path.exists(pt_path):
-            pre = torch.load(pt_path, map_location="cpu")
+            pre = trainstate.model_state_of(torch.load(pt_path, map_location="cpu"))
             sd = {"conv1." + k: v for k, v in pre.items() if "conv1." + k in self._keyset()}
             self.load_state_dict(sd, strict=False)
             print("Loaded I3D pretrained weights from ", pt_path, " for layers: ", len(sd))
@@ -186,7 +186,8 @@ class CapsNet(nn.Module):
                     raise KeyError("unexpected key " + k)
 
     def load_previous_weights(self, weightfile):
-        self.load_state_dict(torch.load(weightfile, map_location="cpu"), strict=False)
+        # a training-state file (trainstate.py) gives its model part; any other dict that is no state_dict raises instead of loading nothing
+        self.load_state_dict(trainstate.model_state_of(torch.load(weightfile, map_location="cpu")), strict=False)
         print('loaded weights from previous run: ', weightfile)
 
     def zero_grad(self, set_to_none=True):

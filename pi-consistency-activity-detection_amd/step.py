@@ -13,7 +13,7 @@ from types import SimpleNamespace
 import numpy as np
 import torch
 
-from . import capi, ops, spec, switches as sw, synthetic
+from . import capi, ops, spec, switches as sw, synthetic, trainstate
 from .plan import Plan
 
 
@@ -231,6 +231,56 @@ class StepEngine:
             else:
                 sd[k] = torch.tensor(self.nbt.get(k, 0), dtype=torch.long)
         return sd
+
+    # ------------------------------------------------------------------ training state (trainstate.py)
+    def param_names(self):
+        """The parameter tensors in the order nn.Module.named_parameters() gives them (the index of torch.optim.Adam's state)."""
+        return [k for k in spec.state_dict_keys(self.C) if k in self.plan.pshape]
+
+    def train_state(self):
+        """What a later engine needs to go on exactly where this one stands, on the host: {"model": the state_dict, "optimizer": the Adam
+        moments per tensor in torch.optim.Adam.state_dict()'s structure, "step_count"}.  The one param_group carries args.lr and the fused
+        op's betas / eps; a trainer whose learning rate lives in a torch optimiser overwrites it with that optimiser's own."""
+        self.synchronize()
+        _lr, b1, b2, eps = self.plan.lists["adam"][self.plan.op_adam][2][:4]
+        group = trainstate.adam_param_group(self.args.lr, betas=(b1, b2), eps=eps, weight_decay=0)
+        return {"model": {k: v.cpu() for k, v in self.state_dict().items()},
+                "optimizer": trainstate.adam_state_from_flat(self.M, self.V, self.step_count, self.plan.poff, self.plan.pshape, self.param_names(), [group]),
+                "step_count": self.step_count}
+
+    def _check_model_state(self, state):
+        """ValueError for a state_dict load_state could not take as it is: a missing key or a tensor of another shape."""
+        shape_of = lambda v: tuple(v.shape) if hasattr(v, "shape") else np.shape(v)
+        for k, shp in self.plan.pshape.items():
+            if k not in state:
+                raise ValueError("model state lacks %s" % k)
+            if shape_of(state[k]) != tuple(shp):
+                raise ValueError("model state: %s has shape %s, this engine's %s" % (k, shape_of(state[k]), tuple(shp)))
+        for k in self.plan.roff:
+            n = self.plan.pshape[k.rsplit(".bn.", 1)[0] + ".bn.weight"][0]
+            if k not in state:
+                raise ValueError("model state lacks %s" % k)
+            if shape_of(state[k]) != (n,):
+                raise ValueError("model state: %s has shape %s, this engine's %s" % (k, shape_of(state[k]), (n,)))
+
+    def load_train_state(self, state):
+        """Take over a train_state() dict or a full training state (trainstate.load): weights, running statistics, num_batches_tracked, Adam
+        moments and the step count, after which the next train_step is the one the engine that wrote the state would have run.  Everything
+        is checked before anything is written: a refused call (ValueError) leaves the engine as it was.  Like load_state this only fills the
+        master buffers -- the weight layouts derived from them are made anew by every step's (and every validation / detection pass's) own
+        prep lists, and the Adam ops take their count from step_count when the step arms them."""
+        if not isinstance(state, dict) or "model" not in state or "optimizer" not in state:
+            raise ValueError("load_train_state: a dict with 'model' and 'optimizer' expected (StepEngine.train_state or trainstate.load)")
+        model = trainstate.model_state_of(state) if "format" in state else state["model"]
+        self._check_model_state(model)
+        count, _ = trainstate.adam_state_check(state["optimizer"], self.M, self.V, self.plan.poff, self.plan.pshape, self.param_names())
+        if "step_count" in state and int(state["step_count"]) != count:
+            raise ValueError("train state: step_count %r, but the optimizer state is at step %d" % (state["step_count"], count))
+        self.synchronize()                 # a step in flight still reads and writes what this overwrites
+        trainstate.adam_state_to_flat(state["optimizer"], self.M, self.V, self.plan.poff, self.plan.pshape, self.param_names())
+        self.load_state(model)
+        self.step_count = count
+        self.synchronize()
 
     # ------------------------------------------------------------------ staging
     def stage(self, label_mb, unlabel_mb, perm, drops):

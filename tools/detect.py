@@ -50,7 +50,7 @@ import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import picons_amd  # noqa: F401,E402
-from picons_amd import detect, synthetic  # noqa: E402
+from picons_amd import detect, synthetic, trainstate  # noqa: E402
 
 
 def main():
@@ -99,7 +99,11 @@ def main():
         raise SystemExit("tools/detect.py needs a GPU: the hot path is HIP-only (no CPU fallback)")
     if a.ckpt:
         state = torch.load(a.ckpt, map_location="cpu")
-        state = state.get("state_dict", state) if isinstance(state, dict) else state
+        state = state.get("state_dict", state) if isinstance(state, dict) and "format" not in state else state
+        try:
+            state = trainstate.model_state_of(state)        # a bare state_dict, or the model part of a training-state file
+        except ValueError as e:
+            raise SystemExit("tools/detect.py: --ckpt %s: %s" % (a.ckpt, e))
         state = {(k[7:] if k.startswith("module.") else k): v for k, v in state.items()}
     else:
         state = synthetic.init_state(47, a.classes)
