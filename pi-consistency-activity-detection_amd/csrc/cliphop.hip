@@ -1,23 +1,20 @@
 // Overlapping clips in time, merged per frame on the device (detect.DetectEngine.set_clip_hop; the window rule: cliphop.h).
 //   pc_clip_hop_starts                 host arithmetic: the clip starts of a video of F frames at a hop
 //   pc_clip_planes_bytes               host arithmetic: a video's slot planes and its cover bytes
-//   pc_clip_planes                     one launch behind each forward: what merge_plane_kernel of detectscale.hip writes per (clip, frame)
-//     clip_planes_kernel     -- merge_group4's merged logit, 0.0f where no view covers, 16 bytes at a time, each logit fetched once -- goes to
-//                            slot (start / hop) % M of the video's planes [M][F][pstride]; the cover bytes [pstride], the same for every
-//                            clip of the video, are written by the blocks of the launch's first frame when the caller asks for them
+//   pc_clip_planes                     one launch behind each forward:
+//     clip_planes_kernel     detectrec.h: merge_to_plane -- merge_group4's merged logit, 0.0f where no view covers, 16 bytes at a time, each
+//                            logit fetched once -- into slot (start / hop) % M of the video's planes [M][F][pstride]; the cover bytes
+//                            [pstride], the same for every clip of the video, are written by the blocks of the launch's first frame when
+//                            the caller asks for them
 //   pc_detect_frames_planes_ws_bytes   host arithmetic: the partials of one frame range
 //   pc_detect_frames_planes            two launches per frame range, behind a video's last clip:
-//     planes_resample_kernel resample_kernel of detectscale.hip with one change: the value of a plane tap is the mean over the windows that
-//                            hold the frame, in ascending window order, by merge_group4's rule (the first value as it is, the others added
-//                            with __fadd_rn, one __fdiv_rn by the count when more than one window holds it).  A slot no window filled is never read.
-//     planes_records_kernel  detect_records_kernel of detectrec.h with the frame taken from the range instead of a clip table and word 6 the
+//     planes_resample_kernel detectrec.h: detect_native_frame, where the value of a plane tap is the mean over the windows that hold the
+//                            frame, in ascending window order, by merge_group4's rule (the first value as it is, the others added with
+//                            __fadd_rn, one __fdiv_rn by the count when more than one window holds it).  A slot no window filled is never read.
+//     planes_records_kernel  detectrec.h: record_from_partials, with the frame taken from the range instead of a clip table and word 6 the
 //                            score row of the first clip that holds the frame
 // Two clips of one launch never address the same (slot, frame): no atomics, no read-modify-write, nothing to zero, and the order in which a
 // video's launches arrive does not matter.
-#include "common.h"
-#include "evalpred.h"
-#include "clipgeom.h"
-#include "viewmerge.h"
 #include "detectrec.h"
 #include "cliphop.h"
 
@@ -41,148 +38,47 @@ struct FramesK {
     int F, H, W, Hs, Ws, V, f_skip, hop, M, f0, nf, row0, bpf;
 };
 
-inline size_t plane_stride(int Hs, int Ws) { return ((size_t)Hs * Ws + 3) & ~(size_t)3; }
-
-inline bool frame_sizes_ok(int Hs, int Ws, int H, int W) {
-    return Hs >= 1 && Ws >= 1 && H >= 1 && W >= 1 && (int64_t)Hs * Ws < (1ll << 31) && (int64_t)H * W < (1ll << 31) &&
-           2 * (int64_t)(H > W ? H : W) < (1ll << 24);
-}
-
-// grid (bpf_s, n * 8): merge_plane_kernel's traversal.  The padding of a plane's last group takes merge_group4's values for pixels that
-// do not exist (0.0f, cover 0); nothing reads it.
+// grid (bpf_s, n * 8): the frame of slot blockIdx.y into the plane of its window, the cover bytes with the launch's first frame (the entry
+// refuses a cover when that frame does not exist)
 __global__ __launch_bounds__(256) void clip_planes_kernel(const PlanesK p) {
-    const ClipGeom& g = p.g;
-    const int c = blockIdx.y >> 3, k = blockIdx.y & 7;
-    const int64_t f = (int64_t)g.starts[c] + (int64_t)k * g.f_skip;
-    if (f >= g.F) return;                                            // a frame past the end: nothing read, nothing written
-    const uint32_t HW = (uint32_t)g.H * (uint32_t)g.W, total4 = (HW + 3u) >> 2;
-    const size_t per = (size_t)g.S * g.S;
-    const float* lp = p.logits + ((size_t)c * 8 + k) * per;          // view v: + v * view_stride * 8 * per
-    const size_t vstep = (size_t)g.view_stride * 8 * per;
-    const int slot = (g.starts[c] / p.hop) % p.M;
-    float* pl = p.plane + ((size_t)slot * g.F + (size_t)f) * p.pstride;
-    uint8_t* cv = blockIdx.y == 0 ? p.cover : nullptr;               // the launch's first frame (the entry refuses a cover when it does not exist)
-    for (uint32_t idx = blockIdx.x * BT + threadIdx.x; idx < total4; idx += (uint32_t)p.bpf_s * BT) {
-        const uint32_t px = idx << 2;
-        float mg[4];
-        int num[4], gy, gx;
-        merge_group4(g, lp, vstep, px, HW, gy, gx, mg, num);
-        f32x4 q;
-        q[0] = mg[0]; q[1] = mg[1]; q[2] = mg[2]; q[3] = mg[3];
-        *(f32x4*)(pl + px) = q;
-        if (cv) *(uint32_t*)(cv + px) = (uint32_t)num[0] | ((uint32_t)num[1] << 8) | ((uint32_t)num[2] << 16) | ((uint32_t)num[3] << 24);
+    const int64_t f = slot_frame(p.g, blockIdx.y);
+    if (f < 0) return;
+    const int slot = (p.g.starts[blockIdx.y >> 3] / p.hop) % p.M;
+    merge_to_plane(p.g, p.logits, blockIdx.y, p.bpf_s, p.plane + ((size_t)slot * p.g.F + (size_t)f) * p.pstride, blockIdx.y == 0 ? p.cover : nullptr);
+}
+
+// A tap of one working pixel: the mean over the cnt windows that hold the frame, slot planes s0, s0 + 1, ... (mod M) in ascending window
+// order, by merge_group4's rule.
+struct MeanTap {
+    const float* pf;             // the frame in slot 0
+    size_t sstride;              // from one slot to the next
+    int s0, cnt, M;
+    __device__ __forceinline__ float at(size_t idx) const {
+        float acc = pf[(size_t)s0 * sstride + idx];
+        int s = s0;
+        for (int i = 1; i < cnt; ++i) {
+            s = s + 1 == M ? 0 : s + 1;
+            acc = __fadd_rn(acc, pf[(size_t)s * sstride + idx]);
+        }
+        return cnt > 1 ? __fdiv_rn(acc, (float)cnt) : acc;
     }
-}
+};
 
-// The mean of one working pixel over the cnt windows that hold the frame: slot planes s0, s0 + 1, ... (mod M), ascending window order.
-__device__ __forceinline__ float tap_mean(const float* pf, size_t sstride, int s0, int cnt, int M, size_t at) {
-    float acc = pf[(size_t)s0 * sstride + at];
-    int s = s0;
-    for (int i = 1; i < cnt; ++i) {
-        s = s + 1 == M ? 0 : s + 1;
-        acc = __fadd_rn(acc, pf[(size_t)s * sstride + at]);
-    }
-    return cnt > 1 ? __fdiv_rn(acc, (float)cnt) : acc;
-}
-
-// One tap row of the bilinear rule, as tap_row of detectscale.hip: a tap of zero weight is not read, `ok` is cleared when a tap that is
-// read has no cover.
-__device__ __forceinline__ float tap_row_mean(const float* pf, size_t sstride, int s0, int cnt, int M, const uint8_t* cv, size_t r, int ix, int ix1,
-                                              float wx0, float wx1, bool& ok) {
-    const float a = tap_mean(pf, sstride, s0, cnt, M, r + ix);
-    ok = ok && cv[r + ix] != 0;
-    if (wx1 == 0.0f) return a;
-    const float b = tap_mean(pf, sstride, s0, cnt, M, r + ix1);
-    ok = ok && cv[r + ix1] != 0;
-    return __fadd_rn(__fmul_rn(a, wx0), __fmul_rn(b, wx1));
-}
-
-// grid (bpf, nf), bpf = det_views_bpf(H * W): resample_kernel's traversal of the native frame f0 + blockIdx.y.  The table's indices are
-// clamped into the plane: a table that is not pc_resample_tables' for these sizes gives wrong values, never an access outside the planes.
+// grid (bpf, nf), bpf = det_views_bpf(H * W): the native frame f0 + blockIdx.y from the windows that hold it
 __global__ __launch_bounds__(256) void planes_resample_kernel(const FramesK p) {
     const int64_t f = (int64_t)p.f0 + blockIdx.y;
-    const int W = p.W, Hs = p.Hs, Ws = p.Ws;
-    const uint32_t HW = (uint32_t)p.H * (uint32_t)W, total4 = (HW + 3u) >> 2;
     const int64_t lo = hop_lo(f, p.f_skip, p.hop), hi = hop_hi(p.F, f, p.f_skip, p.hop);
-    const int cnt = (int)(hi - lo + 1), s0 = (int)(lo % p.M);
-    const size_t sstride = (size_t)p.F * p.pstride;                  // from one slot to the next
-    const float* pf = p.plane + (size_t)f * p.pstride;               // the frame in slot 0
-    const uint8_t* cv = p.cover;
-    const int32_t* rowt = p.tab;
-    const int32_t* colt = p.tab + 2 * (size_t)p.H;
-    uint8_t* mf = p.mask ? p.mask + (size_t)f * HW : nullptr;
-    uint16_t* qf = p.prob ? p.prob + (size_t)f * HW : nullptr;
-    double sum = 0.0;
-    int n = 0, x0 = 0x7fffffff, y0 = 0x7fffffff, x1 = -1, y1 = -1;
-    for (uint32_t idx = blockIdx.x * BT + threadIdx.x; idx < total4; idx += (uint32_t)p.bpf * BT) {
-        const uint32_t px = idx << 2;
-        const int ny = (int)(HW - px < 4u ? HW - px : 4u);
-        const int gy = (int)(px / (uint32_t)W), gx = (int)(px - (uint32_t)gy * (uint32_t)W);
-        uint32_t bits = 0, q[4] = {0u, 0u, 0u, 0u};
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-            if (e >= ny) continue;
-            int y = gy, x = gx + e;
-            if (x >= W) { x -= W; ++y; if (x >= W) { x -= W; ++y; if (x >= W) { x -= W; ++y; } } }     // W >= 1: at most three rows on
-            const int iy = min(max(rowt[2 * y], 0), Hs - 1), iy1 = min(iy + 1, Hs - 1);
-            const int ix = min(max(colt[2 * x], 0), Ws - 1), ix1 = min(ix + 1, Ws - 1);
-            const float wy1 = __int_as_float(rowt[2 * y + 1]), wx1 = __int_as_float(colt[2 * x + 1]);
-            const float wy0 = __fsub_rn(1.0f, wy1), wx0 = __fsub_rn(1.0f, wx1);
-            bool ok = true;
-            float v = tap_row_mean(pf, sstride, s0, cnt, p.M, cv, (size_t)iy * Ws, ix, ix1, wx0, wx1, ok);
-            if (wy1 != 0.0f) {
-                const float bot = tap_row_mean(pf, sstride, s0, cnt, p.M, cv, (size_t)iy1 * Ws, ix, ix1, wx0, wx1, ok);
-                v = __fadd_rn(__fmul_rn(v, wy0), __fmul_rn(bot, wy1));
-            }
-            if (!ok) continue;                                       // a tap that was read has no cover: background, probability 0
-            const float sg = 1.0f / (1.0f + expf(-v));
-            if (v == v) q[e] = __float2uint_rn(sg * (float)PC_PROB_ONE);
-            if (seg_positive(v)) {
-                bits |= 1u << (8 * e);
-                sum += (double)sg;
-                ++n;
-                x0 = min(x0, x); x1 = max(x1, x); y0 = min(y0, y); y1 = max(y1, y);
-            }
-        }
-        if (mf) {
-            uint8_t* m = mf + px;
-            if (ny == 4 && ((uintptr_t)m & 3) == 0) {
-                *(uint32_t*)m = bits;
-            } else {
-                for (int e = 0; e < ny; ++e) m[e] = (uint8_t)((bits >> (8 * e)) & 1);
-            }
-        }
-        if (qf) {
-            uint16_t* o = qf + px;
-            if (ny == 4 && ((uintptr_t)o & 7) == 0) {
-                *(uint2*)o = make_uint2(q[0] | (q[1] << 16), q[2] | (q[3] << 16));
-            } else {
-                for (int e = 0; e < ny; ++e) o[e] = (uint16_t)q[e];
-            }
-        }
-    }
-    block_partial(sum, n, x0, y0, x1, y1, p.part + (size_t)blockIdx.y * p.bpf + blockIdx.x);
+    const MeanTap tap{p.plane + (size_t)f * p.pstride, (size_t)p.F * p.pstride, (int)(lo % p.M), (int)(hi - lo + 1), p.M};
+    detect_native_frame(tap, p.cover, p.tab, f, p.H, p.W, p.Hs, p.Ws, p.mask, p.prob, p.bpf, p.part + (size_t)blockIdx.y * p.bpf + blockIdx.x);
 }
 
-// one thread per frame of the range: the frame's block partials in block order, one division in double, one rounding to float
+// one thread per frame of the range; word 6: the score row of the first clip that holds the frame
 __global__ __launch_bounds__(256) void planes_records_kernel(const FramesK p) {
     const int t = blockIdx.x * BT + threadIdx.x;
     if (t >= p.nf) return;
     const int64_t f = (int64_t)p.f0 + t;
-    const Partial* q = p.part + (size_t)t * p.bpf;
-    double sum = 0.0;
-    int cnt = 0, x0 = 0x7fffffff, y0 = 0x7fffffff, x1 = -1, y1 = -1;
-    for (int b = 0; b < p.bpf; ++b) {
-        sum += q[b].sum; cnt += q[b].count;
-        x0 = min(x0, q[b].x0); y0 = min(y0, q[b].y0); x1 = max(x1, q[b].x1); y1 = max(y1, q[b].y1);
-    }
-    int32_t* r = p.rec + (size_t)f * REC_WORDS;
-    const bool any = cnt > 0;
-    r[0] = cnt;
-    r[1] = any ? x0 : 0; r[2] = any ? y0 : 0; r[3] = any ? x1 + 1 : 0; r[4] = any ? y1 + 1 : 0;
-    r[5] = __float_as_int(any ? (float)(sum / (double)cnt) : 0.0f);
-    r[6] = p.row0 + p.V * (int)(hop_lo(f, p.f_skip, p.hop) * p.f_skip + f % p.f_skip);      // the first clip that holds the frame
-    r[7] = 0;
+    record_from_partials(p.part + (size_t)t * p.bpf, p.bpf, 0, 0, p.row0 + p.V * (int)(hop_lo(f, p.f_skip, p.hop) * p.f_skip + f % p.f_skip),
+                         p.rec + (size_t)f * REC_WORDS);
 }
 
 }  // namespace

@@ -9,15 +9,12 @@
 //   pc_frame_probs     the per-pixel probability of the merged logit as uint16 in video order, for pc_instance_scores (end of this file);
 //                      its merge is the views kernel's own (viewmerge.h: merge_group4's), no records, no workspace
 // Two traversal kernels (detect_frames_kernel walks the crop's float4 and then the margin, detect_frames_views_kernel the full frame in
-// groups of four: another memory traffic and another order of the sums), one end (block_partial), one records kernel, one set of argument
-// checks (detect_args) on the geometry of clipgeom.h -- those three in detectrec.h, which detectscale.hip shares.
+// groups of four: another memory traffic and another order of the sums), one accumulator and end (FrameAcc), one mask and one probability
+// store, one probability conversion, one records kernel, one set of argument checks (detect_args) on the geometry of clipgeom.h -- all in
+// detectrec.h, which detectscale.hip and cliphop.hip share.
 // The mask predicate is the evaluator's own (evalpred.h: seg_positive, shared with pc_seg_frame_counts).  No floating-point atomics and no
 // integer ones either: every block leaves one partial in a caller-owned workspace, a second small launch adds them in block order (the
 // pattern of valmetrics.hip), so a record is bit-identical from run to run and nothing has to be zeroed in front of the launch.
-#include "common.h"
-#include "evalpred.h"
-#include "clipgeom.h"
-#include "viewmerge.h"
 #include "detectrec.h"
 
 namespace {
@@ -33,14 +30,12 @@ inline int det_bpf(int S) {
 // address allows (a mask row starts at any byte address when W is odd), as four bytes otherwise.
 __global__ __launch_bounds__(256) void detect_frames_kernel(const DetectK p) {
     const ClipGeom& g = p.g;
-    const int c = blockIdx.y >> 3, k = blockIdx.y & 7;
-    const int64_t f = (int64_t)g.starts[c] + (int64_t)k * g.f_skip;
-    if (f >= g.F) return;                                            // a frame past the end: nothing read, nothing written
+    const int64_t f = slot_frame(g, blockIdx.y);
+    if (f < 0) return;
     const int S = g.S, S4 = S >> 2, total4 = S * S4, H = g.H, W = g.W, h0 = g.vh0[0], w0 = g.vw0[0];
     const f32x4* lp = (const f32x4*)p.logits + (size_t)blockIdx.y * total4;
     uint8_t* mf = p.mask ? p.mask + (size_t)f * H * W : nullptr;
-    double sum = 0.0;
-    int cnt = 0, x0 = 0x7fffffff, y0 = 0x7fffffff, x1 = -1, y1 = -1;
+    FrameAcc acc;
     for (int idx = blockIdx.x * BT + threadIdx.x; idx < total4; idx += p.bpf * BT) {
         const int y = idx / S4, x = (idx - y * S4) << 2;
         const f32x4 v = lp[idx];
@@ -49,20 +44,10 @@ __global__ __launch_bounds__(256) void detect_frames_kernel(const DetectK p) {
         for (int e = 0; e < 4; ++e) {
             if (seg_positive(v[e])) {
                 bits |= 1u << (8 * e);
-                sum += (double)(1.0f / (1.0f + expf(-v[e])));
-                ++cnt;
-                x0 = min(x0, x + e); x1 = max(x1, x + e);
+                acc.add(sigmoid(v[e]), y, x + e);
             }
         }
-        if (bits) { y0 = min(y0, y); y1 = max(y1, y); }
-        if (mf) {
-            uint8_t* m = mf + (size_t)(h0 + y) * W + w0 + x;
-            if (((uintptr_t)m & 3) == 0) {
-                *(uint32_t*)m = bits;
-            } else {
-                m[0] = (uint8_t)(bits & 1); m[1] = (uint8_t)((bits >> 8) & 1); m[2] = (uint8_t)((bits >> 16) & 1); m[3] = (uint8_t)(bits >> 24);
-            }
-        }
+        if (mf) store_mask4(mf + (size_t)(h0 + y) * W + w0 + x, bits, 4);
     }
     if (mf) {
         // the margin as S + 1 runs of bytes: the rows above the crop and the first row's left margin, the W - S bytes between the crop rows,
@@ -78,7 +63,7 @@ __global__ __launch_bounds__(256) void detect_frames_kernel(const DetectK p) {
             mf[a] = 0;
         }
     }
-    block_partial(sum, cnt, x0, y0, x1, y1, p.part + (size_t)blockIdx.y * p.bpf + blockIdx.x);
+    acc.block_partial(p.part + (size_t)blockIdx.y * p.bpf + blockIdx.x);
 }
 
 __global__ __launch_bounds__(256) void video_class_kernel(const float* __restrict__ scores, int n, int C, float* __restrict__ out) {
@@ -135,17 +120,14 @@ namespace {
 // or none; the four mask bytes go out as one dword where their address allows, as bytes otherwise.
 __global__ __launch_bounds__(256) void detect_frames_views_kernel(const DetectK p) {
     const ClipGeom& g = p.g;
-    const int c = blockIdx.y >> 3, k = blockIdx.y & 7;
-    const int64_t f = (int64_t)g.starts[c] + (int64_t)k * g.f_skip;
-    if (f >= g.F) return;                                            // a frame past the end: nothing read, nothing written
-    const int W = g.W;
-    const uint32_t HW = (uint32_t)g.H * (uint32_t)W, total4 = (HW + 3u) >> 2;
+    const int64_t f = slot_frame(g, blockIdx.y);
+    if (f < 0) return;
+    const uint32_t HW = (uint32_t)g.H * (uint32_t)g.W, total4 = (HW + 3u) >> 2;
     const size_t per = (size_t)g.S * g.S;
-    const float* lp = p.logits + ((size_t)c * 8 + k) * per;          // view v: + v * view_stride * 8 * per
+    const float* lp = p.logits + (size_t)blockIdx.y * per;           // view v: + v * view_stride * 8 * per
     const size_t vstep = (size_t)g.view_stride * 8 * per;
     uint8_t* mf = p.mask ? p.mask + (size_t)f * HW : nullptr;
-    double sum = 0.0;
-    int cnt = 0, x0 = 0x7fffffff, y0 = 0x7fffffff, x1 = -1, y1 = -1;
+    FrameAcc acc;
     for (uint32_t idx = blockIdx.x * BT + threadIdx.x; idx < total4; idx += (uint32_t)p.bpf * BT) {
         const uint32_t px = idx << 2;
         float mg[4];
@@ -154,27 +136,15 @@ __global__ __launch_bounds__(256) void detect_frames_views_kernel(const DetectK 
         uint32_t bits = 0;
 #pragma unroll
         for (int e = 0; e < 4; ++e) {
-            if (num[e] == 0) continue;                               // no view covers the pixel: background
-            const float m = mg[e];
-            if (seg_positive(m)) {
-                int y = gy, x = gx + e;
-                if (x >= W) { x -= W; ++y; if (x >= W) { x -= W; ++y; if (x >= W) { x -= W; ++y; } } }
-                bits |= 1u << (8 * e);
-                sum += (double)(1.0f / (1.0f + expf(-m)));
-                ++cnt;
-                x0 = min(x0, x); x1 = max(x1, x); y0 = min(y0, y); y1 = max(y1, y);
-            }
+            if (num[e] == 0 || !seg_positive(mg[e])) continue;       // no view covers the pixel, or its merged logit fails the predicate: background
+            int y, x;
+            group_pixel(gy, gx, e, g.W, y, x);
+            bits |= 1u << (8 * e);
+            acc.add(sigmoid(mg[e]), y, x);
         }
-        if (mf) {
-            uint8_t* m = mf + px;
-            if (ny == 4 && ((uintptr_t)m & 3) == 0) {
-                *(uint32_t*)m = bits;
-            } else {
-                for (int e = 0; e < ny; ++e) m[e] = (uint8_t)((bits >> (8 * e)) & 1);
-            }
-        }
+        if (mf) store_mask4(mf + px, bits, ny);
     }
-    block_partial(sum, cnt, x0, y0, x1, y1, p.part + (size_t)blockIdx.y * p.bpf + blockIdx.x);
+    acc.block_partial(p.part + (size_t)blockIdx.y * p.bpf + blockIdx.x);
 }
 
 inline bool det_views_shape_ok(int n, int H, int W) { return n >= 1 && n <= MAX_CLIPS && H >= 1 && W >= 1 && (int64_t)H * W < (1ll << 31); }
@@ -217,12 +187,11 @@ struct ProbK {
 // allows (a frame of odd H * W starts at an odd element), as 2-byte stores otherwise; a group that crosses the frame's end writes its ny.
 __global__ __launch_bounds__(256) void frame_probs_kernel(const ProbK p) {
     const ClipGeom& g = p.g;
-    const int c = blockIdx.y >> 3, k = blockIdx.y & 7;
-    const int64_t f = (int64_t)g.starts[c] + (int64_t)k * g.f_skip;
-    if (f >= g.F) return;                                            // a frame past the end: nothing read, nothing written
+    const int64_t f = slot_frame(g, blockIdx.y);
+    if (f < 0) return;
     const uint32_t HW = (uint32_t)g.H * (uint32_t)g.W, total4 = (HW + 3u) >> 2;
     const size_t per = (size_t)g.S * g.S;
-    const float* lp = p.logits + ((size_t)c * 8 + k) * per;          // view v: + v * view_stride * 8 * per
+    const float* lp = p.logits + (size_t)blockIdx.y * per;           // view v: + v * view_stride * 8 * per
     const size_t vstep = (size_t)g.view_stride * 8 * per;
     uint16_t* pf = p.prob + (size_t)f * HW;
     for (uint32_t idx = blockIdx.x * BT + threadIdx.x; idx < total4; idx += (uint32_t)p.bpf * BT) {
@@ -232,17 +201,8 @@ __global__ __launch_bounds__(256) void frame_probs_kernel(const ProbK p) {
         const int ny = merge_group4(g, lp, vstep, px, HW, gy, gx, mg, num);
         uint32_t q[4];
 #pragma unroll
-        for (int e = 0; e < 4; ++e) {
-            const float m = mg[e];
-            // no view covers the pixel, or a NaN: 0, written as such and not left to the conversion
-            q[e] = (num[e] == 0 || m != m) ? 0u : __float2uint_rn((1.0f / (1.0f + expf(-m))) * (float)PC_PROB_ONE);
-        }
-        uint16_t* o = pf + px;
-        if (ny == 4 && ((uintptr_t)o & 7) == 0) {
-            *(uint2*)o = make_uint2(q[0] | (q[1] << 16), q[2] | (q[3] << 16));
-        } else {
-            for (int e = 0; e < ny; ++e) o[e] = (uint16_t)q[e];
-        }
+        for (int e = 0; e < 4; ++e) q[e] = num[e] ? prob_word(mg[e], sigmoid(mg[e])) : 0u;     // no view covers the pixel: 0
+        store_prob4(pf + px, q, ny);
     }
 }
 

@@ -4,20 +4,17 @@
 //                                       centres (cv2.INTER_LINEAR / align_corners=False), the index exact in 64-bit integers
 //   pc_detect_frames_scaled_ws_bytes    host arithmetic: the partials, then the merged plane (a float and a cover byte per working pixel)
 //   pc_detect_frames_scaled             two traversals and the records kernel:
-//     merge_plane_kernel     the working frame in groups of four (viewmerge.h: merge_group4, the rule of pc_detect_frames_views bit for
-//                            bit): merged logit and cover count of every working pixel into the plane in `ws`, each logit fetched once
-//     resample_kernel        the native frame in groups of four: up to four taps of the plane per pixel, every product and sum one fp32
-//                            round-to-nearest operation, a tap of zero weight not read; then seg_positive, mask, box, score and (if asked
-//                            for) the uint16 probability of pc_frame_probs -- one pass, no second walk over the logits
+//     merge_plane_kernel     detectrec.h: merge_to_plane, the working frame in groups of four (merge_group4, the rule of
+//                            pc_detect_frames_views bit for bit): merged logit and cover count of every working pixel into the (clip,
+//                            frame) slot's plane in `ws`, each logit fetched once
+//     resample_kernel        detectrec.h: detect_native_frame over one plane, the native frame in groups of four: up to four taps of
+//                            the plane per pixel, every product and sum one fp32 round-to-nearest operation, a tap of zero weight not read;
+//                            then seg_positive, mask, box, score and (if asked for) the uint16 probability of pc_frame_probs -- one pass,
+//                            no second walk over the logits
 //     detect_records_kernel  detectrec.h: the partials in block order -> the 8-word record
-// The plane of one (clip, frame) slot is padded to a multiple of four pixels, so that a group's four floats and four cover bytes always go
-// out as one 16-byte and one 4-byte store.  No atomics of any kind; nothing has to be zeroed in front of the launch.
+// No atomics of any kind; nothing has to be zeroed in front of the launch.
 #include <cstring>
 
-#include "common.h"
-#include "evalpred.h"
-#include "clipgeom.h"
-#include "viewmerge.h"
 #include "detectrec.h"
 
 namespace {
@@ -32,115 +29,29 @@ struct ScaleK {
     int H, W, bpf_s;             // the native frame; blocks per frame of the merge traversal
 };
 
-inline size_t plane_stride(int Hs, int Ws) { return ((size_t)Hs * Ws + 3) & ~(size_t)3; }
-
 inline bool scaled_shape_ok(int n, int Hs, int Ws, int H, int W) {
     return n >= 1 && n <= MAX_CLIPS && Hs >= 1 && Ws >= 1 && H >= 1 && W >= 1 && (int64_t)Hs * Ws < (1ll << 31) && (int64_t)H * W < (1ll << 31) &&
            2 * (int64_t)(H > W ? H : W) < (1ll << 24);
 }
 
-// grid (bpf_s, n * 8): the groups of four of detect_frames_views_kernel over the working frame.  The padding of a slot's last group takes
-// merge_group4's values for pixels that do not exist (0.0f, cover 0); nothing reads it.
+// grid (bpf_s, n * 8): the working frame of slot blockIdx.y into its plane and cover
 __global__ __launch_bounds__(256) void merge_plane_kernel(const ScaleK p) {
-    const ClipGeom& g = p.d.g;
-    const int c = blockIdx.y >> 3, k = blockIdx.y & 7;
-    const int64_t f = (int64_t)g.starts[c] + (int64_t)k * g.f_skip;
-    if (f >= g.F) return;                                            // a frame past the end: nothing read, nothing written
-    const uint32_t HW = (uint32_t)g.H * (uint32_t)g.W, total4 = (HW + 3u) >> 2;
-    const size_t per = (size_t)g.S * g.S;
-    const float* lp = p.d.logits + ((size_t)c * 8 + k) * per;        // view v: + v * view_stride * 8 * per
-    const size_t vstep = (size_t)g.view_stride * 8 * per;
-    float* pl = p.plane + (size_t)blockIdx.y * p.pstride;
-    uint8_t* cv = p.cover + (size_t)blockIdx.y * p.pstride;
-    for (uint32_t idx = blockIdx.x * BT + threadIdx.x; idx < total4; idx += (uint32_t)p.bpf_s * BT) {
-        const uint32_t px = idx << 2;
-        float mg[4];
-        int num[4], gy, gx;
-        merge_group4(g, lp, vstep, px, HW, gy, gx, mg, num);
-        f32x4 q;
-        q[0] = mg[0]; q[1] = mg[1]; q[2] = mg[2]; q[3] = mg[3];
-        *(f32x4*)(pl + px) = q;
-        *(uint32_t*)(cv + px) = (uint32_t)num[0] | ((uint32_t)num[1] << 8) | ((uint32_t)num[2] << 16) | ((uint32_t)num[3] << 24);
-    }
+    if (slot_frame(p.d.g, blockIdx.y) < 0) return;
+    merge_to_plane(p.d.g, p.d.logits, blockIdx.y, p.bpf_s, p.plane + (size_t)blockIdx.y * p.pstride, p.cover + (size_t)blockIdx.y * p.pstride);
 }
 
-// One tap row of the bilinear rule: the value at column pair (ix, ix + 1) of plane row r with the second weight wx1; `ok` is cleared when a
-// tap that is read has no cover.  A tap of zero weight is not read.
-__device__ __forceinline__ float tap_row(const float* pl, const uint8_t* cv, size_t r, int ix, int ix1, float wx0, float wx1, bool& ok) {
-    const float a = pl[r + ix];
-    ok = ok && cv[r + ix] != 0;
-    if (wx1 == 0.0f) return a;
-    const float b = pl[r + ix1];
-    ok = ok && cv[r + ix1] != 0;
-    return __fadd_rn(__fmul_rn(a, wx0), __fmul_rn(b, wx1));
-}
+struct PlaneTap {                // a tap of the slot's one plane
+    const float* pl;
+    __device__ __forceinline__ float at(size_t idx) const { return pl[idx]; }
+};
 
-// grid (bpf, n * 8), bpf = det_views_bpf(H * W): the native frame in groups of four consecutive pixels (frame order, a group may run over a
-// row's end).  The grouping depends on H, W alone, so the order of the sums is the same with any mask or prob or none.  The table's indices
-// are clamped into the plane: a table that is not pc_resample_tables' for these sizes gives wrong values, never an access outside `ws`.
+// grid (bpf, n * 8), bpf = det_views_bpf(H * W): the native frame from the plane of slot blockIdx.y
 __global__ __launch_bounds__(256) void resample_kernel(const ScaleK p) {
-    const ClipGeom& g = p.d.g;
-    const int c = blockIdx.y >> 3, k = blockIdx.y & 7;
-    const int64_t f = (int64_t)g.starts[c] + (int64_t)k * g.f_skip;
-    if (f >= g.F) return;                                            // a frame past the end: nothing read, nothing written
-    const int W = p.W, Hs = g.H, Ws = g.W;
-    const uint32_t HW = (uint32_t)p.H * (uint32_t)W, total4 = (HW + 3u) >> 2;
-    const float* pl = p.plane + (size_t)blockIdx.y * p.pstride;
-    const uint8_t* cv = p.cover + (size_t)blockIdx.y * p.pstride;
-    const int32_t* rowt = p.tab;
-    const int32_t* colt = p.tab + 2 * (size_t)p.H;
-    uint8_t* mf = p.d.mask ? p.d.mask + (size_t)f * HW : nullptr;
-    uint16_t* pf = p.prob ? p.prob + (size_t)f * HW : nullptr;
-    double sum = 0.0;
-    int cnt = 0, x0 = 0x7fffffff, y0 = 0x7fffffff, x1 = -1, y1 = -1;
-    for (uint32_t idx = blockIdx.x * BT + threadIdx.x; idx < total4; idx += (uint32_t)p.d.bpf * BT) {
-        const uint32_t px = idx << 2;
-        const int ny = (int)(HW - px < 4u ? HW - px : 4u);
-        const int gy = (int)(px / (uint32_t)W), gx = (int)(px - (uint32_t)gy * (uint32_t)W);
-        uint32_t bits = 0, q[4] = {0u, 0u, 0u, 0u};
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-            if (e >= ny) continue;
-            int y = gy, x = gx + e;
-            if (x >= W) { x -= W; ++y; if (x >= W) { x -= W; ++y; if (x >= W) { x -= W; ++y; } } }     // W >= 1: at most three rows on
-            const int iy = min(max(rowt[2 * y], 0), Hs - 1), iy1 = min(iy + 1, Hs - 1);
-            const int ix = min(max(colt[2 * x], 0), Ws - 1), ix1 = min(ix + 1, Ws - 1);
-            const float wy1 = __int_as_float(rowt[2 * y + 1]), wx1 = __int_as_float(colt[2 * x + 1]);
-            const float wy0 = __fsub_rn(1.0f, wy1), wx0 = __fsub_rn(1.0f, wx1);
-            bool ok = true;
-            float v = tap_row(pl, cv, (size_t)iy * Ws, ix, ix1, wx0, wx1, ok);
-            if (wy1 != 0.0f) {
-                const float bot = tap_row(pl, cv, (size_t)iy1 * Ws, ix, ix1, wx0, wx1, ok);
-                v = __fadd_rn(__fmul_rn(v, wy0), __fmul_rn(bot, wy1));
-            }
-            if (!ok) continue;                                       // a tap that was read has no cover: background, probability 0
-            const float sg = 1.0f / (1.0f + expf(-v));
-            if (v == v) q[e] = __float2uint_rn(sg * (float)PC_PROB_ONE);
-            if (seg_positive(v)) {
-                bits |= 1u << (8 * e);
-                sum += (double)sg;
-                ++cnt;
-                x0 = min(x0, x); x1 = max(x1, x); y0 = min(y0, y); y1 = max(y1, y);
-            }
-        }
-        if (mf) {
-            uint8_t* m = mf + px;
-            if (ny == 4 && ((uintptr_t)m & 3) == 0) {
-                *(uint32_t*)m = bits;
-            } else {
-                for (int e = 0; e < ny; ++e) m[e] = (uint8_t)((bits >> (8 * e)) & 1);
-            }
-        }
-        if (pf) {
-            uint16_t* o = pf + px;
-            if (ny == 4 && ((uintptr_t)o & 7) == 0) {
-                *(uint2*)o = make_uint2(q[0] | (q[1] << 16), q[2] | (q[3] << 16));
-            } else {
-                for (int e = 0; e < ny; ++e) o[e] = (uint16_t)q[e];
-            }
-        }
-    }
-    block_partial(sum, cnt, x0, y0, x1, y1, p.d.part + (size_t)blockIdx.y * p.d.bpf + blockIdx.x);
+    const int64_t f = slot_frame(p.d.g, blockIdx.y);
+    if (f < 0) return;
+    const PlaneTap tap{p.plane + (size_t)blockIdx.y * p.pstride};
+    detect_native_frame(tap, p.cover + (size_t)blockIdx.y * p.pstride, p.tab, f, p.H, p.W, p.d.g.H, p.d.g.W, p.d.mask, p.prob, p.d.bpf,
+                        p.d.part + (size_t)blockIdx.y * p.d.bpf + blockIdx.x);
 }
 
 inline int64_t partial_bytes(int n, int H, int W) { return (int64_t)n * 8 * det_views_bpf((int64_t)H * W) * (int64_t)sizeof(Partial); }

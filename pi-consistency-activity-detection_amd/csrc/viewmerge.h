@@ -1,11 +1,18 @@
 // What the mask and the probability map of a multi-view detection share, so that they can never disagree about what was merged:
-//   merge_group4   the merged logits of four consecutive full-frame pixels (pc_detect_frames_views' rule: the views that cover a pixel in table
-//                  order, the first value as it is, the others added with __fadd_rn, one __fdiv_rn by the count when more than one covers)
-// Called by detect_frames_views_kernel (mask, box, score) and frame_probs_kernel (the uint16 probability) of detect.hip, and by
-// merge_plane_kernel of detectscale.hip (the merged plane of a working frame, resampled to native size behind it).
+//   group_pixel      where pixel e of a group of four consecutive pixels lies (the row wrap)
+//   merge_group4     the merged logits of four consecutive full-frame pixels (pc_detect_frames_views' rule: the views that cover a pixel in table
+//                    order, the first value as it is, the others added with __fadd_rn, one __fdiv_rn by the count when more than one covers)
+// merge_group4 is called by detect_frames_views_kernel (mask, box, score) and frame_probs_kernel (the uint16 probability) of detect.hip, and
+// by merge_to_plane of detectrec.h (the merged plane of a working frame or of a window, detected at native size behind it).
 #pragma once
 #include "common.h"
 #include "clipgeom.h"
+
+// Pixel e of the group of four that starts at (gy, gx) of a frame W >= 1 wide: at most three rows on.
+__device__ __forceinline__ void group_pixel(int gy, int gx, int e, int W, int& y, int& x) {
+    y = gy; x = gx + e;
+    if (x >= W) { x -= W; ++y; if (x >= W) { x -= W; ++y; if (x >= W) { x -= W; ++y; } } }
+}
 
 // The group of four consecutive pixels (frame order; it may run over a row's end, and over the frame's end: only the first `ny` exist) that
 // starts at pixel px < HW of an H x W frame.  lp: the logits of view 0 for this clip and frame, vstep: floats from one view to the next.
@@ -38,8 +45,8 @@ __device__ __forceinline__ int merge_group4(const ClipGeom& g, const float* lp, 
         }
 #pragma unroll
         for (int e = 0; e < 4; ++e) {
-            int y = gy, x = gx + e;
-            if (x >= W) { x -= W; ++y; if (x >= W) { x -= W; ++y; if (x >= W) { x -= W; ++y; } } }     // W >= 1: at most three rows on
+            int y, x;
+            group_pixel(gy, gx, e, W, y, x);
             const int ey = y - h0, ex = x - w0;
             if (e < ny && ey >= 0 && ey < S && ex >= 0 && ex < S) {
                 const float t = lv[(size_t)ey * S + (flip ? S - 1 - ex : ex)];
@@ -52,3 +59,4 @@ __device__ __forceinline__ int merge_group4(const ClipGeom& g, const float* lp, 
     for (int e = 0; e < 4; ++e) m[e] = num[e] > 1 ? __fdiv_rn(acc[e], (float)num[e]) : acc[e];
     return ny;
 }
+

@@ -519,6 +519,27 @@ def score_instances(sums, npix, kept, flags):
     return inst_scores, other
 
 
+def collect_launches(n, V, slot, first, row0, per):
+    """The launches (32 clips at most each) that collect a segment of n clips and V views behind its forward.  The segment begins at batch
+    slot `slot` with the video's clip `first`, view v of its clip c at slot v * n + c; a slot holds `per` logits; row0: the video's first
+    score row.  -> [(lo, hi, s0, s1, row)]: the logits [lo:hi] of clips [s0:s1] of the video at view stride n, `row` the first one's row."""
+    return [((slot + q) * per, (slot + q + (V - 1) * n + min(32, n - q)) * per, first + q, first + q + min(32, n - q), row0 + (first + q) * V)
+            for q in range(0, n, 32)]
+
+
+def record_layout(F, C, K, scores, links):
+    """The words of a video's device record, in the order one copy takes them to the host -> a namespace of slices: rec (F records of 8
+    words), cls (the class vector, C + 2), inst (F instance records of 4 + 6K words, K > 0), score (F * 3 (K + 1) words with instance scores),
+    link (F * links * (K + 1)^2 words); words: their total.  A part that is not asked for is empty and moves nothing in front of it."""
+    sizes = dict(rec=F * ops.DETECT_REC_WORDS, cls=C + 2, inst=F * (ops.INST_HDR + K * ops.INST_WORDS) if K else 0,
+                 score=F * ops.SCORE_WORDS * (K + 1) if scores else 0, link=F * links * (K + 1) ** 2)
+    lay = SimpleNamespace(words=0)
+    for name, words in sizes.items():
+        setattr(lay, name, slice(lay.words, lay.words + words))
+        lay.words += words
+    return lay
+
+
 class DetectEngine(ClipEngine):
     """Detects with the weights in the flat buffers P, R: a StepEngine's own (StepEngine.detect_engine: no copy, behind its lanes) or, built
     from a state dict, buffers of its own (load_state per checkpoint).
@@ -692,15 +713,17 @@ class DetectEngine(ClipEngine):
         return views
 
     def _width(self, rec):
-        return len(rec.views) if rec.views else 1
+        return len(rec.views)
 
     def add_video(self, frames_u8):
         """One video: frames [F,H,W,3] uint8 (numpy, host tensor or device tensor).  Uploaded through page-locked memory on the copy stream; its
         clips join the batches.  -> the index of the video in results()."""
         v, starts, row0, pos = self.check_video(frames_u8)
         F, H, W = (int(s) for s in v.shape[:3])
-        h0, w0 = centre_crop(*self._frame(H, W), self.hw)           # crop and views: of the working frame, if one is set
-        views = self.video_views(*self._frame(H, W))
+        frame = self._frame(H, W)                                     # crop and views: of the working frame, if one is set
+        h0, w0 = centre_crop(*frame, self.hw)
+        views = self.video_views(*frame)
+        cut = views or [(h0, w0, 0)]                                  # the centre crop is the one view (h0, w0, 0)
         slot = self.up_slot
         self.up_slot ^= 1
         if self.up_done[slot] is not None:
@@ -709,18 +732,15 @@ class DetectEngine(ClipEngine):
         dv, _none, entry = self._upload(v)
         self.up_pin[slot] = self.pin                                  # (grown, if the video was larger than the slot)
         rec = SimpleNamespace(video=dv, truth=None, entry=entry, F=F, H=H, W=W, h0=h0, w0=w0, ready=torch.cuda.Event(), waited=False,
-                              starts=starts, rows=len(starts) * len(views or (0,)), done=0, views=views, work=self.work, wvideo=None)
+                              starts=starts, rows=len(starts) * len(cut), done=0, views=cut, centre=views is None, frame=frame, work=self.work,
+                              wvideo=None)
         rec.ready.record(self.copy_stream)
         self.up_done[slot] = rec.ready
-        # records [F][8] and the class vector [C + 2] side by side: one copy to the host takes both.  Every frame below F belongs to one clip,
-        # so every mask byte and every record is written by a launch: nothing is filled.
-        # With instances the F records of 4 + 6K words follow behind the class vector: the earlier offsets do not move.
-        rec.inst_words = F * (ops.INST_HDR + self.inst_k * ops.INST_WORDS) if self.inst_k else 0
-        # With instance scores the F records of 3 (K + 1) words follow behind those.
-        rec.score_words = F * ops.SCORE_WORDS * (self.inst_k + 1) if self.instance_scores else 0
-        # With instance links the F records of L (K + 1)^2 words follow behind those.
-        rec.link_words = F * self.instance_links * (self.inst_k + 1) ** 2
-        rec.dev = torch.empty(F * ops.DETECT_REC_WORDS + self.C + 2 + rec.inst_words + rec.score_words + rec.link_words, dtype=torch.int32, device=self.dev)
+        # records, class vector and what instances add side by side: one copy to the host takes them all.  Every frame below F belongs to a
+        # clip, so every mask byte and every record is written by a launch: nothing is filled.
+        rec.at = record_layout(F, self.C, self.inst_k, self.instance_scores, self.instance_links)
+        rec.score_words, rec.link_words = (s.stop - s.start for s in (rec.at.score, rec.at.link))
+        rec.dev = torch.empty(rec.at.words, dtype=torch.int32, device=self.dev)
         rec.mask = torch.empty(F, H, W, dtype=torch.uint8, device=self.dev) if self.masks else None
         rec.imap = torch.empty(F, H, W, dtype=torch.uint8, device=self.dev) if self.instance_maps or self.instance_scores or self.instance_links else None
         rec.prob = torch.empty(F, H, W, dtype=torch.int16, device=self.dev) if self.instance_scores else None
@@ -729,12 +749,12 @@ class DetectEngine(ClipEngine):
         if rec.hop:
             # the slot planes and the cover of the frame the views are cut from, in one allocation, until the video's last clip has run;
             # every (slot, frame) that is read has been written by a launch: nothing is filled
-            rec.planes = torch.empty(ops.clip_planes_bytes(F, *self._frame(H, W), self.f_skip, rec.hop), dtype=torch.uint8, device=self.dev)
+            rec.planes = torch.empty(ops.clip_planes_bytes(F, *frame, self.f_skip, rec.hop), dtype=torch.uint8, device=self.dev)
             need = ops.detect_frames_planes_ws_bytes(min(F, ops.PLANES_MAX_FRAMES), H, W)
             if self.ws_planes is None or self.ws_planes.numel() < need:
                 self.ws_planes = torch.empty(need, dtype=torch.uint8, device=self.dev)
         elif rec.work:
-            need = ops.detect_frames_scaled_ws_bytes(min(self.bs // len(views or (0,)), 32), rec.work[0], rec.work[1], H, W)
+            need = ops.detect_frames_scaled_ws_bytes(min(self.bs // len(cut), 32), *frame, H, W)
             if self.ws_scaled is None or self.ws_scaled.numel() < need:
                 self.ws_scaled = torch.empty(need, dtype=torch.uint8, device=self.dev)
         elif views:
@@ -747,7 +767,7 @@ class DetectEngine(ClipEngine):
 
     def _cut(self, rec, first, k, slot, seg):
         # view v of the segment's clip c at slot v * seg + c: this launch's clips start at `slot`.  The centre crop is the one view at stride seg.
-        per, views = self.per, rec.views or [(rec.h0, rec.w0, 0)]
+        per, views = self.per, rec.views
         video = rec.video
         if rec.work:
             if rec.wvideo is None:                                    # the video's first cut, behind rec.ready on this stream: its one resize
@@ -762,72 +782,44 @@ class DetectEngine(ClipEngine):
         v.wvideo = None                                               # made and read on the compute stream alone
 
     def _collect(self, rec, first, n, slot):
-        per, hw, W8 = self.per, self.hw, ops.DETECT_REC_WORDS
-        if rec.hop:
-            # one launch: the views (the centre crop as the one view) merged on the frame they are cut from, into the video's slot planes;
-            # the cover bytes with the video's first launch.  Mask, records and probability wait for the last clip (_finish).
-            views = rec.views or [(rec.h0, rec.w0, 0)]
-            V = len(views)
-            Hs, Ws = rec.work[:2] if rec.work else (rec.H, rec.W)
-            for q in range(0, n, 32):
-                k = min(32, n - q)
-                ops.clip_planes(self.out[(slot + q) * per:(slot + q + (V - 1) * n + k) * per].view(-1, 8, hw, hw), views, rec.starts[first + q:first + q + k],
-                                rec.F, Hs, Ws, self.f_skip, rec.hop, view_stride=n, planes=rec.planes, cover=first + q == 0)
-            return
-        if rec.work:
-            # one launch: the views (the centre crop as the one view) merged on the working frame, resampled to native size, and the
-            # probability map with them
-            views = rec.views or [(rec.h0, rec.w0, 0)]
-            V = len(views)
-            for q in range(0, n, 32):
-                k = min(32, n - q)
-                ops.detect_frames_scaled(self.out[(slot + q) * per:(slot + q + (V - 1) * n + k) * per].view(-1, 8, hw, hw), views,
-                                         rec.starts[first + q:first + q + k], rec.F, rec.H, rec.W, rec.work[0], rec.work[1], self.f_skip, view_stride=n,
-                                         row0=rec.row0 + (first + q) * V, mask=rec.mask, prob=rec.prob, rec=rec.dev[:rec.F * W8].view(rec.F, W8),
-                                         ws=self.ws_scaled, want_mask=False)
-            return
-        if rec.views:
-            V = len(rec.views)
-            for q in range(0, n, 32):
-                k = min(32, n - q)
-                ops.detect_frames_views(self.out[(slot + q) * per:(slot + q + (V - 1) * n + k) * per].view(-1, 8, hw, hw), rec.views,
-                                        rec.starts[first + q:first + q + k], rec.F, rec.H, rec.W, self.f_skip, view_stride=n, row0=rec.row0 + (first + q) * V,
-                                        mask=rec.mask, rec=rec.dev[:rec.F * W8].view(rec.F, W8), ws=self.ws_views, want_mask=False)
+        F, H, W, (Hs, Ws), views, fs = rec.F, rec.H, rec.W, rec.frame, rec.views, self.f_skip
+        out = dict(mask=rec.mask, rec=rec.dev[rec.at.rec].view(F, -1), want_mask=False)
+        for lo, hi, s0, s1, row in collect_launches(n, len(views), slot, first, rec.row0, self.per):
+            logits, starts = self.out[lo:hi].view(-1, 8, self.hw, self.hw), rec.starts[s0:s1]
+            if rec.hop:
+                # the views merged on the frame they are cut from, into the video's slot planes; the cover bytes with the video's first
+                # launch.  Mask, records and probability wait for the last clip (_finish).
+                ops.clip_planes(logits, views, starts, F, Hs, Ws, fs, rec.hop, view_stride=n, planes=rec.planes, cover=s0 == 0)
+            elif rec.work:
+                # the views merged on the working frame, resampled to native size, and the probability map with them
+                ops.detect_frames_scaled(logits, views, starts, F, H, W, Hs, Ws, fs, view_stride=n, row0=row, prob=rec.prob, ws=self.ws_scaled, **out)
+            else:
+                if rec.centre:
+                    ops.detect_frames(logits, starts, F, H, W, rec.h0, rec.w0, fs, row0=row, ws=self.ws, **out)
+                else:
+                    ops.detect_frames_views(logits, views, starts, F, H, W, fs, view_stride=n, row0=row, ws=self.ws_views, **out)
                 if rec.prob is not None:
-                    ops.frame_probs(self.out[(slot + q) * per:(slot + q + (V - 1) * n + k) * per].view(-1, 8, hw, hw), rec.views,
-                                    rec.starts[first + q:first + q + k], rec.F, rec.H, rec.W, self.f_skip, view_stride=n, prob=rec.prob)
-            return
-        for q in range(0, n, 32):
-            k = min(32, n - q)
-            ops.detect_frames(self.out[(slot + q) * per:(slot + q + k) * per].view(k, 8, hw, hw), rec.starts[first + q:first + q + k], rec.F, rec.H, rec.W,
-                              rec.h0, rec.w0, self.f_skip, row0=rec.row0 + first + q, mask=rec.mask, rec=rec.dev[:rec.F * W8].view(rec.F, W8), ws=self.ws,
-                              want_mask=False)
-            if rec.prob is not None:
-                ops.frame_probs(self.out[(slot + q) * per:(slot + q + k) * per].view(k, 8, hw, hw), [(rec.h0, rec.w0, 0)], rec.starts[first + q:first + q + k],
-                                rec.F, rec.H, rec.W, self.f_skip, prob=rec.prob)
+                    ops.frame_probs(logits, views, starts, F, H, W, fs, view_stride=n, prob=rec.prob)
 
     def _finish(self, rec):
         """The video's class from its score rows, its instances from its masks (every frame has been written by now, on this stream); records,
         class vector and instances on their way to the host."""
-        cls0 = rec.F * ops.DETECT_REC_WORDS
+        at = rec.at
         if rec.hop:
             # every clip's frames lie in the slot planes: per frame the mean of the windows that hold it -> mask, probability and records
-            Hs, Ws = rec.work[:2] if rec.work else (rec.H, rec.W)
             for f0 in range(0, rec.F, ops.PLANES_MAX_FRAMES):
-                ops.detect_frames_planes(rec.planes, rec.F, rec.H, rec.W, Hs, Ws, self._width(rec), self.f_skip, rec.hop, f0,
+                ops.detect_frames_planes(rec.planes, rec.F, rec.H, rec.W, *rec.frame, self._width(rec), self.f_skip, rec.hop, f0,
                                          min(ops.PLANES_MAX_FRAMES, rec.F - f0), row0=rec.row0, mask=rec.mask, prob=rec.prob,
-                                         rec=rec.dev[:cls0].view(rec.F, ops.DETECT_REC_WORDS), ws=self.ws_planes, want_mask=False)
+                                         rec=rec.dev[at.rec].view(rec.F, -1), ws=self.ws_planes, want_mask=False)
             rec.planes = None                                         # written and read on the compute stream alone: the allocator may reuse them
-        ops.video_class(self.scores[rec.row0:rec.row0 + rec.rows], out=rec.dev[cls0:cls0 + self.C + 2].view(torch.float32))
+        ops.video_class(self.scores[rec.row0:rec.row0 + rec.rows], out=rec.dev[at.cls].view(torch.float32))
         if self.inst_k:
-            inst0 = cls0 + self.C + 2
-            ops.frame_instances(rec.mask, conn=self.conn, min_area=self.min_area, K=self.inst_k, inst=rec.dev[inst0:inst0 + rec.inst_words].view(rec.F, -1),
-                                imap=rec.imap, want_imap=False)
+            ops.frame_instances(rec.mask, conn=self.conn, min_area=self.min_area, K=self.inst_k, inst=rec.dev[at.inst].view(rec.F, -1), imap=rec.imap,
+                                want_imap=False)
             if rec.prob is not None:
-                ops.instance_scores(rec.imap, rec.prob, self.inst_k, out=rec.dev[inst0 + rec.inst_words:inst0 + rec.inst_words + rec.score_words].view(rec.F, -1))
+                ops.instance_scores(rec.imap, rec.prob, self.inst_k, out=rec.dev[at.score].view(rec.F, -1))
             if self.instance_links:
-                link0 = inst0 + rec.inst_words + rec.score_words
-                ops.instance_overlaps(rec.imap, self.inst_k, self.instance_links, out=rec.dev[link0:link0 + rec.link_words])
+                ops.instance_overlaps(rec.imap, self.inst_k, self.instance_links, out=rec.dev[at.link])
         rec.pin = self._stage(rec.dev.numel())
         rec.pin.copy_(rec.dev, non_blocking=True)
 
@@ -837,28 +829,44 @@ class DetectEngine(ClipEngine):
         torch.cuda.current_stream(self.dev).synchronize()
         out = []
         for rec in self.videos:
-            words = rec.pin.numpy()
-            counts, boxes, fscores, _rows = ops.decode_detect_records(words[:rec.F * ops.DETECT_REC_WORDS])
-            cls0 = rec.F * ops.DETECT_REC_WORDS
-            cls = words[cls0:cls0 + self.C + 2].copy().view(np.float32)
+            words, at = rec.pin.numpy(), rec.at
+            counts, boxes, fscores, _rows = ops.decode_detect_records(words[at.rec])
+            cls = words[at.cls].copy().view(np.float32)
             inst = scores = overlaps = None
             if self.inst_k:
-                inst0 = cls0 + self.C + 2
-                n, kept, _runs, flags, areas, ibox, first = ops.decode_instances(words[inst0:inst0 + rec.inst_words], self.inst_k)
+                n, kept, _runs, flags, areas, ibox, first = ops.decode_instances(words[at.inst], self.inst_k)
                 inst = substitute_overflow(counts, boxes, self.min_area, (n, kept, flags, areas, ibox, first))
                 if self.instance_scores:
-                    sums, npix = ops.decode_instance_scores(words[inst0 + rec.inst_words:inst0 + rec.inst_words + rec.score_words], self.inst_k)
+                    sums, npix = ops.decode_instance_scores(words[at.score], self.inst_k)
                     scores = score_instances(sums, npix, inst[1], inst[2])
                 if self.instance_links:
-                    link0 = inst0 + rec.inst_words + rec.score_words
-                    overlaps = ops.decode_instance_overlaps(words[link0:link0 + rec.link_words], self.inst_k, self.instance_links)
-            out.append(Detection(int(cls[self.C]), float(cls[self.C + 1]), cls[:self.C].copy(), counts, boxes, fscores, rec.mask,
-                                 list(rec.views) if rec.views else [(rec.h0, rec.w0, 0)], inst, rec.imap if self.instance_maps else None, scores, rec.prob, overlaps))
+                    overlaps = ops.decode_instance_overlaps(words[at.link], self.inst_k, self.instance_links)
+            out.append(Detection(int(cls[self.C]), float(cls[self.C + 1]), cls[:self.C].copy(), counts, boxes, fscores, rec.mask, list(rec.views), inst,
+                                 rec.imap if self.instance_maps else None, scores, rec.prob, overlaps))
             if rec.work:
                 out[-1].work = tuple(rec.work)
             if rec.hop:
                 out[-1].hop = rec.hop
         return out
+
+    def _check_pass(self, who, which):
+        """The refusals mask_runs and score (who) open with: a `which` the engine does not keep, no finished pass."""
+        if which not in ("masks", "imap"):
+            raise ValueError("%s: which = %r, \"masks\" or \"imap\"" % (who, which))
+        if which == "masks" and not self.masks:
+            raise ValueError("%s: the engine keeps no masks (masks=False)" % who)
+        if which == "imap" and not self.instance_maps:
+            raise ValueError("%s: the engine keeps no maps of ranks (instances=K with instance_maps=True)" % who)
+        if not self.videos or any(rec.pin is None for rec in self.videos):
+            raise ValueError("%s: no finished pass (call it after results())" % who)
+
+    def _picks(self, who, videos):
+        """`videos` of mask_runs and score (who) -> the indices of the pass's videos they name, all of them for None."""
+        picks = list(range(len(self.videos))) if videos is None else [int(v) for v in videos]
+        for v in picks:
+            if not 0 <= v < len(self.videos):
+                raise ValueError("%s: video %d outside the %d of the pass" % (who, v, len(self.videos)))
+        return picks
 
     def mask_runs(self, which="masks", videos=None):
         """The masks (which="masks") or the maps of ranks (which="imap": needs instance_maps=True) of the last pass as row runs -> [MaskRuns],
@@ -867,18 +875,8 @@ class DetectEngine(ClipEngine):
         pixels or more in several frame ranges) and the per-frame offsets gathered into page-locked memory -- first wait --, then one buffer
         of exactly the pass's runs is filled (pc_mask_runs per range) and leaves in one asynchronous copy -- second wait.  Every refusal is a
         ValueError before anything is enqueued."""
-        if which not in ("masks", "imap"):
-            raise ValueError("mask_runs: which = %r, \"masks\" or \"imap\"" % (which,))
-        if which == "masks" and not self.masks:
-            raise ValueError("mask_runs: the engine keeps no masks (masks=False)")
-        if which == "imap" and not self.instance_maps:
-            raise ValueError("mask_runs: the engine keeps no maps of ranks (instances=K with instance_maps=True)")
-        if not self.videos or any(rec.pin is None for rec in self.videos):
-            raise ValueError("mask_runs: no finished pass (call it after results())")
-        picks = list(range(len(self.videos))) if videos is None else [int(v) for v in videos]
-        for v in picks:
-            if not 0 <= v < len(self.videos):
-                raise ValueError("mask_runs: video %d outside the %d of the pass" % (v, len(self.videos)))
+        self._check_pass("mask_runs", which)
+        picks = self._picks("mask_runs", videos)
         jobs = []                                                     # (map, f0, nf, first word of its offsets in the staging)
         words = 0
         for v in picks:
@@ -942,24 +940,14 @@ class DetectEngine(ClipEngine):
         (score_pass).  Unlike EvalEngine the truth is taken on the full frame, not inside the centre crop, and `correct` compares with the
         detection's class, voted over all clips of the video, where EvalEngine votes over the clips that hold truth.  Every refusal is a
         ValueError before anything is enqueued."""
-        if which not in ("masks", "imap"):
-            raise ValueError("score: which = %r, \"masks\" or \"imap\"" % (which,))
-        if which == "masks" and not self.masks:
-            raise ValueError("score: the engine keeps no masks (masks=False)")
-        if which == "imap" and not self.instance_maps:
-            raise ValueError("score: the engine keeps no maps of ranks (instances=K with instance_maps=True)")
-        if not self.videos or any(rec.pin is None for rec in self.videos):
-            raise ValueError("score: no finished pass (call it after results())")
+        self._check_pass("score", which)
         try:
             A = int(actors)
         except (TypeError, ValueError):
             raise ValueError("score: actors = %r is not a number" % (actors,)) from None
         if A != actors or not 1 <= A <= ops.CROSS_MAX_SLOTS:
             raise ValueError("score: actors = %r outside 1..%d" % (actors, ops.CROSS_MAX_SLOTS))
-        picks = list(range(len(self.videos))) if videos is None else [int(v) for v in videos]
-        for v in picks:
-            if not 0 <= v < len(self.videos):
-                raise ValueError("score: video %d outside the %d of the pass" % (v, len(self.videos)))
+        picks = self._picks("score", videos)
         truths, labels = list(truths), list(labels)
         if not (len(truths) == len(labels) == len(picks)):
             raise ValueError("score: %d truths and %d labels for %d videos" % (len(truths), len(labels), len(picks)))
@@ -1001,8 +989,7 @@ class DetectEngine(ClipEngine):
         tables = [ops.decode_map_crosstab(host[w0:w0 + rec.F * (P + 2) * (A + 2)], P, A) for rec, _t, w0 in jobs]      # copies: the staging is used again
         predicted = []
         for rec, _t, _w0 in jobs:
-            cls0 = rec.F * ops.DETECT_REC_WORDS
-            predicted.append(int(rec.pin.numpy()[cls0:cls0 + self.C + 2].copy().view(np.float32)[self.C]))
+            predicted.append(int(rec.pin.numpy()[rec.at.cls].copy().view(np.float32)[self.C]))
         return score_pass(tables, labs, predicted, self.C)
 
     def _truth_to_device(self, t, main):

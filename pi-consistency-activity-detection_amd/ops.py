@@ -653,12 +653,7 @@ def detect_frames(logits, starts, F, H, W, h0, w0, f_skip=2, row0=0, mask=None, 
     """pc_detect_frames: logits contiguous float32 device [n,8,S,S] (any shape with those elements; S from the last dim), the eval forward's
     output for the n <= 32 clips of one video cut at `starts`.  -> (mask uint8 [F,H,W] or None, rec int32 [F,8]); given tensors are written
     in place -- only the frames the clips address -- fresh ones are zero-filled first.  want_mask=False with mask=None: records only."""
-    if logits.dtype != torch.float32 or not logits.is_contiguous():
-        raise ValueError("detect_frames: contiguous float32 logits")
-    st, n = _starts_table(starts)
-    S = int(logits.shape[-1])
-    if int(logits.shape[-2]) != S or logits.numel() < n * 8 * S * S:
-        raise ValueError("detect_frames: logits %s do not hold %d clips of 8 x %d x %d" % (tuple(logits.shape), n, S, S))
+    _tab, _V, st, n, S, _stride = _clip_logits("detect_frames", logits, None, starts, None)
     mask, rec, ws = _detect_buffers("detect_frames", logits.device, F, H, W, mask, rec, ws, want_mask, "detect_frames_ws_bytes(n, S)",
                                     detect_frames_ws_bytes(n, S))
     capi.call("pc_detect_frames", ptr(logits), int(F), int(H), int(W), int(h0), int(w0), S, st, n, int(f_skip), int(row0), ptr(mask), ptr(rec),
@@ -675,6 +670,25 @@ def _view_table(views, who):
     if not 1 <= len(rows) <= MAX_VIEWS or any(len(r) != 3 for r in rows):
         raise ValueError("%s: 1..%d views (h0, w0, flip), got %r" % (who, MAX_VIEWS, views))
     return (C.c_int32 * (3 * len(rows)))(*[x for r in rows for x in r]), len(rows)
+
+
+def _clip_logits(who, logits, views, starts, view_stride):
+    """The opening of the entries that take a forward's logits: contiguous float32 (S from the last dim) that hold view v of clip c at clip slot
+    v * view_stride + c (default stride: n = len(starts)).  views=None: the centre entry, which has no view table and one view.
+    -> (view table or None, V, starts table, n, S, view_stride)."""
+    if logits.dtype != torch.float32 or not logits.is_contiguous():
+        raise ValueError("%s: contiguous float32 logits" % who)
+    tab, V = (None, 1) if views is None else _view_table(views, who)
+    st, n = _starts_table(starts)
+    S = int(logits.shape[-1])
+    stride = n if view_stride is None else int(view_stride)
+    if stride < n:
+        raise ValueError("%s: view_stride = %d below the %d clips" % (who, stride, n))
+    if int(logits.shape[-2]) != S or logits.numel() < ((V - 1) * stride + n) * 8 * S * S:
+        if views is None:
+            raise ValueError("%s: logits %s do not hold %d clips of 8 x %d x %d" % (who, tuple(logits.shape), n, S, S))
+        raise ValueError("%s: logits %s do not hold %d views of %d clips of 8 x %d x %d at stride %d" % (who, tuple(logits.shape), V, n, S, S, stride))
+    return tab, V, st, n, S, stride
 
 
 def clips_from_u8_views(video, views, S, starts, f_skip=2, view_stride=None, out=None):
@@ -703,16 +717,7 @@ def detect_frames_views(logits, views, starts, F, H, W, f_skip=2, view_stride=No
     """pc_detect_frames_views: detect_frames with the views (h0, w0, flip) of every clip merged per full-frame pixel.  logits contiguous float32
     device (S from the last dim), view v of clip c at clip slot v * view_stride + c (default stride: n = len(starts)).
     -> (mask uint8 [F,H,W] or None, rec int32 [F,8]) as detect_frames; rec[:, 6] = row0 + c * V."""
-    if logits.dtype != torch.float32 or not logits.is_contiguous():
-        raise ValueError("detect_frames_views: contiguous float32 logits")
-    tab, V = _view_table(views, "detect_frames_views")
-    st, n = _starts_table(starts)
-    S = int(logits.shape[-1])
-    stride = n if view_stride is None else int(view_stride)
-    if stride < n:
-        raise ValueError("detect_frames_views: view_stride = %d below the %d clips" % (stride, n))
-    if int(logits.shape[-2]) != S or logits.numel() < ((V - 1) * stride + n) * 8 * S * S:
-        raise ValueError("detect_frames_views: logits %s do not hold %d views of %d clips of 8 x %d x %d at stride %d" % (tuple(logits.shape), V, n, S, S, stride))
+    tab, V, st, n, S, stride = _clip_logits("detect_frames_views", logits, views, starts, view_stride)
     mask, rec, ws = _detect_buffers("detect_frames_views", logits.device, F, H, W, mask, rec, ws, want_mask, "detect_frames_views_ws_bytes(n, H, W)",
                                     detect_frames_views_ws_bytes(n, H, W))
     capi.call("pc_detect_frames_views", ptr(logits), int(F), int(H), int(W), S, tab, V, stride, st, n, int(f_skip), int(row0), ptr(mask), ptr(rec),
@@ -740,6 +745,15 @@ def resample_tables(Hs, Ws, H, W, device):
     return tab
 
 
+def _native_buffers(who, dev, F, H, W, Hs, Ws, mask, prob, rec, ws, want_mask, ws_call, need):
+    """What the entries that detect at native size from an Hs x Ws plane write and read besides it: _detect_buffers, a given prob checked,
+    the tables on the device.  -> mask, prob, rec, ws, dev_tab."""
+    mask, rec, ws = _detect_buffers(who, dev, F, H, W, mask, rec, ws, want_mask, ws_call, need)
+    if prob is not None:
+        prob = _prob_tensor(who, prob, F, H, W, dev)
+    return mask, prob, rec, ws, resample_tables(Hs, Ws, H, W, dev)
+
+
 def detect_frames_scaled_ws_bytes(n, Hs, Ws, H, W):
     return int(capi.lib().pc_detect_frames_scaled_ws_bytes(int(n), int(Hs), int(Ws), int(H), int(W)))
 
@@ -750,25 +764,13 @@ def detect_frames_scaled(logits, views, starts, F, H, W, Hs, Ws, f_skip=2, view_
     resampled bilinearly to every pixel of the native H x W frame in front of the threshold, the box, the score and the probability.
     -> (mask uint8 [F,H,W] or None, rec int32 [F,8]) as detect_frames_views, in native coordinates; prob: a 16-bit integer device tensor
     [F,H,W] the same launch fills as frame_probs would (only the frames the clips address), or None for none."""
-    if logits.dtype != torch.float32 or not logits.is_contiguous():
-        raise ValueError("detect_frames_scaled: contiguous float32 logits")
-    tab, V = _view_table(views, "detect_frames_scaled")
-    st, n = _starts_table(starts)
-    S = int(logits.shape[-1])
-    stride = n if view_stride is None else int(view_stride)
-    if stride < n:
-        raise ValueError("detect_frames_scaled: view_stride = %d below the %d clips" % (stride, n))
-    if int(logits.shape[-2]) != S or logits.numel() < ((V - 1) * stride + n) * 8 * S * S:
-        raise ValueError("detect_frames_scaled: logits %s do not hold %d views of %d clips of 8 x %d x %d at stride %d" % (tuple(logits.shape), V, n, S, S, stride))
+    tab, V, st, n, S, stride = _clip_logits("detect_frames_scaled", logits, views, starts, view_stride)
     F, H, W, Hs, Ws = int(F), int(H), int(W), int(Hs), int(Ws)
     need = detect_frames_scaled_ws_bytes(n, Hs, Ws, H, W)
     if need < 0:
         raise ValueError("detect_frames_scaled: %d clips, working frame %d x %d, native frame %d x %d" % (n, Hs, Ws, H, W))
-    mask, rec, ws = _detect_buffers("detect_frames_scaled", logits.device, F, H, W, mask, rec, ws, want_mask,
-                                    "detect_frames_scaled_ws_bytes(n, Hs, Ws, H, W)", need)
-    if prob is not None:
-        prob = _prob_tensor("detect_frames_scaled", prob, F, H, W, logits.device)
-    dev_tab = resample_tables(Hs, Ws, H, W, logits.device)
+    mask, prob, rec, ws, dev_tab = _native_buffers("detect_frames_scaled", logits.device, F, H, W, Hs, Ws, mask, prob, rec, ws, want_mask,
+                                                   "detect_frames_scaled_ws_bytes(n, Hs, Ws, H, W)", need)
     capi.call("pc_detect_frames_scaled", ptr(logits), F, H, W, Hs, Ws, S, tab, V, stride, st, n, int(f_skip), int(row0), ptr(dev_tab), ptr(mask),
               ptr(prob), ptr(rec), ptr(ws), stream())
     return mask, rec
@@ -804,7 +806,7 @@ def clip_plane_views(planes, F, Hs, Ws, f_skip, hop):
         raise ValueError("clip_planes: %d frames of %d x %d, f_skip = %d, hop = %d" % (F, Hs, Ws, f_skip, hop))
     if planes.dtype != torch.uint8 or not planes.is_contiguous() or planes.numel() < need:
         raise ValueError("clip_planes: planes must be a contiguous uint8 device tensor of clip_planes_bytes(F, Hs, Ws, f_skip, hop) = %d bytes" % need)
-    ps = (int(Hs) * int(Ws) + 3) // 4 * 4
+    ps = clip_planes_bytes(1, Hs, Ws, 1, 8) // 5                    # the library's own stride: one frame in one slot is 4 * ps + ps bytes
     M = (need - ps) // (4 * int(F) * ps)
     return planes[:need - ps].view(torch.float32).view(M, int(F), ps), planes[need - ps:need]
 
@@ -814,16 +816,7 @@ def clip_planes(logits, views, starts, F, Hs, Ws, f_skip, hop, view_stride=None,
     device tensor of clip_planes_bytes(F, Hs, Ws, f_skip, hop): frame k of clip c as the merged logits of the Hs x Ws frame in slot
     (starts[c] / hop) % M of frame starts[c] + k * f_skip.  cover=True: the launch also writes the cover bytes (a video's first launch).  A
     given buffer is written in place -- only the (slot, frame) pairs the clips address; a fresh one is NOT filled."""
-    if logits.dtype != torch.float32 or not logits.is_contiguous():
-        raise ValueError("clip_planes: contiguous float32 logits")
-    tab, V = _view_table(views, "clip_planes")
-    st, n = _starts_table(starts)
-    S = int(logits.shape[-1])
-    stride = n if view_stride is None else int(view_stride)
-    if stride < n:
-        raise ValueError("clip_planes: view_stride = %d below the %d clips" % (stride, n))
-    if int(logits.shape[-2]) != S or logits.numel() < ((V - 1) * stride + n) * 8 * S * S:
-        raise ValueError("clip_planes: logits %s do not hold %d views of %d clips of 8 x %d x %d at stride %d" % (tuple(logits.shape), V, n, S, S, stride))
+    tab, V, st, n, S, stride = _clip_logits("clip_planes", logits, views, starts, view_stride)
     F, Hs, Ws, f_skip, hop = int(F), int(Hs), int(Ws), int(f_skip), int(hop)
     need = clip_planes_bytes(F, Hs, Ws, f_skip, hop)
     if need < 0:
@@ -852,11 +845,8 @@ def detect_frames_planes(planes, F, H, W, Hs, Ws, V, f_skip, hop, f0=0, nf=None,
     need = detect_frames_planes_ws_bytes(nf, H, W)
     if need < 0 or f0 < 0 or f0 + nf > F:
         raise ValueError("detect_frames_planes: frames %d .. %d + %d of %d (a range holds 1..%d), native frame %d x %d" % (f0, f0, nf, F, PLANES_MAX_FRAMES, H, W))
-    mask, rec, ws = _detect_buffers("detect_frames_planes", planes.device, F, H, W, mask, rec, ws, want_mask, "detect_frames_planes_ws_bytes(nf, H, W)",
-                                    need)
-    if prob is not None:
-        prob = _prob_tensor("detect_frames_planes", prob, F, H, W, planes.device)
-    dev_tab = resample_tables(Hs, Ws, H, W, planes.device)
+    mask, prob, rec, ws, dev_tab = _native_buffers("detect_frames_planes", planes.device, F, H, W, Hs, Ws, mask, prob, rec, ws, want_mask,
+                                                   "detect_frames_planes_ws_bytes(nf, H, W)", need)
     capi.call("pc_detect_frames_planes", ptr(plane), ptr(cov), F, H, W, Hs, Ws, int(V), int(f_skip), int(hop), f0, nf, int(row0), ptr(dev_tab), ptr(mask),
               ptr(prob), ptr(rec), ptr(ws), stream())
     return mask, rec
@@ -924,16 +914,7 @@ def frame_probs(logits, views, starts, F, H, W, f_skip=2, view_stride=None, prob
     """pc_frame_probs: the logits, views and starts of detect_frames_views (the centre crop: the one view (h0, w0, 0)) -> prob, 16-bit integer
     device [F,H,W]: round(65535 * sigmoid(merged logit)) as uint16, 0 where no view covers the pixel.  A given tensor is written in place
     -- only the frames the clips address -- a fresh one is zero-filled first."""
-    if logits.dtype != torch.float32 or not logits.is_contiguous():
-        raise ValueError("frame_probs: contiguous float32 logits")
-    tab, V = _view_table(views, "frame_probs")
-    st, n = _starts_table(starts)
-    S = int(logits.shape[-1])
-    stride = n if view_stride is None else int(view_stride)
-    if stride < n:
-        raise ValueError("frame_probs: view_stride = %d below the %d clips" % (stride, n))
-    if int(logits.shape[-2]) != S or logits.numel() < ((V - 1) * stride + n) * 8 * S * S:
-        raise ValueError("frame_probs: logits %s do not hold %d views of %d clips of 8 x %d x %d at stride %d" % (tuple(logits.shape), V, n, S, S, stride))
+    tab, V, st, n, S, stride = _clip_logits("frame_probs", logits, views, starts, view_stride)
     prob = _prob_tensor("frame_probs", prob, int(F), int(H), int(W), logits.device)
     capi.call("pc_frame_probs", ptr(logits), int(F), int(H), int(W), S, tab, V, stride, st, n, int(f_skip), ptr(prob), stream())
     return prob

@@ -105,6 +105,34 @@ def test_the_clips_of_an_unlabelled_video_cover_every_frame_exactly_once(F):
     assert len(starts) == len([i + j for i in range(0, F, 16) for j in (0, 1) if i + j < F])
 
 
+def test_collect_launches_are_the_slices_every_route_cut_for_itself():
+    """detect.collect_launches against the four formula sets DetectEngine._collect held, one per route (hop, working frame, views, centre crop
+    with V = 1), written out as they stood.  n up to 70: three launches, where the engine's tests (bs <= 32) reach only the first."""
+    per = 8 * 8 * 8
+    for n in range(1, 71):
+        for V in (1, 2, 3, 4):
+            for slot, first, row0 in ((0, 0, 0), (3, 0, 7), (0, 5, 0), (11, 40, 129), (64, 33, 250)):
+                hop, work, views, centre = [], [], [], []
+                for q in range(0, n, 32):
+                    k = min(32, n - q)
+                    hop.append(((slot + q) * per, (slot + q + (V - 1) * n + k) * per, first + q, first + q + k, first + q == 0))
+                for q in range(0, n, 32):
+                    k = min(32, n - q)
+                    work.append(((slot + q) * per, (slot + q + (V - 1) * n + k) * per, first + q, first + q + k, row0 + (first + q) * V))
+                for q in range(0, n, 32):
+                    k = min(32, n - q)
+                    views.append(((slot + q) * per, (slot + q + (V - 1) * n + k) * per, first + q, first + q + k, row0 + (first + q) * V))
+                for q in range(0, n, 32):
+                    k = min(32, n - q)
+                    centre.append(((slot + q) * per, (slot + q + k) * per, first + q, first + q + k, row0 + first + q))
+                got = detect.collect_launches(n, V, slot, first, row0, per)
+                assert len(got) == (n + 31) // 32 and all(s1 - s0 <= 32 for _lo, _hi, s0, s1, _row in got)
+                assert got == work == views, (n, V, slot, first, row0)
+                assert [g[:4] + (g[2] == 0,) for g in got] == hop, (n, V, slot, first, row0)          # cover: with the video's first clip
+                if V == 1:
+                    assert got == centre, (n, slot, first, row0)
+
+
 def _refusals(lib):
     """(entry, argument order, good arguments, [(key, bad value, word of the message)])."""
     vp = C.c_void_p
