@@ -70,7 +70,8 @@ typedef void* pc_stream;            /* hipStream_t */
  * PC_INST_* constants, pc_frame_probs / pc_instance_scores with PC_PROB_ONE / PC_SCORE_WORDS, pc_instance_overlaps with PC_LINK_MAX_LAGS, pc_mask_run_ws_bytes /
  * pc_mask_run_index / pc_mask_runs with PC_RUN_WORDS, pc_map_crosstab / pc_map_crosstab_ws_bytes with PC_CROSS_MAX_SLOTS, and pc_resample_tables / pc_detect_frames_scaled_ws_bytes /
  * pc_detect_frames_scaled, and pc_clip_hop_starts / pc_clip_planes_bytes / pc_clip_planes / pc_detect_frames_planes_ws_bytes /
- * pc_detect_frames_planes with PC_PLANES_MAX_FRAMES: came later, move nothing).  Descriptors must be zero-initialised by the caller:
+ * pc_detect_frames_planes with PC_PLANES_MAX_FRAMES, and pc_prob_truth_hist_ws_bytes / pc_prob_truth_hist with PC_SWEEP_MAX_THRESHOLDS: came
+ * later, move nothing).  Descriptors must be zero-initialised by the caller:
  * fields added later read as "old behaviour" when 0.  pc_version() returns the value the library was built with; the Python host
  * (capi.lib()) refuses a library whose version differs from the header it mirrors. */
 #define PC_VERSION 107
@@ -551,6 +552,27 @@ int     pc_mask_runs(const uint8_t* map, int F, int H, int W, int f0, int nf, co
 int     pc_map_crosstab(const uint8_t* pred, const uint8_t* truth, int F, int H, int W, int f0, int nf, int P, int A, int32_t* out, void* ws,
                         pc_stream s);
 int64_t pc_map_crosstab_ws_bytes(int nf, int H, int W, int P, int A);
+/* The probability map of a pass against a truth map at every mask threshold at once (csrc/probhist.hip; picons_amd/detect.py:
+ * DetectEngine.sweep).  prob uint16 [F][H][W] as pc_frame_probs, pc_detect_frames_scaled and pc_detect_frames_planes leave it (a frame may
+ * start at any 2-byte address), truth uint8 [F][H][W] (any byte address; ANY non-zero byte is truth, as in pc_map_crosstab); frame offsets are
+ * 64-bit.  thr: N HOST words, strictly ascending, each in 1..PC_PROB_ONE; they are read before the call returns and travel in the kernel
+ * arguments, so the caller may free them at once.  With q a pixel's probability word and b the number of k with thr[k] <= q, the pixel is
+ * positive at threshold k (q >= thr[k]) exactly if b > k.
+ * pc_prob_truth_hist writes, for each of the frames f0 .. f0 + nf - 1 and no others, EVERY cell of `out` int32 [F][2][N + 1]: out[f][t][b] =
+ * the pixels of frame f whose truth byte is zero (t = 0) or not (t = 1) and for which exactly b of the thresholds are <= q, cell [0][0]
+ * included, so the cells of a frame sum to H * W.  Nothing has to be zeroed in front of the call; the prior contents of out and ws are
+ * irrelevant.  ws: pc_prob_truth_hist_ws_bytes(nf, H, W, N) bytes, 8-byte aligned, meaningless after the call.  Two launches, as
+ * pc_map_crosstab: bpf blocks per frame (a function of H * W alone, at most 64) leave one partial table each in ws, then one block per frame
+ * adds them in block order and writes [0][0] as H * W minus the rest -- a pixel without truth below thr[0] costs no LDS traffic.  Integer LDS
+ * atomics only (per-wave bins, folded at the end), no global atomics, no floating point, nothing waits on another block: bit-identical from
+ * run to run.  pc_prob_truth_hist_ws_bytes is host arithmetic: -1 for nf, H or W < 1, H * W >= 2^31, N outside
+ * 1..PC_SWEEP_MAX_THRESHOLDS.  Refusals of the call (PC_E_ARG before any HIP call): null prob, truth, thr, out or ws; F, H, W < 1;
+ * H * W >= 2^31; f0 < 0, nf < 1, f0 + nf > F; N outside 1..PC_SWEEP_MAX_THRESHOLDS; a threshold word of 0; thresholds not strictly ascending;
+ * prob not 2-byte, out not 4-byte, ws not 8-byte aligned. */
+#define PC_SWEEP_MAX_THRESHOLDS 64
+int64_t pc_prob_truth_hist_ws_bytes(int nf, int H, int W, int N);
+int     pc_prob_truth_hist(const uint16_t* prob, const uint8_t* truth, int F, int H, int W, int f0, int nf, const uint16_t* thr, int N,
+                           int32_t* out, void* ws, pc_stream s);
 /* Detection on a resized working frame, results at native size (csrc/detectscale.hip; picons_amd/detect.py: DetectEngine.set_working_frame).
  * The views are crops of an Hs x Ws WORKING frame; mask, box, score and probability stand on the H x W NATIVE frame.
  * pc_resample_tables is HOST arithmetic with pc_resize_tables' call shape: it returns the word count 2 * (H + W) and writes `tab` if `cap`

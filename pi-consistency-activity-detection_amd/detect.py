@@ -47,6 +47,12 @@ every video is resized on the device to Hs x Ws (pc_resize_u8: cv2.resize restat
 pc_detect_frames_scaled merges them there and resamples the merged logits bilinearly to every native pixel in front of the threshold, the
 box, the score and the probability -- masks, records, instances, runs and score() stand in native coordinates at native size as before.
 
+Sweep.  The mask is cut at sigmoid(x) >= 0.5; whether that is the right operating point is what DetectEngine.sweep(truths, labels,
+thresholds), called after results(), answers from the probability maps of a pass (set_keep_probs, or instance_scores=True): one
+pc_prob_truth_hist launch per video counts its pixels by (truth or not, how many of the N threshold words lie at or below the probability
+word), all histograms leave in one copy -- one host wait per call -- and the host turns their suffix sums into the (inter, union, gt) of every
+threshold (sweep_counts) and those into f-mAP / v-mAP per threshold through the evaluator's own accumulate_video, in a SweepScore.
+
 Clip hop.  A video is cut into windows of 8 * f_skip frames that start every 8 * f_skip frames, so every frame is decided by one forward,
 unless DetectEngine.set_clip_hop(hop) is called: then the windows start every `hop` frames (clip_starts_hop), a frame lies in up to
 ceil(8 * f_skip / hop) of them, pc_clip_planes keeps the merged logits of every (window, frame) on the device until the video's last clip has
@@ -481,6 +487,102 @@ def score_pass(tables, labels, predicted, n_classes):
     return PassScore(acc.result(), videos)
 
 
+# ---------------------------------------------------------------------- a pass against truth at every mask threshold (tests/test_detect_sweep_cpu.py)
+DEFAULT_SWEEP = tuple(k / 20.0 for k in range(1, 20))               # 0.05, 0.10 .. 0.95
+
+
+def threshold_words(thresholds=None):
+    """Mask thresholds t in (0, 1] (default: DEFAULT_SWEEP) -> words np.uint16 [N]: word = ceil(t * 65535), the product and its ceiling in
+    float64; the mask at t is q >= word.  0.5 gives 32768, the word of a logit of +-0.0: the mask of that word is seg_positive's on every
+    finite logit (include/picons.h, pc_frame_probs; csrc/evalpred.h).  The thresholds must ascend strictly and be at most
+    ops.SWEEP_MAX_THRESHOLDS; ValueError for a t outside (0, 1], a NaN, too many, none, or two thresholds with one word."""
+    try:
+        t = np.asarray(DEFAULT_SWEEP if thresholds is None else thresholds, dtype=np.float64)
+    except (TypeError, ValueError):
+        raise ValueError("threshold_words: thresholds = %r are not numbers" % (thresholds,)) from None
+    if t.ndim != 1 or not 1 <= t.size <= ops.SWEEP_MAX_THRESHOLDS:
+        raise ValueError("threshold_words: 1..%d thresholds in one dimension, got shape %s" % (ops.SWEEP_MAX_THRESHOLDS, t.shape))
+    if not (np.isfinite(t) & (t > 0.0) & (t <= 1.0)).all():
+        raise ValueError("threshold_words: thresholds %s outside (0, 1]" % (t.tolist(),))
+    words = np.ceil(t * float(ops.PROB_ONE)).astype(np.int64)
+    if (np.diff(words) <= 0).any():
+        raise ValueError("threshold_words: thresholds %s must ascend strictly and differ by at least one word of 1 / 65535 (words %s)"
+                         % (t.tolist(), words.tolist()))
+    return words.astype(np.uint16)
+
+
+def sweep_counts(hist):
+    """Histograms int32 [F, 2, N + 1] of pc_prob_truth_hist -> int64 [N, F, 3]: per threshold k the (inter, union, gt) of crosstab_counts for
+    the mask q >= word k.  A pixel is positive at k exactly if more than k words are at or below it, so inter_k = sum(hist[f, 1, k + 1:]),
+    gt = sum(hist[f, 1, :]), union_k = gt + sum(hist[f, 0, k + 1:])."""
+    h = np.asarray(hist).astype(np.int64)
+    if h.ndim != 3 or h.shape[1] != 2 or h.shape[2] < 2:
+        raise ValueError("sweep_counts: histograms [F, 2, N + 1], got %s" % (h.shape,))
+    above = np.cumsum(h[:, :, ::-1], axis=2)[:, :, ::-1]               # above[f, t, b] = sum(h[f, t, b:])
+    out = np.empty((h.shape[2] - 1, h.shape[0], 3), np.int64)
+    out[:, :, 0] = above[:, 1, 1:].T
+    out[:, :, 2] = above[:, 1, 0][None, :]
+    out[:, :, 1] = out[:, :, 2] + above[:, 0, 1:].T
+    return out
+
+
+class SweepScore:
+    """A pass against truth at N mask thresholds.  thresholds float64 [N] and words uint16 [N] (threshold_words); results: per threshold the
+    dict of evalmetrics.MapAccumulator.result() -- PassScore.result, had the masks been cut at that word; fmAP / vmAP float64 [N, 20]: their
+    rows, one column per IoU threshold 0, 0.05 .. 0.95; pixel int64 [N, 3] = (tp, fp, fn) over every frame of every scored video; videos: the
+    histogram int32 [F, 2, N + 1] of every video of the call in order, skipped ones included; n_skipped: how many held no truth."""
+
+    def __init__(self, thresholds, words, results, pixel, videos, n_skipped):
+        self.thresholds, self.words = np.asarray(thresholds, np.float64), np.asarray(words, np.uint16)
+        self.results, self.videos, self.n_skipped = list(results), list(videos), int(n_skipped)
+        self.fmAP = np.array([r["fmAP"] for r in self.results], np.float64).reshape(len(self.results), -1)
+        self.vmAP = np.array([r["vmAP"] for r in self.results], np.float64).reshape(len(self.results), -1)
+        self.pixel = np.asarray(pixel, np.int64).reshape(len(self.results), 3)
+
+    def best(self, metric="fmAP", iou=0.5):
+        """The index of the first threshold at which `metric` ("fmAP" or "vmAP") at the IoU threshold `iou` (a multiple of 0.05 in
+        [0, 0.95]) is largest; NaN (no scored video of some class) is ignored, ValueError if every value is NaN."""
+        if metric not in ("fmAP", "vmAP"):
+            raise ValueError("best: metric = %r, \"fmAP\" or \"vmAP\"" % (metric,))
+        try:
+            col = int(round(float(iou) * 20.0))
+        except (TypeError, ValueError):
+            raise ValueError("best: iou = %r is not a number" % (iou,)) from None
+        if not 0 <= col < evalmetrics.N_THR or abs(float(iou) * 20.0 - col) > 1e-9:
+            raise ValueError("best: iou = %r, a multiple of 0.05 in [0, 0.95]" % (iou,))
+        v = getattr(self, metric)[:, col]
+        if v.size == 0 or np.isnan(v).all():
+            raise ValueError("best: %s at IoU %.2f is NaN at every threshold" % (metric, col / 20.0))
+        return int(np.nanargmax(v))
+
+
+def sweep_pass(hists, labels, predicted, n_classes, words, thresholds=None):
+    """The host side of DetectEngine.sweep: per-video histograms [F, 2, N + 1], true and predicted classes, the N words they were split by
+    (and the thresholds behind them: words / 65535 when None) -> SweepScore.  Threshold k's counts of every video go through accumulate_video
+    into a MapAccumulator of its own; a video without a truth pixel enters none of them, as in score_pass."""
+    words = np.asarray(words).reshape(-1)
+    N = int(words.size)
+    hists = [np.asarray(h) for h in hists]
+    counts = [sweep_counts(h) for h in hists]
+    for c in counts:
+        if c.shape[0] != N:
+            raise ValueError("sweep_pass: a histogram of %d thresholds for %d words" % (c.shape[0], N))
+    accs = [evalmetrics.MapAccumulator(n_classes, device="cpu") for _ in range(N)]
+    pixel = np.zeros((N, 3), np.int64)
+    n_skipped = 0
+    for c, label, pred in zip(counts, labels, predicted):
+        if not (c[0, :, 2] != 0).any():                               # gt is the same at every threshold
+            n_skipped += 1
+            continue
+        for k in range(N):
+            accumulate_video(c[k], label, accs[k])
+            accs[k].n_correct += int(int(label) == int(pred))
+        inter, union, gt = (c[:, :, j].sum(axis=1) for j in range(3))
+        pixel += np.stack([inter, union - gt, gt - inter], axis=1)    # pred = inter + fp, union = gt + fp
+    t = words.astype(np.float64) / float(ops.PROB_ONE) if thresholds is None else thresholds
+    return SweepScore(t, words, [a.result() for a in accs], pixel, hists, n_skipped)
+
+
 def check_instances(instances, min_area, conn, masks):
     """The instance arguments of DetectEngine -> (K, min_area, conn) as ints, or ValueError."""
     K, min_area, conn = int(instances), int(min_area), int(conn)
@@ -572,7 +674,10 @@ class DetectEngine(ClipEngine):
     detected at native size through pc_detect_frames_scaled (below).
 
     set_clip_hop(hop): videos added from then on are cut into overlapping windows that start every `hop` frames and every frame is
-    detected from the mean of the windows that hold it (below)."""
+    detected from the mean of the windows that hold it (below).
+
+    set_keep_probs(True): videos added from then on keep their probability map (Detection.probs) without instances; sweep(truths, labels)
+    then scores the pass at every mask threshold from one histogram launch per video (below)."""
 
     hop = None                           # set_clip_hop: the distance between two windows for the videos to come, None for today's cut
     ws_planes = None                     # pc_detect_frames_planes' partials, grown only for a larger frame
@@ -610,6 +715,8 @@ class DetectEngine(ClipEngine):
         # score: two page-locked slots the truths go up through (as up_pin), the tables' staging and the kernel's workspace; all made by the first call
         self.tr_pin, self.tr_done, self.tr_slot = [None, None], [None, None], 0
         self.score_pin = self.score_ws = None
+        self.keep_probs = False              # set_keep_probs: the probability map of the videos to come without instance scores
+        self.sweep_pin = self.sweep_ws = None        # sweep: the histograms' staging and the kernel's workspace, made by the first call
         self._clear()
 
     def _clear(self):
@@ -673,6 +780,16 @@ class DetectEngine(ClipEngine):
         if hop % self.f_skip or not self.f_skip <= hop <= span:
             raise ValueError("set_clip_hop: hop = %d, a multiple of f_skip = %d in [%d, %d]" % (hop, self.f_skip, self.f_skip, span))
         self.hop = None if hop == span else hop
+
+    def set_keep_probs(self, keep=True):
+        """keep=True: every video added from now on keeps its per-pixel probability map on the device (Detection.probs, 16-bit [F,H,W] in
+        steps of 1 / 65535) whether or not the engine reduces it per instance: one pc_frame_probs launch behind each pc_detect_frames /
+        pc_detect_frames_views, the prob operand of pc_detect_frames_scaled / pc_detect_frames_planes -- what instance_scores=True keeps
+        already, without instances -- and with it sweep().  keep=False: only what instance_scores asks for, today's launches.  A bool
+        only: ValueError for anything else; nothing changes then."""
+        if not isinstance(keep, (bool, np.bool_)):
+            raise ValueError("set_keep_probs: keep = %r, True or False" % (keep,))
+        self.keep_probs = bool(keep)
 
     def _frame(self, H, W):
         """The frame the views of an H x W video are cut from: the working frame if one is set, else its own."""
@@ -743,7 +860,7 @@ class DetectEngine(ClipEngine):
         rec.dev = torch.empty(rec.at.words, dtype=torch.int32, device=self.dev)
         rec.mask = torch.empty(F, H, W, dtype=torch.uint8, device=self.dev) if self.masks else None
         rec.imap = torch.empty(F, H, W, dtype=torch.uint8, device=self.dev) if self.instance_maps or self.instance_scores or self.instance_links else None
-        rec.prob = torch.empty(F, H, W, dtype=torch.int16, device=self.dev) if self.instance_scores else None
+        rec.prob = torch.empty(F, H, W, dtype=torch.int16, device=self.dev) if self.instance_scores or self.keep_probs else None
         rec.pin = None
         rec.hop, rec.planes = self.hop, None
         if rec.hop:
@@ -816,7 +933,7 @@ class DetectEngine(ClipEngine):
         if self.inst_k:
             ops.frame_instances(rec.mask, conn=self.conn, min_area=self.min_area, K=self.inst_k, inst=rec.dev[at.inst].view(rec.F, -1), imap=rec.imap,
                                 want_imap=False)
-            if rec.prob is not None:
+            if self.instance_scores:
                 ops.instance_scores(rec.imap, rec.prob, self.inst_k, out=rec.dev[at.score].view(rec.F, -1))
             if self.instance_links:
                 ops.instance_overlaps(rec.imap, self.inst_k, self.instance_links, out=rec.dev[at.link])
@@ -991,6 +1108,62 @@ class DetectEngine(ClipEngine):
         for rec, _t, _w0 in jobs:
             predicted.append(int(rec.pin.numpy()[rec.at.cls].copy().view(np.float32)[self.C]))
         return score_pass(tables, labs, predicted, self.C)
+
+    def sweep(self, truths, labels, thresholds=None, videos=None):
+        """The last pass against truth masks at every mask threshold of `thresholds` (floats in (0, 1], ascending; default 0.05, 0.10 ..
+        0.95: threshold_words) -> SweepScore: what score() would give had the masks been cut at each of them, from the probability maps the
+        pass kept (set_keep_probs, or instance_scores=True).  truths, labels and videos as in score().  Called after results(); it changes
+        nothing results() returned and can be called again.  Per video one upload of its truth (score()'s staging) and one
+        pc_prob_truth_hist launch into its part of one buffer; all histograms leave in one asynchronous copy and the call has ONE wait on the
+        compute stream, after which the host does the rest (sweep_pass).  Every refusal is a ValueError before anything is enqueued."""
+        if not self.videos or any(rec.pin is None for rec in self.videos):
+            raise ValueError("sweep: no finished pass (call it after results())")
+        t = np.asarray(DEFAULT_SWEEP, np.float64) if thresholds is None else thresholds
+        words = threshold_words(t)
+        t = np.asarray(t, np.float64)
+        N = int(words.size)
+        picks = self._picks("sweep", videos)
+        truths, labels = list(truths), list(labels)
+        if not (len(truths) == len(labels) == len(picks)):
+            raise ValueError("sweep: %d truths and %d labels for %d videos" % (len(truths), len(labels), len(picks)))
+        jobs, labs, total, ws_need = [], [], 0, 0                       # (record, truth, first word of its histograms)
+        for v, truth, label in zip(picks, truths, labels):
+            rec = self.videos[v]
+            if rec.prob is None:
+                raise ValueError("sweep: video %d keeps no probability map (set_keep_probs(True) before it is added, or instance_scores=True)" % v)
+            tr = _as_u8(truth, "sweep: truth of video %d" % v)
+            if tr.dim() == 4 and tr.shape[3] == 1:
+                tr = tr.reshape(tr.shape[:3])
+            if tuple(tr.shape) != (rec.F, rec.H, rec.W):
+                raise ValueError("sweep: truth of video %d has shape %s, expected (%d, %d, %d) or (%d, %d, %d, 1)"
+                                 % (v, tuple(truth.shape), rec.F, rec.H, rec.W, rec.F, rec.H, rec.W))
+            try:
+                lab = int(label)
+            except (TypeError, ValueError):
+                raise ValueError("sweep: label %r is not a class id" % (label,)) from None
+            if lab != label or not 0 <= lab < self.C:
+                raise ValueError("sweep: label %r outside [0, %d)" % (label, self.C))
+            jobs.append((rec, tr, total))
+            labs.append(lab)
+            total += rec.F * 2 * (N + 1)
+            ws_need = max(ws_need, ops.prob_truth_hist_ws_bytes(rec.F, rec.H, rec.W, N))
+        if not jobs:
+            return sweep_pass([], [], [], self.C, words, t)
+        main = torch.cuda.current_stream(self.dev)
+        if self.sweep_ws is None or self.sweep_ws.numel() < ws_need:
+            self.sweep_ws = torch.empty(ws_need, dtype=torch.uint8, device=self.dev)
+        tab_dev = torch.empty(total, dtype=torch.int32, device=self.dev)
+        for rec, tr, w0 in jobs:
+            ops.prob_truth_hist(rec.prob, self._truth_to_device(tr, main), words, out=tab_dev[w0:w0 + rec.F * 2 * (N + 1)].view(rec.F, 2, N + 1),
+                                ws=self.sweep_ws)
+        if self.sweep_pin is None or self.sweep_pin.numel() < total:
+            self.sweep_pin = torch.empty(max(total, 1024), dtype=torch.int32).pin_memory()
+        self.sweep_pin[:total].copy_(tab_dev, non_blocking=True)
+        main.synchronize()                                           # the call's one wait on the compute stream
+        host = self.sweep_pin[:total].numpy()
+        hists = [ops.decode_prob_truth_hist(host[w0:w0 + rec.F * 2 * (N + 1)], N) for rec, _tr, w0 in jobs]      # copies: the staging is used again
+        predicted = [int(rec.pin.numpy()[rec.at.cls].copy().view(np.float32)[self.C]) for rec, _tr, _w0 in jobs]
+        return sweep_pass(hists, labs, predicted, self.C, words, t)
 
     def _truth_to_device(self, t, main):
         """A truth [F,H,W] on the device, contiguous, ordered in front of what `main` runs next.  A host truth goes through one of two

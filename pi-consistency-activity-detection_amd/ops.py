@@ -1105,6 +1105,70 @@ def decode_map_crosstab(words, P, A):
     return r.reshape(-1, P + 2, A + 2).copy()
 
 
+SWEEP_MAX_THRESHOLDS = 64                  # PC_SWEEP_MAX_THRESHOLDS of include/picons.h: the threshold words one histogram is split by
+
+
+def _sweep_words(who, words):
+    """Threshold words -> contiguous np.uint16 [N]: 1..SWEEP_MAX_THRESHOLDS integers in 1..PROB_ONE, strictly ascending, or ValueError."""
+    try:
+        w = np.asarray(words.cpu().numpy() if torch.is_tensor(words) else words)
+    except (TypeError, ValueError):
+        raise ValueError("%s: words = %r are not integers" % (who, words)) from None
+    if w.ndim != 1 or not 1 <= w.size <= SWEEP_MAX_THRESHOLDS or w.dtype.kind not in "iu":
+        raise ValueError("%s: words must be 1..%d integers in one dimension, got %s %s" % (who, SWEEP_MAX_THRESHOLDS, w.dtype, w.shape))
+    w = w.astype(np.int64)
+    if w[0] < 1 or w[-1] > PROB_ONE or (np.diff(w) <= 0).any():
+        raise ValueError("%s: words must lie in 1..%d and ascend strictly, got %s" % (who, PROB_ONE, w.tolist()))
+    return np.ascontiguousarray(w.astype(np.uint16))
+
+
+def prob_truth_hist_ws_bytes(nf, H, W, N):
+    """pc_prob_truth_hist_ws_bytes (host arithmetic): the bytes of workspace one prob_truth_hist call over nf frames of H x W takes."""
+    n = int(capi.lib().pc_prob_truth_hist_ws_bytes(int(nf), int(H), int(W), int(N)))
+    if n < 0:
+        raise ValueError("prob_truth_hist_ws_bytes: nf = %d frames of %d x %d with N = %d: nf, H, W >= 1, H * W < 2^31, N in 1..%d"
+                         % (nf, H, W, N, SWEEP_MAX_THRESHOLDS))
+    return n
+
+
+def prob_truth_hist(prob, truth, words, f0=0, nf=None, out=None, ws=None):
+    """pc_prob_truth_hist: prob a contiguous 16-bit integer device tensor [F,H,W] (frame_probs': uint16 words), truth contiguous uint8 device
+    [F,H,W], words 1..64 host integers in 1..65535, strictly ascending -> out int32 [F, 2, N + 1]: out[f, t, b] the pixels of frame f whose
+    truth byte is zero (t = 0) or not (t = 1) and whose probability word has exactly b of the words at or below it, cell [0, 0] included, for
+    the frames f0 .. f0 + nf - 1 (default: all from f0 on).  A given out is written in place -- only those frames -- a fresh one is
+    zero-filled first.  ws: uint8 device scratch of at least prob_truth_hist_ws_bytes(nf, H, W, N) bytes, made when None."""
+    if not torch.is_tensor(prob) or prob.dtype not in _PROB_DTYPES or prob.dim() != 3 or not prob.is_contiguous():
+        raise ValueError("prob_truth_hist: contiguous 16-bit integer [F,H,W] prob")
+    if not torch.is_tensor(truth) or truth.dtype != torch.uint8 or truth.dim() != 3 or not truth.is_contiguous():
+        raise ValueError("prob_truth_hist: contiguous uint8 [F,H,W] truth")
+    if prob.shape != truth.shape or prob.device != truth.device:
+        raise ValueError("prob_truth_hist: prob %s and truth %s must have one shape and lie on one device" % (tuple(prob.shape), tuple(truth.shape)))
+    F, H, W = (int(v) for v in prob.shape)
+    w = _sweep_words("prob_truth_hist", words)
+    N, f0 = int(w.size), int(f0)
+    nf = F - f0 if nf is None else int(nf)
+    if f0 < 0 or nf < 1 or f0 + nf > F:
+        raise ValueError("prob_truth_hist: frames f0 = %d, nf = %d outside the %d of the map" % (f0, nf, F))
+    if out is None:
+        out = torch.zeros(F, 2, N + 1, dtype=torch.int32, device=prob.device)
+    elif not torch.is_tensor(out) or out.dtype != torch.int32 or not out.is_contiguous() or out.numel() != F * 2 * (N + 1) or out.device != prob.device:
+        raise ValueError("prob_truth_hist: out must be a contiguous int32 device tensor [F, 2, %d]" % (N + 1))
+    need = prob_truth_hist_ws_bytes(nf, H, W, N)
+    if ws is None:
+        ws = torch.empty(need, dtype=torch.uint8, device=prob.device)
+    elif not torch.is_tensor(ws) or ws.dtype != torch.uint8 or not ws.is_contiguous() or ws.numel() < need or ws.device != prob.device:
+        raise ValueError("prob_truth_hist: ws must be a contiguous uint8 device tensor of at least %d bytes" % need)
+    capi.call("pc_prob_truth_hist", ptr(prob), ptr(truth), F, H, W, f0, nf, w.ctypes.data_as(C.c_void_p), N, ptr(out), ptr(ws), stream())
+    return out
+
+
+def decode_prob_truth_hist(words, N):
+    """Host int32 tables of F * 2 * (N + 1) words (numpy or torch, any shape) -> int32 [F, 2, N + 1]."""
+    N = int(N)
+    r = np.ascontiguousarray(words.cpu().numpy() if torch.is_tensor(words) else words, dtype=np.int32)
+    return r.reshape(-1, 2, N + 1).copy()
+
+
 def video_class(scores, out=None):
     """pc_video_class: scores contiguous float32 device [n,C] -> float32 device [C + 2]: mean class scores, arg-max (as a float), its mean."""
     if scores.dtype != torch.float32 or scores.dim() != 2 or not scores.is_contiguous():

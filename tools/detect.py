@@ -35,11 +35,17 @@ crops of the working frame; work_i int32 [3] = (Hs, Ws, cv2 interpolation flag) 
 --hop N: the clips of a video start every N frames instead of every 16 (DetectEngine.set_clip_hop: N a multiple of f_skip = 2 in 2..16), a
 frame lies in up to 16 / N of them, and mask, box, score and probability come from the mean of their merged logits; hop_i records it.  The
 class is voted over all the overlapping clips.  The effect on f-mAP / v-mAP is not measured.
+--sweep [t ...] (with --truth / --labels or --score; implies DetectEngine.set_keep_probs): the pass scored at every mask threshold t in (0, 1]
+(none given: 0.05, 0.10 .. 0.95) from one histogram of the kept probability map per video (DetectEngine.sweep: one pc_prob_truth_hist launch
+per video, one host wait).  One line per threshold: f-mAP@0.5 and v-mAP@0.5 (the mean over the classes that hold a video, as --truth prints
+them) and the pixel precision and recall over every frame of every scored video; `*` marks the first threshold with the largest printed
+f-mAP@0.5.  Stored: sweep_thresholds [N], sweep_words [N], sweep_fmAP [N, 20] and sweep_vmAP [N, 20] (the evaluator's own: NaN as soon as one
+class holds no video), sweep_pixel int64 [N, 3] = (tp, fp, fn).
 
     python tools/detect.py --out detections.npz [--ckpt best_model.pth] [--synthetic 4 | video.npy ...] [--masks] [--pack] [--tile] [--flip]
                            [--max-gap 0] [--min-pixels 1] [--instances K] [--min_area 1] [--conn 8] [--instance_maps] [--instance_scores]
                            [--instance_links L] [--link box|mask] [--mask_runs] [--truth t0.npy ... --labels l0 ... | --score]
-                           [--frame_size Hs Ws [--interp area|linear|nearest]] [--hop N]
+                           [--frame_size Hs Ws [--interp area|linear|nearest]] [--hop N] [--sweep [t ...]]
 """
 import argparse
 import os
@@ -82,11 +88,19 @@ def main():
     ap.add_argument("--frame_size", nargs=2, type=int, default=None, metavar=("Hs", "Ws"), help="resize every video to this working frame on the device; results stay at native size")
     ap.add_argument("--interp", default="area", choices=sorted(detect.INTERPOLATIONS), help="with --frame_size: cv2.resize's interpolation")
     ap.add_argument("--hop", type=int, default=None, help="cut overlapping clips that start every N frames and average the clips that hold a frame (a multiple of 2 in 2..16; 16: today's cut)")
+    ap.add_argument("--sweep", nargs="*", type=float, default=None, metavar="t", help="with --truth/--labels or --score: f-mAP / v-mAP and pixel precision / recall at every mask threshold t (default 0.05 .. 0.95) from the kept probability map")
     a = ap.parse_args()
     if (a.truth is None) != (a.labels is None) or (a.truth is not None and not (len(a.truth) == len(a.labels) == len(a.videos))):
         raise SystemExit("tools/detect.py: --truth and --labels go together, one of each per video file")
     if a.score and a.videos:
         raise SystemExit("tools/detect.py: --score is for the synthetic videos; give --truth and --labels for video files")
+    if a.sweep is not None:
+        if a.truth is None and not a.score:
+            raise SystemExit("tools/detect.py: --sweep scores against truth: give --truth and --labels, or --score with synthetic videos")
+        try:
+            detect.threshold_words(a.sweep or None)
+        except ValueError as e:
+            raise SystemExit("tools/detect.py: --sweep: %s" % e)
     if a.instance_scores and a.instances <= 0:
         raise SystemExit("tools/detect.py: --instance_scores needs --instances K with K > 0 (the scores are reduced per instance)")
     if a.instance_links and a.instances <= 0:
@@ -130,6 +144,8 @@ def main():
             engine.set_clip_hop(a.hop)
         except ValueError as e:
             raise SystemExit("tools/detect.py: --hop: %s" % e)
+    if a.sweep is not None:
+        engine.set_keep_probs(True)
     engine.begin()
     for v in videos:
         engine.add_video(v)
@@ -150,6 +166,18 @@ def main():
         out.update({"score_" + k: np.asarray(v) for k, v in r.items()})
         for i, v in enumerate(ps.videos):
             out.update({"score_table_%d" % i: v.table, "score_counts_%d" % i: v.counts, "score_label_%d" % i: np.int32(v.label)})
+    if a.sweep is not None and truths is not None:
+        sw = engine.sweep(truths, labels, a.sweep or None)
+        with np.errstate(invalid="ignore", divide="ignore"):          # printed as above: the mean over the classes that hold a video
+            fm = np.array([np.nanmean(r["frame_ious"] / r["n_tot_frames"], axis=0)[10] for r in sw.results])
+            vm = np.array([np.nanmean(r["video_ious"] / r["n_vids"], axis=0)[10] for r in sw.results])
+            tp, fp, fn = (sw.pixel[:, j].astype(np.float64) for j in range(3))
+            prec, rec = tp / (tp + fp), tp / (tp + fn)                # NaN where nothing is predicted / nothing is true
+        best = -1 if np.isnan(fm).all() else int(np.nanargmax(fm))
+        print("sweep of the mask threshold (%d videos, %d without truth):  threshold  f-mAP@0.5  v-mAP@0.5  pixel precision  pixel recall" % (len(sw.videos), sw.n_skipped))
+        for k, t in enumerate(sw.thresholds):
+            print("  %s %.4f  %.4f  %.4f  %.4f  %.4f" % ("*" if k == best else " ", t, fm[k], vm[k], prec[k], rec[k]))
+        out.update({"sweep_thresholds": sw.thresholds, "sweep_words": sw.words, "sweep_fmAP": sw.fmAP, "sweep_vmAP": sw.vmAP, "sweep_pixel": sw.pixel})
     for i, (name, d) in enumerate(zip(names, dets)):
         tubes = d.tubes(a.min_pixels, a.max_gap)
         out.update({"label_%d" % i: np.int32(d.label), "class_scores_%d" % i: d.class_scores, "counts_%d" % i: d.counts, "boxes_%d" % i: d.boxes,
