@@ -70,8 +70,8 @@ typedef void* pc_stream;            /* hipStream_t */
  * PC_INST_* constants, pc_frame_probs / pc_instance_scores with PC_PROB_ONE / PC_SCORE_WORDS, pc_instance_overlaps with PC_LINK_MAX_LAGS, pc_mask_run_ws_bytes /
  * pc_mask_run_index / pc_mask_runs with PC_RUN_WORDS, pc_map_crosstab / pc_map_crosstab_ws_bytes with PC_CROSS_MAX_SLOTS, and pc_resample_tables / pc_detect_frames_scaled_ws_bytes /
  * pc_detect_frames_scaled, and pc_clip_hop_starts / pc_clip_planes_bytes / pc_clip_planes / pc_detect_frames_planes_ws_bytes /
- * pc_detect_frames_planes with PC_PLANES_MAX_FRAMES, and pc_prob_truth_hist_ws_bytes / pc_prob_truth_hist with PC_SWEEP_MAX_THRESHOLDS: came
- * later, move nothing).  Descriptors must be zero-initialised by the caller:
+ * pc_detect_frames_planes with PC_PLANES_MAX_FRAMES, and pc_prob_truth_hist_ws_bytes / pc_prob_truth_hist with PC_SWEEP_MAX_THRESHOLDS, and
+ * pc_prob_cut_ws_bytes / pc_prob_cut: came later, move nothing).  Descriptors must be zero-initialised by the caller:
  * fields added later read as "old behaviour" when 0.  pc_version() returns the value the library was built with; the Python host
  * (capi.lib()) refuses a library whose version differs from the header it mirrors. */
 #define PC_VERSION 107
@@ -573,6 +573,24 @@ int64_t pc_map_crosstab_ws_bytes(int nf, int H, int W, int P, int A);
 int64_t pc_prob_truth_hist_ws_bytes(int nf, int H, int W, int N);
 int     pc_prob_truth_hist(const uint16_t* prob, const uint8_t* truth, int F, int H, int W, int f0, int nf, const uint16_t* thr, int N,
                            int32_t* out, void* ws, pc_stream s);
+/* The kept probability map of a pass cut at a threshold word (csrc/probcut.hip; picons_amd/detect.py: DetectEngine.set_mask_threshold /
+ * DetectEngine.recut).  prob uint16 [F][H][W] as pc_frame_probs, pc_detect_frames_scaled and pc_detect_frames_planes leave it (a frame may
+ * start at any 2-byte address); frame offsets are 64-bit.  word in 1..PC_PROB_ONE; a pixel of probability word q is positive exactly if
+ * q >= word -- pc_prob_truth_hist's rule, so a sweep and a cut cannot disagree on a pixel.
+ * pc_prob_cut writes, for each of the frames f0 .. f0 + nf - 1 and no others, the whole frame of mask uint8 [F][H][W] (1 positive, 0 not; a
+ * frame may start at any byte address; mask may be null, the records are then the same bits) and words 0..5 of the frame's record in rec
+ * int32 [F][8]: [0] the count c of positive pixels, [1..4] their half-open box x0, y0, x1, y1 in frame coordinates (all zero for c == 0),
+ * [5] the bits of the float32 score (float)((double)S / (65535.0 * (double)c)) with S the exact integer sum of q over the positive pixels
+ * (S < 2^47: exact as an integer and as a double, so the score is a function of the input alone), 0.0f for c == 0.  WORDS 6 AND 7 ARE NOT
+ * TOUCHED: they hold the frame's score row, written by the detect entry that ran first.  Nothing has to be zeroed in front of the call; the
+ * prior contents of mask, rec and ws are irrelevant.  ws: pc_prob_cut_ws_bytes(nf, H, W) bytes, 8-byte aligned, meaningless after the
+ * call.  Two launches, as pc_prob_truth_hist: bpf blocks per frame (a function of H * W alone, at most 64) write the mask and leave one
+ * partial (count, box, sum) each in ws, then one thread per frame adds them in block order.  No global atomics, no LDS atomics, no floating
+ * point that rounds except the final division, nothing waits on another block: bit-identical from run to run.  pc_prob_cut_ws_bytes is host
+ * arithmetic: -1 for nf, H or W < 1, H * W >= 2^31.  Refusals of the call (PC_E_ARG before any HIP call): null prob, rec or ws; F, H,
+ * W < 1; H * W >= 2^31; f0 < 0, nf < 1, f0 + nf > F; word outside 1..PC_PROB_ONE; prob not 2-byte, rec not 4-byte, ws not 8-byte aligned. */
+int64_t pc_prob_cut_ws_bytes(int nf, int H, int W);
+int     pc_prob_cut(const uint16_t* prob, int F, int H, int W, int f0, int nf, int word, uint8_t* mask, int32_t* rec, void* ws, pc_stream s);
 /* Detection on a resized working frame, results at native size (csrc/detectscale.hip; picons_amd/detect.py: DetectEngine.set_working_frame).
  * The views are crops of an Hs x Ws WORKING frame; mask, box, score and probability stand on the H x W NATIVE frame.
  * pc_resample_tables is HOST arithmetic with pc_resize_tables' call shape: it returns the word count 2 * (H + W) and writes `tab` if `cap`

@@ -9,6 +9,7 @@
 //   slot_frame              which video frame a (clip, frame of the clip) slot of a launch is
 //   merge_to_plane          a frame's merged logits (viewmerge.h: merge_group4) and cover counts into a padded plane
 //   tap_row / detect_native_frame   the traversal of a native frame whose logits are bilinear taps of a plane, over a tap reader
+//   record_count_box        a frame's accumulated share -> words 0..4 of its record (probcut.hip ends in it too)
 //   record_from_partials    a frame's partials in block order -> its 8-word record
 //   detect_records_kernel   the second launch of the clip-table entries
 //   det_views_bpf, plane_stride, detect_args   host arithmetic and the argument checks, in the order they refuse
@@ -192,14 +193,21 @@ __device__ __forceinline__ void detect_native_frame(const Tap& tap, const uint8_
     acc.block_partial(out);
 }
 
+// Words 0..4 of a record from a frame's accumulated share: the count and the half-open box, all zero for an empty frame.  (bx, by): what
+// takes the box to full-frame coordinates.  True when the frame has a positive pixel.
+__device__ __forceinline__ bool record_count_box(const FrameAcc& a, int bx, int by, int32_t* r) {
+    const bool any = a.cnt > 0;
+    r[0] = a.cnt;
+    r[1] = any ? bx + a.x0 : 0; r[2] = any ? by + a.y0 : 0; r[3] = any ? bx + a.x1 + 1 : 0; r[4] = any ? by + a.y1 + 1 : 0;
+    return any;
+}
+
 // A frame's block partials q[0 .. bpf) in block order, one division in double, one rounding to float -> the record r.  (bx, by): what takes
 // the partials' box to full-frame coordinates; row: word 6, the frame's score row.
 __device__ __forceinline__ void record_from_partials(const Partial* q, int bpf, int bx, int by, int row, int32_t* r) {
     FrameAcc a;
     for (int b = 0; b < bpf; ++b) a.add(q[b]);
-    const bool any = a.cnt > 0;
-    r[0] = a.cnt;
-    r[1] = any ? bx + a.x0 : 0; r[2] = any ? by + a.y0 : 0; r[3] = any ? bx + a.x1 + 1 : 0; r[4] = any ? by + a.y1 + 1 : 0;
+    const bool any = record_count_box(a, bx, by, r);
     r[5] = __float_as_int(any ? (float)(a.sum / (double)a.cnt) : 0.0f);
     r[6] = row;
     r[7] = 0;

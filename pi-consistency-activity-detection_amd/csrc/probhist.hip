@@ -16,6 +16,7 @@
 // of the input alone.
 #include "common.h"
 #include "rowbytes.h"
+#include "probwords.h"
 
 namespace {
 
@@ -38,15 +39,6 @@ struct HistK {
     int H, W, N, bpf, top;                                           // top: the largest power of two <= N, the search's first step
     uint32_t thr[MAXN / 2];                                          // word 2i in the low half, 2i + 1 in the high half
 };
-
-// the four probabilities at q (the first n of them wanted, the others 0) as two dwords; wide: q is 8-byte aligned
-__device__ __forceinline__ uint2 prob_words(const uint16_t* q, int n, bool wide) {
-    if (wide && n == 4) return *(const uint2*)q;
-    uint32_t v[4];
-#pragma unroll
-    for (int e = 0; e < 4; ++e) v[e] = e < n ? (uint32_t)q[e] : 0u;
-    return make_uint2(v[0] | (v[1] << 16), v[2] | (v[3] << 16));
-}
 
 // grid (frames * bpf): block x is share x % bpf of frame x / bpf.  The bpf blocks of a frame stride over its groups of four consecutive
 // pixels.  A pixel without truth and below the first threshold is not counted at all (cell [0][0] comes out of the fold), as is a group of

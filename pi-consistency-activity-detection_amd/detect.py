@@ -58,6 +58,13 @@ unless DetectEngine.set_clip_hop(hop) is called: then the windows start every `h
 ceil(8 * f_skip / hop) of them, pc_clip_planes keeps the merged logits of every (window, frame) on the device until the video's last clip has
 run, and pc_detect_frames_planes averages the windows that hold a frame in front of the resample, the threshold, the box, the score and the
 probability.  Everything behind mask, probability and record -- instances, scores, links, runs, score() -- works on them unchanged.
+
+Mask threshold.  What sweep() finds the engine can use: DetectEngine.set_mask_threshold(t) has the videos to come cut at the word
+cut_word(t) -- the sweep's own word for t -- by one pc_prob_cut launch per video over its kept probability map, behind its last clip and in
+front of the class vote and the instances: the mask is q >= word (pc_prob_truth_hist's "positive at threshold k"), count, box and score of
+the records are made from it, and everything behind a mask runs on it unchanged.  DetectEngine.recut(t), called after results(), cuts the
+pass that just ran again at t on the device, with no second forward and one host wait: recut(sw.thresholds[k]) followed by score() gives
+sw.results[k] bit for bit.
 """
 from types import SimpleNamespace
 
@@ -276,10 +283,16 @@ class Detection:
 
     With DetectEngine(instance_links=L) also inst_overlaps int32 [F, L, K + 1, K + 1]: inst_overlaps[f, l, a, b] the pixels that slot a of
     frame f shares with slot b of frame f + l + 1 (slot r < K: the instance of rank r; slot K: all other foreground, and ALL foreground of a
-    frame whose overflow flag is set; zeros where frame f + l + 1 does not exist).  None without the option."""
+    frame whose overflow flag is set; zeros where frame f + l + 1 does not exist).  None without the option.
+
+    threshold: None for a video whose mask is seg_positive's (fp32 sigmoid(x) >= 0.5), or (threshold, word) when it was cut from its
+    probability map at q >= word (DetectEngine.set_mask_threshold / recut).  The frame_scores of a cut video are means of the probability
+    WORDS of the positive pixels / 65535, not of the fp32 sigmoid: a word is the sigmoid rounded to a step of 1 / 65535, so the two differ
+    by at most half a step plus the rounding of the float32 result, below 1e-5 -- the bound instance scores carry."""
 
     work = None                          # set by DetectEngine.results() behind the constructor, whose parameter list is pinned
     hop = None                           # likewise
+    threshold = None                     # likewise (and by DetectEngine.recut)
 
     def __init__(self, label, class_score, class_scores, counts, boxes, frame_scores, masks, views=None, inst=None, imap=None, scores=None, probs=None,
                  inst_overlaps=None):
@@ -511,6 +524,24 @@ def threshold_words(thresholds=None):
     return words.astype(np.uint16)
 
 
+def cut_word(threshold):
+    """One mask threshold in (0, 1] -> its word, an int in 1..65535: the one word of threshold_words([threshold]), with its refusals
+    (ValueError).  The engine's word (DetectEngine.set_mask_threshold / recut) and the sweep's word are therefore the same function of the
+    same float, and cut_word(w / 65535) == w for every word w: a word read off a SweepScore can be handed back as a threshold exactly."""
+    return int(threshold_words([threshold])[0])
+
+
+def _cut_threshold(who, threshold):
+    """The (threshold, word) a video is cut at, or ValueError naming `who`: what cut_word refuses, and a bool."""
+    if isinstance(threshold, (bool, np.bool_)):
+        raise ValueError("%s: threshold = %r, a number in (0, 1]" % (who, threshold))
+    try:
+        word = cut_word(threshold)
+    except ValueError as e:
+        raise ValueError("%s: %s" % (who, e)) from None
+    return float(threshold), word
+
+
 def sweep_counts(hist):
     """Histograms int32 [F, 2, N + 1] of pc_prob_truth_hist -> int64 [N, F, 3]: per threshold k the (inter, union, gt) of crosstab_counts for
     the mask q >= word k.  A pixel is positive at k exactly if more than k words are at or below it, so inter_k = sum(hist[f, 1, k + 1:]),
@@ -677,8 +708,14 @@ class DetectEngine(ClipEngine):
     detected from the mean of the windows that hold it (below).
 
     set_keep_probs(True): videos added from then on keep their probability map (Detection.probs) without instances; sweep(truths, labels)
-    then scores the pass at every mask threshold from one histogram launch per video (below)."""
+    then scores the pass at every mask threshold from one histogram launch per video (below).
 
+    set_mask_threshold(t): videos added from then on keep their probability map and are cut at the word cut_word(t) by one pc_prob_cut
+    launch behind their last clip, in front of the class vote and the instances (below).  recut(t), after results(): the finished pass cut
+    again at t on the device, with no second forward (below)."""
+
+    mask_threshold = None                # set_mask_threshold: (threshold, word) for the videos to come, None for seg_positive's mask
+    ws_cut = None                        # pc_prob_cut's partials, grown only for a larger video
     hop = None                           # set_clip_hop: the distance between two windows for the videos to come, None for today's cut
     ws_planes = None                     # pc_detect_frames_planes' partials, grown only for a larger frame
 
@@ -791,6 +828,23 @@ class DetectEngine(ClipEngine):
             raise ValueError("set_keep_probs: keep = %r, True or False" % (keep,))
         self.keep_probs = bool(keep)
 
+    def set_mask_threshold(self, threshold=None):
+        """threshold: a number in (0, 1].  Every video added from now on is cut at the word cut_word(threshold) -- the word sweep() gives
+        that threshold -- instead of at seg_positive's sigmoid(x) >= 0.5: the video keeps its probability map whether or not keep_probs /
+        instance_scores ask for it (filled by the route's own launches, as under set_keep_probs(True)), and behind its last clip ONE
+        pc_prob_cut launch over all its frames rewrites its mask (q >= word) and words 0..5 of its records (count, box, score) -- behind the
+        hop path's pc_detect_frames_planes, in front of pc_video_class, pc_frame_instances, the instance scores and the overlaps, which run
+        on that mask unchanged.  The existing detect kernels are not told the threshold: the price is one more pass over the map.  Each
+        video keeps the threshold it was added under (Detection.threshold = (threshold, word)); its frame_scores are means of probability
+        words (Detection).  threshold=None: seg_positive's mask again, today's launches and nothing else.  ValueError for anything
+        threshold_words refuses and for a bool; nothing changes then."""
+        self.mask_threshold = None if threshold is None else _cut_threshold("set_mask_threshold", threshold)
+
+    def _cut_ws(self, F, H, W):
+        need = ops.prob_cut_ws_bytes(F, H, W)
+        if self.ws_cut is None or self.ws_cut.numel() < need:
+            self.ws_cut = torch.empty(need, dtype=torch.uint8, device=self.dev)
+
     def _frame(self, H, W):
         """The frame the views of an H x W video are cut from: the working frame if one is set, else its own."""
         return (H, W) if self.work is None else self.work[:2]
@@ -860,8 +914,11 @@ class DetectEngine(ClipEngine):
         rec.dev = torch.empty(rec.at.words, dtype=torch.int32, device=self.dev)
         rec.mask = torch.empty(F, H, W, dtype=torch.uint8, device=self.dev) if self.masks else None
         rec.imap = torch.empty(F, H, W, dtype=torch.uint8, device=self.dev) if self.instance_maps or self.instance_scores or self.instance_links else None
-        rec.prob = torch.empty(F, H, W, dtype=torch.int16, device=self.dev) if self.instance_scores or self.keep_probs else None
+        rec.prob = torch.empty(F, H, W, dtype=torch.int16, device=self.dev) if self.instance_scores or self.keep_probs or self.mask_threshold else None
         rec.pin = None
+        rec.cut = self.mask_threshold
+        if rec.cut:
+            self._cut_ws(F, H, W)
         rec.hop, rec.planes = self.hop, None
         if rec.hop:
             # the slot planes and the cover of the frame the views are cut from, in one allocation, until the video's last clip has run;
@@ -929,7 +986,17 @@ class DetectEngine(ClipEngine):
                                          min(ops.PLANES_MAX_FRAMES, rec.F - f0), row0=rec.row0, mask=rec.mask, prob=rec.prob,
                                          rec=rec.dev[at.rec].view(rec.F, -1), ws=self.ws_planes, want_mask=False)
             rec.planes = None                                         # written and read on the compute stream alone: the allocator may reuse them
+        if rec.cut:
+            # the kept probability map, whole by now, cut at the video's word: mask and words 0..5 of the records anew
+            ops.prob_cut(rec.prob, rec.cut[1], mask=rec.mask, rec=rec.dev[at.rec].view(rec.F, -1), ws=self.ws_cut, want_mask=False)
         ops.video_class(self.scores[rec.row0:rec.row0 + rec.rows], out=rec.dev[at.cls].view(torch.float32))
+        self._instances(rec)
+        rec.pin = self._stage(rec.dev.numel())
+        rec.pin.copy_(rec.dev, non_blocking=True)
+
+    def _instances(self, rec):
+        """The video's instances, their scores and their overlaps from its mask, into their words of rec.dev and into rec.imap."""
+        at = rec.at
         if self.inst_k:
             ops.frame_instances(rec.mask, conn=self.conn, min_area=self.min_area, K=self.inst_k, inst=rec.dev[at.inst].view(rec.F, -1), imap=rec.imap,
                                 want_imap=False)
@@ -937,34 +1004,73 @@ class DetectEngine(ClipEngine):
                 ops.instance_scores(rec.imap, rec.prob, self.inst_k, out=rec.dev[at.score].view(rec.F, -1))
             if self.instance_links:
                 ops.instance_overlaps(rec.imap, self.inst_k, self.instance_links, out=rec.dev[at.link])
-        rec.pin = self._stage(rec.dev.numel())
-        rec.pin.copy_(rec.dev, non_blocking=True)
+
+    def _detection(self, rec):
+        """The video's staged record (rec.pin, copied by now) -> its Detection."""
+        words, at = rec.pin.numpy(), rec.at
+        counts, boxes, fscores, _rows = ops.decode_detect_records(words[at.rec])
+        cls = words[at.cls].copy().view(np.float32)
+        inst = scores = overlaps = None
+        if self.inst_k:
+            n, kept, _runs, flags, areas, ibox, first = ops.decode_instances(words[at.inst], self.inst_k)
+            inst = substitute_overflow(counts, boxes, self.min_area, (n, kept, flags, areas, ibox, first))
+            if self.instance_scores:
+                sums, npix = ops.decode_instance_scores(words[at.score], self.inst_k)
+                scores = score_instances(sums, npix, inst[1], inst[2])
+            if self.instance_links:
+                overlaps = ops.decode_instance_overlaps(words[at.link], self.inst_k, self.instance_links)
+        d = Detection(int(cls[self.C]), float(cls[self.C + 1]), cls[:self.C].copy(), counts, boxes, fscores, rec.mask, list(rec.views), inst,
+                      rec.imap if self.instance_maps else None, scores, rec.prob, overlaps)
+        if rec.work:
+            d.work = tuple(rec.work)
+        if rec.hop:
+            d.hop = rec.hop
+        if rec.cut:
+            d.threshold = tuple(rec.cut)
+        return d
 
     def results(self):
         """The pass's one host wait -> [Detection], one per video in arrival order."""
         self.flush()
         torch.cuda.current_stream(self.dev).synchronize()
-        out = []
-        for rec in self.videos:
-            words, at = rec.pin.numpy(), rec.at
-            counts, boxes, fscores, _rows = ops.decode_detect_records(words[at.rec])
-            cls = words[at.cls].copy().view(np.float32)
-            inst = scores = overlaps = None
-            if self.inst_k:
-                n, kept, _runs, flags, areas, ibox, first = ops.decode_instances(words[at.inst], self.inst_k)
-                inst = substitute_overflow(counts, boxes, self.min_area, (n, kept, flags, areas, ibox, first))
-                if self.instance_scores:
-                    sums, npix = ops.decode_instance_scores(words[at.score], self.inst_k)
-                    scores = score_instances(sums, npix, inst[1], inst[2])
-                if self.instance_links:
-                    overlaps = ops.decode_instance_overlaps(words[at.link], self.inst_k, self.instance_links)
-            out.append(Detection(int(cls[self.C]), float(cls[self.C + 1]), cls[:self.C].copy(), counts, boxes, fscores, rec.mask, list(rec.views), inst,
-                                 rec.imap if self.instance_maps else None, scores, rec.prob, overlaps))
-            if rec.work:
-                out[-1].work = tuple(rec.work)
-            if rec.hop:
-                out[-1].hop = rec.hop
-        return out
+        return [self._detection(rec) for rec in self.videos]
+
+    def recut(self, threshold, videos=None):
+        """The last pass cut again at `threshold` (a number in (0, 1]: the word cut_word(threshold), the one sweep() gives it) -> [Detection],
+        one per video in arrival order, or per index in `videos`.  Called after results() -- the natural step after sweep().best() -- and
+        again with another threshold; no forward runs.  Per picked video, on the compute stream: pc_prob_cut over its kept probability map
+        into its mask (null with masks=False) and words 0..5 of its records; pc_frame_instances / pc_instance_scores / pc_instance_overlaps
+        into their words and into the map of ranks, as behind a video's last clip, when the engine has instances; the whole record to fresh
+        page-locked staging.  ONE host wait per call, however many videos.
+
+        recut works IN PLACE ON THE DEVICE: the `masks` / `imap` tensors of Detection objects handed out earlier are the same tensors and
+        show the new contents, their host arrays (counts, boxes, scores, instances) do not change; mask_runs(), score() and sweep() called
+        afterwards see the re-cut pass.  Videos not picked are not touched.  Class label and scores, views, work, hop and probs are
+        unchanged; Detection.threshold = (threshold, word), and frame_scores are means of probability words (Detection): recut(0.5) of a
+        plain pass gives its masks, counts, boxes and instances bit for bit and its frame_scores within 1e-5.
+        Every refusal is a ValueError before anything is enqueued or allocated: no finished pass, a threshold threshold_words refuses or a
+        bool, an index outside the pass, a picked video that keeps no probability map."""
+        if not self.videos or any(rec.pin is None for rec in self.videos):
+            raise ValueError("recut: no finished pass (call it after results())")
+        cut = _cut_threshold("recut", threshold)
+        picks = self._picks("recut", videos)
+        for v in picks:
+            if self.videos[v].prob is None:
+                raise ValueError("recut: video %d keeps no probability map (set_keep_probs(True) or set_mask_threshold(t) before it is added, "
+                                 "or instance_scores=True)" % v)
+        if not picks:
+            return []
+        recs = [self.videos[v] for v in picks]
+        for rec in recs:
+            self._cut_ws(rec.F, rec.H, rec.W)
+        for rec in recs:
+            ops.prob_cut(rec.prob, cut[1], mask=rec.mask, rec=rec.dev[rec.at.rec].view(rec.F, -1), ws=self.ws_cut, want_mask=False)
+            self._instances(rec)
+            rec.cut = cut
+            rec.pin = self._stage(rec.dev.numel())
+            rec.pin.copy_(rec.dev, non_blocking=True)
+        torch.cuda.current_stream(self.dev).synchronize()             # the call's one wait on the compute stream
+        return [self._detection(rec) for rec in recs]
 
     def _check_pass(self, who, which):
         """The refusals mask_runs and score (who) open with: a `which` the engine does not keep, no finished pass."""

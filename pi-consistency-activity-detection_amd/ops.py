@@ -1169,6 +1169,49 @@ def decode_prob_truth_hist(words, N):
     return r.reshape(-1, 2, N + 1).copy()
 
 
+def prob_cut_ws_bytes(nf, H, W):
+    """pc_prob_cut_ws_bytes (host arithmetic): the bytes of workspace one prob_cut call over nf frames of H x W takes."""
+    n = int(capi.lib().pc_prob_cut_ws_bytes(int(nf), int(H), int(W)))
+    if n < 0:
+        raise ValueError("prob_cut_ws_bytes: nf = %d frames of %d x %d: nf, H, W >= 1, H * W < 2^31" % (nf, H, W))
+    return n
+
+
+def prob_cut(prob, word, f0=0, nf=None, mask=None, rec=None, ws=None, want_mask=True):
+    """pc_prob_cut: prob a contiguous 16-bit integer device tensor [F,H,W] (frame_probs': uint16 words), word an integer in 1..65535 ->
+    (mask uint8 [F,H,W] or None, rec int32 [F,8]) for the frames f0 .. f0 + nf - 1 (default: all from f0 on): mask = 1 where the
+    probability word is >= word, rec words 0..5 = count, half-open box x0, y0, x1, y1 and the float32 bits of the mean probability word of
+    the positive pixels / 65535; words 6 and 7 of a record are left as they are.  Given tensors are written in place -- only those frames --
+    fresh ones are zero-filled first.  want_mask=False with mask=None: records only.  ws: uint8 device scratch of at least
+    prob_cut_ws_bytes(nf, H, W) bytes, made when None."""
+    if not torch.is_tensor(prob) or prob.dtype not in _PROB_DTYPES or prob.dim() != 3 or not prob.is_contiguous() or not prob.is_cuda:
+        raise ValueError("prob_cut: contiguous 16-bit integer [F,H,W] device prob")
+    if isinstance(word, (bool, np.bool_)) or not isinstance(word, (int, np.integer)) or not 1 <= int(word) <= PROB_ONE:
+        raise ValueError("prob_cut: word = %r is no integer in 1..%d" % (word, PROB_ONE))
+    F, H, W = (int(v) for v in prob.shape)
+    f0 = int(f0)
+    nf = F - f0 if nf is None else int(nf)
+    if f0 < 0 or nf < 1 or f0 + nf > F:
+        raise ValueError("prob_cut: frames f0 = %d, nf = %d outside the %d of the map" % (f0, nf, F))
+    dev = prob.device
+    if mask is None and want_mask:
+        mask = torch.zeros(F, H, W, dtype=torch.uint8, device=dev)
+    elif mask is not None and (not torch.is_tensor(mask) or mask.dtype != torch.uint8 or not mask.is_contiguous() or mask.numel() != F * H * W
+                               or mask.device != dev):
+        raise ValueError("prob_cut: mask must be a contiguous uint8 device tensor [F,H,W]")
+    if rec is None:
+        rec = torch.zeros(F, DETECT_REC_WORDS, dtype=torch.int32, device=dev)
+    elif not torch.is_tensor(rec) or rec.dtype != torch.int32 or not rec.is_contiguous() or rec.numel() != F * DETECT_REC_WORDS or rec.device != dev:
+        raise ValueError("prob_cut: rec must be a contiguous int32 device tensor [F,8]")
+    need = prob_cut_ws_bytes(nf, H, W)
+    if ws is None:
+        ws = torch.empty(need, dtype=torch.uint8, device=dev)
+    elif not torch.is_tensor(ws) or ws.dtype != torch.uint8 or not ws.is_contiguous() or ws.numel() < need or ws.device != dev:
+        raise ValueError("prob_cut: ws must be a contiguous uint8 device tensor of at least %d bytes" % need)
+    capi.call("pc_prob_cut", ptr(prob), F, H, W, f0, nf, int(word), ptr(mask), ptr(rec), ptr(ws), stream())
+    return mask, rec
+
+
 def video_class(scores, out=None):
     """pc_video_class: scores contiguous float32 device [n,C] -> float32 device [C + 2]: mean class scores, arg-max (as a float), its mean."""
     if scores.dtype != torch.float32 or scores.dim() != 2 or not scores.is_contiguous():

@@ -41,11 +41,18 @@ per video, one host wait).  One line per threshold: f-mAP@0.5 and v-mAP@0.5 (the
 them) and the pixel precision and recall over every frame of every scored video; `*` marks the first threshold with the largest printed
 f-mAP@0.5.  Stored: sweep_thresholds [N], sweep_words [N], sweep_fmAP [N, 20] and sweep_vmAP [N, 20] (the evaluator's own: NaN as soon as one
 class holds no video), sweep_pixel int64 [N, 3] = (tp, fp, fn).
+--threshold t: the masks are cut at probability >= t, t in (0, 1], instead of at sigmoid(x) >= 0.5 (DetectEngine.set_mask_threshold: the
+videos keep their probability map and one pc_prob_cut launch per video cuts it at the word ceil(t * 65535), in front of the class vote and
+the instances); counts, boxes, instances, runs and score are those of that mask, frame_scores_i the means of the probability words.
+--sweep [t ...] --recut: after the sweep the finished pass is cut again ON THE DEVICE at the printed best threshold (DetectEngine.recut: no
+second forward, one host wait), before masks, runs, score and records are stored: everything stored is the pass at that threshold.  The
+sweep is then printed in front of the score.  Without a best threshold (every f-mAP@0.5 NaN) nothing is cut again.  With either option
+mask_threshold and mask_word record the threshold and its word.
 
     python tools/detect.py --out detections.npz [--ckpt best_model.pth] [--synthetic 4 | video.npy ...] [--masks] [--pack] [--tile] [--flip]
                            [--max-gap 0] [--min-pixels 1] [--instances K] [--min_area 1] [--conn 8] [--instance_maps] [--instance_scores]
                            [--instance_links L] [--link box|mask] [--mask_runs] [--truth t0.npy ... --labels l0 ... | --score]
-                           [--frame_size Hs Ws [--interp area|linear|nearest]] [--hop N] [--sweep [t ...]]
+                           [--frame_size Hs Ws [--interp area|linear|nearest]] [--hop N] [--sweep [t ...] [--recut]] [--threshold t]
 """
 import argparse
 import os
@@ -89,6 +96,8 @@ def main():
     ap.add_argument("--interp", default="area", choices=sorted(detect.INTERPOLATIONS), help="with --frame_size: cv2.resize's interpolation")
     ap.add_argument("--hop", type=int, default=None, help="cut overlapping clips that start every N frames and average the clips that hold a frame (a multiple of 2 in 2..16; 16: today's cut)")
     ap.add_argument("--sweep", nargs="*", type=float, default=None, metavar="t", help="with --truth/--labels or --score: f-mAP / v-mAP and pixel precision / recall at every mask threshold t (default 0.05 .. 0.95) from the kept probability map")
+    ap.add_argument("--threshold", type=float, default=None, metavar="t", help="cut the masks at probability >= t in (0, 1] instead of at sigmoid(x) >= 0.5 (DetectEngine.set_mask_threshold)")
+    ap.add_argument("--recut", action="store_true", help="with --sweep: cut the finished pass again on the device at the best threshold of the sweep before anything is stored (DetectEngine.recut)")
     a = ap.parse_args()
     if (a.truth is None) != (a.labels is None) or (a.truth is not None and not (len(a.truth) == len(a.labels) == len(a.videos))):
         raise SystemExit("tools/detect.py: --truth and --labels go together, one of each per video file")
@@ -101,6 +110,13 @@ def main():
             detect.threshold_words(a.sweep or None)
         except ValueError as e:
             raise SystemExit("tools/detect.py: --sweep: %s" % e)
+    if a.recut and a.sweep is None:
+        raise SystemExit("tools/detect.py: --recut cuts at the best threshold of a sweep: give --sweep")
+    if a.threshold is not None:
+        try:
+            detect.cut_word(a.threshold)
+        except ValueError as e:
+            raise SystemExit("tools/detect.py: --threshold: %s" % e)
     if a.instance_scores and a.instances <= 0:
         raise SystemExit("tools/detect.py: --instance_scores needs --instances K with K > 0 (the scores are reduced per instance)")
     if a.instance_links and a.instances <= 0:
@@ -146,11 +162,38 @@ def main():
             raise SystemExit("tools/detect.py: --hop: %s" % e)
     if a.sweep is not None:
         engine.set_keep_probs(True)
+    if a.threshold is not None:
+        engine.set_mask_threshold(a.threshold)
     engine.begin()
     for v in videos:
         engine.add_video(v)
     out = {"names": np.array(names), "tile": np.bool_(a.tile), "flip": np.bool_(a.flip)}
     dets = engine.results()
+
+    def sweep():
+        """Print and store the sweep -> the best threshold, None when every f-mAP@0.5 is NaN."""
+        sw = engine.sweep(truths, labels, a.sweep or None)
+        with np.errstate(invalid="ignore", divide="ignore"):          # printed as below: the mean over the classes that hold a video
+            fm = np.array([np.nanmean(r["frame_ious"] / r["n_tot_frames"], axis=0)[10] for r in sw.results])
+            vm = np.array([np.nanmean(r["video_ious"] / r["n_vids"], axis=0)[10] for r in sw.results])
+            tp, fp, fn = (sw.pixel[:, j].astype(np.float64) for j in range(3))
+            prec, rec = tp / (tp + fp), tp / (tp + fn)                # NaN where nothing is predicted / nothing is true
+        best = -1 if np.isnan(fm).all() else int(np.nanargmax(fm))
+        print("sweep of the mask threshold (%d videos, %d without truth):  threshold  f-mAP@0.5  v-mAP@0.5  pixel precision  pixel recall" % (len(sw.videos), sw.n_skipped))
+        for k, t in enumerate(sw.thresholds):
+            print("  %s %.4f  %.4f  %.4f  %.4f  %.4f" % ("*" if k == best else " ", t, fm[k], vm[k], prec[k], rec[k]))
+        out.update({"sweep_thresholds": sw.thresholds, "sweep_words": sw.words, "sweep_fmAP": sw.fmAP, "sweep_vmAP": sw.vmAP, "sweep_pixel": sw.pixel})
+        return None if best < 0 else float(sw.thresholds[best])
+
+    if a.recut and truths is not None:                                # the sweep first: what follows is stored at its best threshold
+        t = sweep()
+        if t is None:
+            print("no best threshold (every f-mAP@0.5 is NaN): the pass stays as it was cut")
+        else:
+            dets = engine.recut(t)
+            print("re-cut on the device at the best threshold %.6f (word %d)" % dets[0].threshold)
+    if dets and dets[0].threshold is not None:
+        out.update({"mask_threshold": np.float64(dets[0].threshold[0]), "mask_word": np.int32(dets[0].threshold[1])})
     if a.mask_runs:
         for key, which in (("mask", "masks"),) + ((("imap", "imap"),) if a.instances and a.instance_maps else ()):
             for i, r in enumerate(engine.mask_runs(which)):
@@ -166,18 +209,8 @@ def main():
         out.update({"score_" + k: np.asarray(v) for k, v in r.items()})
         for i, v in enumerate(ps.videos):
             out.update({"score_table_%d" % i: v.table, "score_counts_%d" % i: v.counts, "score_label_%d" % i: np.int32(v.label)})
-    if a.sweep is not None and truths is not None:
-        sw = engine.sweep(truths, labels, a.sweep or None)
-        with np.errstate(invalid="ignore", divide="ignore"):          # printed as above: the mean over the classes that hold a video
-            fm = np.array([np.nanmean(r["frame_ious"] / r["n_tot_frames"], axis=0)[10] for r in sw.results])
-            vm = np.array([np.nanmean(r["video_ious"] / r["n_vids"], axis=0)[10] for r in sw.results])
-            tp, fp, fn = (sw.pixel[:, j].astype(np.float64) for j in range(3))
-            prec, rec = tp / (tp + fp), tp / (tp + fn)                # NaN where nothing is predicted / nothing is true
-        best = -1 if np.isnan(fm).all() else int(np.nanargmax(fm))
-        print("sweep of the mask threshold (%d videos, %d without truth):  threshold  f-mAP@0.5  v-mAP@0.5  pixel precision  pixel recall" % (len(sw.videos), sw.n_skipped))
-        for k, t in enumerate(sw.thresholds):
-            print("  %s %.4f  %.4f  %.4f  %.4f  %.4f" % ("*" if k == best else " ", t, fm[k], vm[k], prec[k], rec[k]))
-        out.update({"sweep_thresholds": sw.thresholds, "sweep_words": sw.words, "sweep_fmAP": sw.fmAP, "sweep_vmAP": sw.vmAP, "sweep_pixel": sw.pixel})
+    if a.sweep is not None and truths is not None and not a.recut:
+        sweep()
     for i, (name, d) in enumerate(zip(names, dets)):
         tubes = d.tubes(a.min_pixels, a.max_gap)
         out.update({"label_%d" % i: np.int32(d.label), "class_scores_%d" % i: d.class_scores, "counts_%d" % i: d.counts, "boxes_%d" % i: d.boxes,
