@@ -72,7 +72,7 @@ import numpy as np
 import torch
 
 from . import evalmetrics, ops
-from .evalstep import ClipEngine, _as_u8, centre_crop, clip_starts, ring_place
+from .evalstep import ClipEngine, _as_u8, centre_crop, check_counts, check_label, check_truth, clip_starts, ring_place
 
 PIN_CHUNK_WORDS = 1 << 18          # page-locked staging of the records, 1 MiB at a time
 MAX_VIEWS = ops.MAX_VIEWS          # views of one video (one launch cuts, one merges, all of them)
@@ -840,10 +840,18 @@ class DetectEngine(ClipEngine):
         threshold_words refuses and for a bool; nothing changes then."""
         self.mask_threshold = None if threshold is None else _cut_threshold("set_mask_threshold", threshold)
 
-    def _cut_ws(self, F, H, W):
-        need = ops.prob_cut_ws_bytes(F, H, W)
-        if self.ws_cut is None or self.ws_cut.numel() < need:
-            self.ws_cut = torch.empty(need, dtype=torch.uint8, device=self.dev)
+    def _grow(self, name, n, pin=None, slot=None):
+        """The engine's buffer `name` (element `slot` of it, where it is a pair) with room for n elements -> the buffer: None until first
+        needed, made then, made anew only for a larger n.  pin=None: uint8 on the device, a kernel's workspace; else page-locked host memory
+        of dtype `pin`, 1024 elements at least."""
+        buf = getattr(self, name) if slot is None else getattr(self, name)[slot]
+        if buf is None or buf.numel() < n:
+            buf = torch.empty(n, dtype=torch.uint8, device=self.dev) if pin is None else torch.empty(max(n, 1024), dtype=pin).pin_memory()
+            if slot is None:
+                setattr(self, name, buf)
+            else:
+                getattr(self, name)[slot] = buf
+        return buf
 
     def _frame(self, H, W):
         """The frame the views of an H x W video are cut from: the working frame if one is set, else its own."""
@@ -918,23 +926,17 @@ class DetectEngine(ClipEngine):
         rec.pin = None
         rec.cut = self.mask_threshold
         if rec.cut:
-            self._cut_ws(F, H, W)
+            self._grow("ws_cut", ops.prob_cut_ws_bytes(F, H, W))
         rec.hop, rec.planes = self.hop, None
         if rec.hop:
             # the slot planes and the cover of the frame the views are cut from, in one allocation, until the video's last clip has run;
             # every (slot, frame) that is read has been written by a launch: nothing is filled
             rec.planes = torch.empty(ops.clip_planes_bytes(F, *frame, self.f_skip, rec.hop), dtype=torch.uint8, device=self.dev)
-            need = ops.detect_frames_planes_ws_bytes(min(F, ops.PLANES_MAX_FRAMES), H, W)
-            if self.ws_planes is None or self.ws_planes.numel() < need:
-                self.ws_planes = torch.empty(need, dtype=torch.uint8, device=self.dev)
+            self._grow("ws_planes", ops.detect_frames_planes_ws_bytes(min(F, ops.PLANES_MAX_FRAMES), H, W))
         elif rec.work:
-            need = ops.detect_frames_scaled_ws_bytes(min(self.bs // len(cut), 32), *frame, H, W)
-            if self.ws_scaled is None or self.ws_scaled.numel() < need:
-                self.ws_scaled = torch.empty(need, dtype=torch.uint8, device=self.dev)
+            self._grow("ws_scaled", ops.detect_frames_scaled_ws_bytes(min(self.bs // len(cut), 32), *frame, H, W))
         elif views:
-            need = ops.detect_frames_views_ws_bytes(min(self.bs, 32), H, W)
-            if self.ws_views is None or self.ws_views.numel() < need:
-                self.ws_views = torch.empty(need, dtype=torch.uint8, device=self.dev)
+            self._grow("ws_views", ops.detect_frames_views_ws_bytes(min(self.bs, 32), H, W))
         self.videos.append(rec)
         self._join(rec, row0, pos)
         return len(self.videos) - 1
@@ -991,8 +993,17 @@ class DetectEngine(ClipEngine):
             ops.prob_cut(rec.prob, rec.cut[1], mask=rec.mask, rec=rec.dev[at.rec].view(rec.F, -1), ws=self.ws_cut, want_mask=False)
         ops.video_class(self.scores[rec.row0:rec.row0 + rec.rows], out=rec.dev[at.cls].view(torch.float32))
         self._instances(rec)
+        self._to_host(rec)
+
+    def _to_host(self, rec):
+        """The video's record into page-locked memory of its own, the copy enqueued behind the launches that wrote it."""
         rec.pin = self._stage(rec.dev.numel())
         rec.pin.copy_(rec.dev, non_blocking=True)
+
+    def _predicted(self, rec):
+        """The class vector of the video's staged record (rec.pin, copied by now) -> (label, class_score, class_scores [C]), copies."""
+        cls = rec.pin.numpy()[rec.at.cls].copy().view(np.float32)
+        return int(cls[self.C]), float(cls[self.C + 1]), cls[:self.C].copy()
 
     def _instances(self, rec):
         """The video's instances, their scores and their overlaps from its mask, into their words of rec.dev and into rec.imap."""
@@ -1009,7 +1020,6 @@ class DetectEngine(ClipEngine):
         """The video's staged record (rec.pin, copied by now) -> its Detection."""
         words, at = rec.pin.numpy(), rec.at
         counts, boxes, fscores, _rows = ops.decode_detect_records(words[at.rec])
-        cls = words[at.cls].copy().view(np.float32)
         inst = scores = overlaps = None
         if self.inst_k:
             n, kept, _runs, flags, areas, ibox, first = ops.decode_instances(words[at.inst], self.inst_k)
@@ -1019,8 +1029,8 @@ class DetectEngine(ClipEngine):
                 scores = score_instances(sums, npix, inst[1], inst[2])
             if self.instance_links:
                 overlaps = ops.decode_instance_overlaps(words[at.link], self.inst_k, self.instance_links)
-        d = Detection(int(cls[self.C]), float(cls[self.C + 1]), cls[:self.C].copy(), counts, boxes, fscores, rec.mask, list(rec.views), inst,
-                      rec.imap if self.instance_maps else None, scores, rec.prob, overlaps)
+        d = Detection(*self._predicted(rec), counts, boxes, fscores, rec.mask, list(rec.views), inst, rec.imap if self.instance_maps else None, scores,
+                      rec.prob, overlaps)
         if rec.work:
             d.work = tuple(rec.work)
         if rec.hop:
@@ -1050,8 +1060,7 @@ class DetectEngine(ClipEngine):
         plain pass gives its masks, counts, boxes and instances bit for bit and its frame_scores within 1e-5.
         Every refusal is a ValueError before anything is enqueued or allocated: no finished pass, a threshold threshold_words refuses or a
         bool, an index outside the pass, a picked video that keeps no probability map."""
-        if not self.videos or any(rec.pin is None for rec in self.videos):
-            raise ValueError("recut: no finished pass (call it after results())")
+        self._check_pass("recut")
         cut = _cut_threshold("recut", threshold)
         picks = self._picks("recut", videos)
         for v in picks:
@@ -1062,26 +1071,28 @@ class DetectEngine(ClipEngine):
             return []
         recs = [self.videos[v] for v in picks]
         for rec in recs:
-            self._cut_ws(rec.F, rec.H, rec.W)
+            self._grow("ws_cut", ops.prob_cut_ws_bytes(rec.F, rec.H, rec.W))
         for rec in recs:
             ops.prob_cut(rec.prob, cut[1], mask=rec.mask, rec=rec.dev[rec.at.rec].view(rec.F, -1), ws=self.ws_cut, want_mask=False)
             self._instances(rec)
             rec.cut = cut
-            rec.pin = self._stage(rec.dev.numel())
-            rec.pin.copy_(rec.dev, non_blocking=True)
+            self._to_host(rec)
         torch.cuda.current_stream(self.dev).synchronize()             # the call's one wait on the compute stream
         return [self._detection(rec) for rec in recs]
 
-    def _check_pass(self, who, which):
-        """The refusals mask_runs and score (who) open with: a `which` the engine does not keep, no finished pass."""
+    def _check_pass(self, who):
+        """The refusal everything that reads a pass (who) opens with: no finished pass."""
+        if not self.videos or any(rec.pin is None for rec in self.videos):
+            raise ValueError("%s: no finished pass (call it after results())" % who)
+
+    def _check_which(self, who, which):
+        """The refusal of mask_runs and score (who) in front of that: a `which` the engine does not keep."""
         if which not in ("masks", "imap"):
             raise ValueError("%s: which = %r, \"masks\" or \"imap\"" % (who, which))
         if which == "masks" and not self.masks:
             raise ValueError("%s: the engine keeps no masks (masks=False)" % who)
         if which == "imap" and not self.instance_maps:
             raise ValueError("%s: the engine keeps no maps of ranks (instances=K with instance_maps=True)" % who)
-        if not self.videos or any(rec.pin is None for rec in self.videos):
-            raise ValueError("%s: no finished pass (call it after results())" % who)
 
     def _picks(self, who, videos):
         """`videos` of mask_runs and score (who) -> the indices of the pass's videos they name, all of them for None."""
@@ -1098,7 +1109,8 @@ class DetectEngine(ClipEngine):
         pixels or more in several frame ranges) and the per-frame offsets gathered into page-locked memory -- first wait --, then one buffer
         of exactly the pass's runs is filled (pc_mask_runs per range) and leaves in one asynchronous copy -- second wait.  Every refusal is a
         ValueError before anything is enqueued."""
-        self._check_pass("mask_runs", which)
+        self._check_which("mask_runs", which)
+        self._check_pass("mask_runs")
         picks = self._picks("mask_runs", videos)
         jobs = []                                                     # (map, f0, nf, first word of its offsets in the staging)
         words = 0
@@ -1112,7 +1124,7 @@ class DetectEngine(ClipEngine):
         stream = torch.cuda.current_stream(self.dev)
         # ---- phase 1: the index of every range; its entries at the frame starts and the total (index[::H]) to the host
         off_dev = torch.empty(words, dtype=torch.int32, device=self.dev)
-        off_pin = self._run_stage(0, words)
+        off_pin = self._grow("run_pins", words, torch.int32, 0)[:words]
         indexes = []
         for m, f0, nf, w0 in jobs:
             index = ops.mask_run_index(m, f0, nf)
@@ -1129,7 +1141,7 @@ class DetectEngine(ClipEngine):
         run_dev = torch.empty(total, ops.RUN_WORDS, dtype=torch.int32, device=self.dev)
         for j, (m, f0, nf, _w0) in enumerate(jobs):
             ops.mask_runs(m, indexes[j], f0, nf, runs=run_dev[int(starts[j]):int(starts[j + 1])])
-        run_pin = self._run_stage(1, total * ops.RUN_WORDS)
+        run_pin = self._grow("run_pins", total * ops.RUN_WORDS, torch.int32, 1)[:total * ops.RUN_WORDS]
         run_pin.copy_(run_dev.view(-1), non_blocking=True)
         stream.synchronize()
         words_host = run_pin.numpy().view(np.uint32).reshape(-1, ops.RUN_WORDS)
@@ -1147,12 +1159,6 @@ class DetectEngine(ClipEngine):
             j += len(ranges)
         return out
 
-    def _run_stage(self, slot, words):
-        """`words` int32 of page-locked memory for mask_runs (slot 0: offsets, 1: runs), kept between calls and grown when too small."""
-        if self.run_pins[slot] is None or self.run_pins[slot].numel() < words:
-            self.run_pins[slot] = torch.empty(max(words, 1024), dtype=torch.int32).pin_memory()
-        return self.run_pins[slot][:words]
-
     def score(self, truths, labels, actors=1, which="masks", videos=None):
         """The last pass against truth masks -> PassScore.  truths[i]: uint8 [F,H,W] or [F,H,W,1] (numpy, host tensor or device tensor) for
         the i-th video of the pass, or of `videos`; any non-zero byte is truth, a byte 1..actors is that actor.  labels[i]: its class id.
@@ -1163,57 +1169,54 @@ class DetectEngine(ClipEngine):
         (score_pass).  Unlike EvalEngine the truth is taken on the full frame, not inside the centre crop, and `correct` compares with the
         detection's class, voted over all clips of the video, where EvalEngine votes over the clips that hold truth.  Every refusal is a
         ValueError before anything is enqueued."""
-        self._check_pass("score", which)
+        self._check_which("score", which)
+        self._check_pass("score")
         try:
             A = int(actors)
         except (TypeError, ValueError):
             raise ValueError("score: actors = %r is not a number" % (actors,)) from None
         if A != actors or not 1 <= A <= ops.CROSS_MAX_SLOTS:
             raise ValueError("score: actors = %r outside 1..%d" % (actors, ops.CROSS_MAX_SLOTS))
-        picks = self._picks("score", videos)
-        truths, labels = list(truths), list(labels)
-        if not (len(truths) == len(labels) == len(picks)):
-            raise ValueError("score: %d truths and %d labels for %d videos" % (len(truths), len(labels), len(picks)))
         P = 1 if which == "masks" else self.inst_k
-        jobs, labs, words, ws_need = [], [], 0, 0                       # (record, truth, first word of its tables)
+
+        def launch(rec, truth, out, ws):
+            ops.map_crosstab(rec.mask if which == "masks" else rec.imap, truth, P, A, out=out.view(rec.F, P + 2, A + 2), ws=ws)
+        tables, labs, predicted = self._truth_pass("score", truths, labels, videos, lambda rec: rec.F * (P + 2) * (A + 2),
+                                                   lambda rec: ops.map_crosstab_ws_bytes(rec.F, rec.H, rec.W, P, A), launch,
+                                                   lambda words: ops.decode_map_crosstab(words, P, A))
+        return score_pass(tables, labs, predicted, self.C)
+
+    def _truth_pass(self, who, truths, labels, videos, words_of, ws_of, launch, decode, check=None):
+        """What score and sweep (who) do with the truths of a finished pass, once.  The refusals, in order -- an index outside the pass,
+        not as many truths and labels as videos, then video by video: check(v, record), its truth, its label, the sizes ws_of(record)
+        refuses -- in front of anything allocated or uploaded.  Then ONE buffer of words_of(record) int32 per video, the workspace
+        `<who>_ws` grown to the largest ws_of(record) bytes, per video its truth uploaded and launch(record, truth on the device, its words,
+        workspace) on the compute stream, all words in one asynchronous copy through the page-locked `<who>_pin`, and the call's one wait
+        on the compute stream.  -> ([decode(words) per video]: copies, the staging is used again, [label], [predicted class])."""
+        picks = self._picks(who, videos)
+        truths, labels = check_counts(who, truths, labels, len(picks))
+        jobs, labs, total, ws_need = [], [], 0, 0                       # (record, truth, its words in the buffer)
         for v, truth, label in zip(picks, truths, labels):
             rec = self.videos[v]
-            t = _as_u8(truth, "score: truth of video %d" % v)
-            if t.dim() == 4 and t.shape[3] == 1:
-                t = t.reshape(t.shape[:3])
-            if tuple(t.shape) != (rec.F, rec.H, rec.W):
-                raise ValueError("score: truth of video %d has shape %s, expected (%d, %d, %d) or (%d, %d, %d, 1)"
-                                 % (v, tuple(truth.shape), rec.F, rec.H, rec.W, rec.F, rec.H, rec.W))
-            try:
-                lab = int(label)
-            except (TypeError, ValueError):
-                raise ValueError("score: label %r is not a class id" % (label,)) from None
-            if lab != label or not 0 <= lab < self.C:
-                raise ValueError("score: label %r outside [0, %d)" % (label, self.C))
-            jobs.append((rec, t, words))
-            labs.append(lab)
-            words += rec.F * (P + 2) * (A + 2)
-            ws_need = max(ws_need, ops.map_crosstab_ws_bytes(rec.F, rec.H, rec.W, P, A))
+            if check:
+                check(v, rec)
+            t = check_truth(who, truth, rec.F, rec.H, rec.W, v)
+            labs.append(check_label(who, label, self.C))
+            jobs.append((rec, t, slice(total, total + words_of(rec))))
+            total = jobs[-1][2].stop
+            ws_need = max(ws_need, ws_of(rec))
         if not jobs:
-            return score_pass([], [], [], self.C)
+            return [], [], []
         main = torch.cuda.current_stream(self.dev)
-        if self.score_ws is None or self.score_ws.numel() < ws_need:
-            self.score_ws = torch.empty(ws_need, dtype=torch.uint8, device=self.dev)
-        tab_dev = torch.empty(words, dtype=torch.int32, device=self.dev)
-        for rec, t, w0 in jobs:
-            n = rec.F * (P + 2) * (A + 2)
-            ops.map_crosstab(rec.mask if which == "masks" else rec.imap, self._truth_to_device(t, main), P, A,
-                             out=tab_dev[w0:w0 + n].view(rec.F, P + 2, A + 2), ws=self.score_ws)
-        if self.score_pin is None or self.score_pin.numel() < words:
-            self.score_pin = torch.empty(max(words, 1024), dtype=torch.int32).pin_memory()
-        self.score_pin[:words].copy_(tab_dev, non_blocking=True)
+        ws = self._grow(who + "_ws", ws_need)
+        tab_dev = torch.empty(total, dtype=torch.int32, device=self.dev)
+        for rec, t, at in jobs:
+            launch(rec, self._truth_to_device(t, main), tab_dev[at], ws)
+        pin = self._grow(who + "_pin", total, torch.int32)[:total]
+        pin.copy_(tab_dev, non_blocking=True)
         main.synchronize()                                           # the call's one wait on the compute stream
-        host = self.score_pin[:words].numpy()
-        tables = [ops.decode_map_crosstab(host[w0:w0 + rec.F * (P + 2) * (A + 2)], P, A) for rec, _t, w0 in jobs]      # copies: the staging is used again
-        predicted = []
-        for rec, _t, _w0 in jobs:
-            predicted.append(int(rec.pin.numpy()[rec.at.cls].copy().view(np.float32)[self.C]))
-        return score_pass(tables, labs, predicted, self.C)
+        host = pin.numpy()
+        return [decode(host[at]) for _rec, _t, at in jobs], labs, [self._predicted(rec)[0] for rec, _t, _at in jobs]
 
     def sweep(self, truths, labels, thresholds=None, videos=None):
         """The last pass against truth masks at every mask threshold of `thresholds` (floats in (0, 1], ascending; default 0.05, 0.10 ..
@@ -1222,53 +1225,21 @@ class DetectEngine(ClipEngine):
         nothing results() returned and can be called again.  Per video one upload of its truth (score()'s staging) and one
         pc_prob_truth_hist launch into its part of one buffer; all histograms leave in one asynchronous copy and the call has ONE wait on the
         compute stream, after which the host does the rest (sweep_pass).  Every refusal is a ValueError before anything is enqueued."""
-        if not self.videos or any(rec.pin is None for rec in self.videos):
-            raise ValueError("sweep: no finished pass (call it after results())")
+        self._check_pass("sweep")
         t = np.asarray(DEFAULT_SWEEP, np.float64) if thresholds is None else thresholds
         words = threshold_words(t)
         t = np.asarray(t, np.float64)
         N = int(words.size)
-        picks = self._picks("sweep", videos)
-        truths, labels = list(truths), list(labels)
-        if not (len(truths) == len(labels) == len(picks)):
-            raise ValueError("sweep: %d truths and %d labels for %d videos" % (len(truths), len(labels), len(picks)))
-        jobs, labs, total, ws_need = [], [], 0, 0                       # (record, truth, first word of its histograms)
-        for v, truth, label in zip(picks, truths, labels):
-            rec = self.videos[v]
+
+        def keeps_prob(v, rec):
             if rec.prob is None:
                 raise ValueError("sweep: video %d keeps no probability map (set_keep_probs(True) before it is added, or instance_scores=True)" % v)
-            tr = _as_u8(truth, "sweep: truth of video %d" % v)
-            if tr.dim() == 4 and tr.shape[3] == 1:
-                tr = tr.reshape(tr.shape[:3])
-            if tuple(tr.shape) != (rec.F, rec.H, rec.W):
-                raise ValueError("sweep: truth of video %d has shape %s, expected (%d, %d, %d) or (%d, %d, %d, 1)"
-                                 % (v, tuple(truth.shape), rec.F, rec.H, rec.W, rec.F, rec.H, rec.W))
-            try:
-                lab = int(label)
-            except (TypeError, ValueError):
-                raise ValueError("sweep: label %r is not a class id" % (label,)) from None
-            if lab != label or not 0 <= lab < self.C:
-                raise ValueError("sweep: label %r outside [0, %d)" % (label, self.C))
-            jobs.append((rec, tr, total))
-            labs.append(lab)
-            total += rec.F * 2 * (N + 1)
-            ws_need = max(ws_need, ops.prob_truth_hist_ws_bytes(rec.F, rec.H, rec.W, N))
-        if not jobs:
-            return sweep_pass([], [], [], self.C, words, t)
-        main = torch.cuda.current_stream(self.dev)
-        if self.sweep_ws is None or self.sweep_ws.numel() < ws_need:
-            self.sweep_ws = torch.empty(ws_need, dtype=torch.uint8, device=self.dev)
-        tab_dev = torch.empty(total, dtype=torch.int32, device=self.dev)
-        for rec, tr, w0 in jobs:
-            ops.prob_truth_hist(rec.prob, self._truth_to_device(tr, main), words, out=tab_dev[w0:w0 + rec.F * 2 * (N + 1)].view(rec.F, 2, N + 1),
-                                ws=self.sweep_ws)
-        if self.sweep_pin is None or self.sweep_pin.numel() < total:
-            self.sweep_pin = torch.empty(max(total, 1024), dtype=torch.int32).pin_memory()
-        self.sweep_pin[:total].copy_(tab_dev, non_blocking=True)
-        main.synchronize()                                           # the call's one wait on the compute stream
-        host = self.sweep_pin[:total].numpy()
-        hists = [ops.decode_prob_truth_hist(host[w0:w0 + rec.F * 2 * (N + 1)], N) for rec, _tr, w0 in jobs]      # copies: the staging is used again
-        predicted = [int(rec.pin.numpy()[rec.at.cls].copy().view(np.float32)[self.C]) for rec, _tr, _w0 in jobs]
+
+        def launch(rec, truth, out, ws):
+            ops.prob_truth_hist(rec.prob, truth, words, out=out.view(rec.F, 2, N + 1), ws=ws)
+        hists, labs, predicted = self._truth_pass("sweep", truths, labels, videos, lambda rec: rec.F * 2 * (N + 1),
+                                                  lambda rec: ops.prob_truth_hist_ws_bytes(rec.F, rec.H, rec.W, N), launch,
+                                                  lambda h: ops.decode_prob_truth_hist(h, N), keeps_prob)
         return sweep_pass(hists, labs, predicted, self.C, words, t)
 
     def _truth_to_device(self, t, main):

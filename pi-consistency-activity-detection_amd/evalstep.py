@@ -73,6 +73,37 @@ def _as_u8(a, what):
     return t
 
 
+# What a caller hands in next to a video -- EvalEngine.add_video, DetectEngine.score / sweep (who) -- checked on the host: no GPU use.
+def check_truth(who, truth, F, H, W, video=None):
+    """A truth mask (of video `video` of a pass): uint8, of shape (F, H, W) or (F, H, W, 1) -> torch uint8 [F, H, W] (no copy), or ValueError."""
+    name = "%s: truth" % who if video is None else "%s: truth of video %d" % (who, video)
+    t = _as_u8(truth, name)
+    if t.dim() == 4 and t.shape[3] == 1:
+        t = t.reshape(t.shape[:3])
+    if tuple(t.shape) != (F, H, W):
+        raise ValueError("%s has shape %s, expected (%d, %d, %d) or (%d, %d, %d, 1)" % (name, tuple(truth.shape), F, H, W, F, H, W))
+    return t
+
+
+def check_label(who, label, C):
+    """A class id: an int in [0, C) -> int, or ValueError."""
+    try:
+        lab = int(label)
+    except (TypeError, ValueError):
+        raise ValueError("%s: label %r is not a class id" % (who, label)) from None
+    if lab != label or not 0 <= lab < C:
+        raise ValueError("%s: label %r outside [0, %d)" % (who, label, C))
+    return lab
+
+
+def check_counts(who, truths, labels, n):
+    """As many truths and labels as the n picked videos -> (truths, labels) as lists, or ValueError."""
+    truths, labels = list(truths), list(labels)
+    if not (len(truths) == len(labels) == n):
+        raise ValueError("%s: %d truths and %d labels for %d videos" % (who, len(truths), len(labels), n))
+    return truths, labels
+
+
 class ClipEngine(PlanEngine):
     """What the engines that run decoded uint8 video through the eval plan share (EvalEngine here, detect.DetectEngine): one plan of `bs` clips
     whose first conv reads the clip tensor as the clip kernel writes it, the upload pool behind a copy stream, batch forming (pack on / off),
@@ -310,23 +341,13 @@ class EvalEngine(ClipEngine):
 
     def check_video(self, frames, truth, label):
         """Refuse (ValueError) a video the engine cannot take, before anything is enqueued or changed.  -> (frames, truth [F,H,W], label)."""
-        v, t = _as_u8(frames, "frames"), _as_u8(truth, "truth")
+        v = _as_u8(frames, "frames")
         if v.dim() != 4 or v.shape[3] != 3 or v.shape[0] < 1:
             raise ValueError("frames: shape %s, expected (F, H, W, 3)" % (tuple(v.shape),))
         F, H, W = (int(s) for s in v.shape[:3])
         if H < self.hw or W < self.hw:
             raise ValueError("frames of %d x %d are smaller than the %d x %d crop" % (H, W, self.hw, self.hw))
-        if t.dim() == 4 and t.shape[3] == 1:
-            t = t.reshape(t.shape[:3])
-        if t.dim() != 3 or tuple(t.shape) != (F, H, W):
-            raise ValueError("truth: shape %s, expected (%d, %d, %d) or (%d, %d, %d, 1)" % (tuple(truth.shape), F, H, W, F, H, W))
-        try:
-            lab = int(label)
-        except (TypeError, ValueError):
-            raise ValueError("label: %r is not a class id" % (label,)) from None
-        if lab != label or not 0 <= lab < self.C:
-            raise ValueError("label: %r outside [0, %d)" % (label, self.C))
-        return v, t, lab
+        return v, check_truth("add_video", truth, F, H, W), check_label("add_video", label, self.C)
 
     def add_video(self, frames_u8, truth_u8, label):
         """One video: frames [F,H,W,3] uint8, truth [F,H,W] or [F,H,W,1] uint8 (numpy, host tensor or device tensor), class id.  Uploaded through

@@ -510,7 +510,7 @@ def val_metrics(output, loc_msk, predicted_action, action, record=None, ws=None)
 
 def decode_val_record(rec):
     """One record (host int32 array, numpy or torch) -> dict: the eight float scalars by name, n_correct, B, counts int32 [B][3]."""
-    r = np.ascontiguousarray(rec.cpu().numpy() if torch.is_tensor(rec) else rec, dtype=np.int32)
+    r = _host_words(rec)
     B = int(r[9])
     out = {k: float(v) for k, v in zip(VAL_SCALARS, r[:8].view(np.float32))}
     out.update(n_correct=int(r[8]), B=B, counts=r[VAL_HEAD:VAL_HEAD + 3 * B].reshape(B, 3).copy())
@@ -555,13 +555,113 @@ def clip_from_u8_masks(video, span, h0, w0, maskframes, valid, S=224):
     return data, aug, mask, mask_cls
 
 
+def _operand(who, name, t, dtypes, n=None, dev=None, dim=None, exact=True, what=""):
+    """The operand check of the eval / detect wrappers.  The library refuses nulls, ranges, alignment and the sizes it is told; what it cannot
+    see behind a pointer is checked here: `t` is a tensor, of one of `dtypes`, contiguous, of exactly (exact=False: at least) n elements, of
+    `dim` dimensions (an int, or a tuple of the allowed ones) and on `dev` -- n, dim and dev where they are given -- or ValueError naming the
+    wrapper and the operand (`what`: the layout or the shape, for the message).  -> t."""
+    if (isinstance(t, torch.Tensor) and (t.dtype in dtypes if type(dtypes) is tuple else t.dtype == dtypes) and t.is_contiguous()
+            and (n is None or (t.numel() == n if exact else t.numel() >= n)) and (dim is None or (t.dim() in dim if type(dim) is tuple else t.dim() == dim))
+            and (dev is None or t.device == dev)):
+        return t                                                       # (every launch passes here: nothing is formatted on the way)
+    raise ValueError("%s: %s must be a contiguous %s tensor%s%s%s%s" % (
+        who, name, str(dtypes).replace("torch.", ""), "" if dim is None else " of %s dimensions" % (dim,),
+        "" if n is None else " of %s %d elements" % ("exactly" if exact else "at least", n), "" if dev is None else " on %s" % dev,
+        what and " (%s)" % (what if isinstance(what, str) else list(what))))
+
+
+def _frames(who, name, t, dtypes=torch.uint8):
+    """A map the wrapper reads its sizes from: _operand with three dimensions -> F, H, W."""
+    return (int(v) for v in _operand(who, name, t, dtypes, dim=3, what="[F,H,W]").shape)
+
+
+def _buffer(who, name, t, shape, dtypes, dev, fill=True, exact=True, n=None):
+    """A tensor the launch writes: a given one checked (_operand: n elements, by default those of `shape`, on dev), a missing one made on dev
+    with `shape` and the first of `dtypes`, zero-filled -- fill=False: as the allocator leaves it, for a launch that writes all of it."""
+    if t is None:
+        return (torch.zeros if fill else torch.empty)(shape, dtype=dtypes[0] if isinstance(dtypes, tuple) else dtypes, device=dev)
+    if n is None:
+        n = 1
+        for s in shape:
+            n *= int(s)
+    return _operand(who, name, t, dtypes, n, dev, exact=exact, what=shape)
+
+
+def _workspace(who, ws, need, dev, ws_call, any_dtype=False):
+    """The scratch of a launch that needs `need` bytes (ws_call: the size function, for the message): a given one checked -- contiguous uint8 of
+    at least `need` elements on dev; any_dtype=True (the detect_frames family): any dtype, by its bytes -- a missing one made, None for no
+    bytes."""
+    if ws is None:
+        return torch.empty(need, dtype=torch.uint8, device=dev) if need > 0 else None
+    if any_dtype and torch.is_tensor(ws):
+        return _operand(who, "ws", ws, ws.dtype, -(-need // ws.element_size()), dev, exact=False, what=ws_call)
+    return _operand(who, "ws", ws, torch.uint8, need, dev, exact=False, what=ws_call)
+
+
+def _ws_bytes(name, limits, *args, tail=()):
+    """pc_<name>(*args), host arithmetic in the library -> the bytes of workspace; ValueError (`limits` % (args + tail): what the sizes must
+    keep to) where it answers -1."""
+    n = int(getattr(capi.lib(), "pc_" + name)(*map(int, args)))
+    if n < 0:
+        raise ValueError("%s: %s" % (name, limits % (args + tail)))
+    return n
+
+
+def _frame_range(who, F, f0, nf, refuse=True):
+    """The frames f0 .. f0 + nf - 1 of F (nf=None: all from f0 on) -> f0, nf as ints.  refuse=False leaves a range outside the F frames to the
+    library (RuntimeError); else it is a ValueError here, in front of the buffers the range sizes."""
+    f0 = int(f0)
+    nf = F - f0 if nf is None else int(nf)
+    if refuse and (f0 < 0 or nf < 1 or f0 + nf > F):
+        raise ValueError("%s: frames f0 = %d, nf = %d outside the %d of the map" % (who, f0, nf, F))
+    return f0, nf
+
+
+def _bound(who, name, v, hi):
+    """A count the buffers are sized by -> int(v) in 1..hi, or ValueError."""
+    v = int(v)
+    if not 1 <= v <= hi:
+        raise ValueError("%s: %s = %d outside 1..%d" % (who, name, v, hi))
+    return v
+
+
+def _host_words(x, dtype=np.int32):
+    """What the decode_* functions take (a host array, numpy or torch) -> contiguous numpy of `dtype` (None: its own)."""
+    return np.ascontiguousarray(x.cpu().numpy() if torch.is_tensor(x) else x, dtype=dtype)
+
+
+_HOST_TABLES = {}
+
+
+def _host_table(entry, args, device=None, refuse=None):
+    """A table the library computes on the host, by its size-then-fill protocol: entry(*args, NULL, 0) -> the int32 words it takes, then
+    entry(*args, buffer, words) fills them.  device=None: -> the numpy array.  Else -> the table on that device, cached per (entry, args,
+    device).  Arguments the entry does not take: ValueError(refuse), without one the library's own RuntimeError."""
+    key = (entry, args, device if device is None else str(torch.device(device)))
+    tab = _HOST_TABLES.get(key)
+    if tab is None:
+        fn = getattr(capi.lib(), entry)
+        need = int(fn(*args, None, 0))
+        if need < 0 and refuse:
+            raise ValueError(refuse)
+        if need < 0:
+            capi.check(need)
+        tab = np.zeros(need, np.int32)
+        got = fn(*args, C.c_void_p(tab.ctypes.data), need)
+        assert got == need
+        if device is not None:
+            tab = _HOST_TABLES[key] = torch.from_numpy(tab).to(device)
+    return tab
+
+
 def _u8_video(video, who, truth=None):
     """The video check of the clip-cut wrappers (and the truth's, where one comes with it) -> F, H, W."""
-    if video.dtype != torch.uint8 or video.dim() != 4 or video.shape[3] != 3 or not video.is_contiguous():
+    if _operand(who, "video", video, torch.uint8, dim=4, what="[F,H,W,3] frames").shape[3] != 3:
         raise ValueError("%s: contiguous uint8 [F,H,W,3] frames" % who)
-    if truth is not None and (truth.dtype != torch.uint8 or not truth.is_contiguous() or truth.numel() != video.numel() // 3
-                              or tuple(truth.shape[:3]) != tuple(video.shape[:3])):
-        raise ValueError("%s: truth must be contiguous uint8 [F,H,W] of the video's size" % who)
+    if truth is not None:
+        _operand(who, "truth", truth, torch.uint8, video.numel() // 3, what="[F,H,W] of the video's size")
+        if tuple(truth.shape[:3]) != tuple(video.shape[:3]):
+            raise ValueError("%s: truth must be contiguous uint8 [F,H,W] of the video's size" % who)
     return (int(v) for v in video.shape[:3])
 
 
@@ -574,13 +674,11 @@ def _starts_table(starts):
 def truth_frame_flags(truth, h0, w0, S, flags=None):
     """pc_truth_frame_flags: truth uint8 device [F,H,W] -> int32 [F], the non-zero truth pixels of each frame inside the S x S crop at (h0, w0).
     flags: an int32 device tensor of at least F elements to write into."""
-    if truth.dtype != torch.uint8 or truth.dim() != 3 or not truth.is_contiguous():
-        raise ValueError("truth_frame_flags: contiguous uint8 [F,H,W] truth")
-    F, H, W = (int(v) for v in truth.shape)
+    F, H, W = _frames("truth_frame_flags", "truth", truth)
     if flags is None:
         flags = torch.empty(F, dtype=torch.int32, device=truth.device)
-    elif flags.dtype != torch.int32 or not flags.is_contiguous() or flags.numel() < F:
-        raise ValueError("truth_frame_flags: flags must be contiguous int32 with at least %d elements" % F)
+    else:
+        _operand("truth_frame_flags", "flags", flags, torch.int32, F, exact=False)
     capi.call("pc_truth_frame_flags", ptr(truth), F, H, W, int(h0), int(w0), int(S), ptr(flags), stream())
     return flags[:F]
 
@@ -591,22 +689,17 @@ def eval_clips_from_u8(video, truth, h0, w0, S, starts, f_skip=2, out=None):
     float32 device tensors with room for n clips -- a batch's place in the plan's clip tensor -- instead of fresh ones."""
     F, H, W = _u8_video(video, "eval_clips_from_u8", truth)
     st, n = _starts_table(starts)
-    if out is None:
-        data = torch.empty(n, 8, S, S, 4, device=video.device); gt = torch.empty(n, 8, S, S, device=video.device)
-    else:
-        data, gt = out
-        for t, n_ in ((data, 32 * S * S), (gt, 8 * S * S)):
-            if t.dtype != torch.float32 or not t.is_contiguous() or t.numel() < n * n_ or t.device != video.device:
-                raise ValueError("eval_clips_from_u8: out tensors must be contiguous float32 device tensors of at least n*8*S*S*4 / n*8*S*S elements")
+    data, gt = (None, None) if out is None else out
+    data = _buffer("eval_clips_from_u8", "out[0]", data, (n, 8, S, S, 4), torch.float32, video.device, fill=False, exact=False)
+    gt = _buffer("eval_clips_from_u8", "out[1]", gt, (n, 8, S, S), torch.float32, video.device, fill=False, exact=False)
     capi.call("pc_eval_clips_from_u8", ptr(video), ptr(truth), F, H, W, int(h0), int(w0), int(S), st, n, int(f_skip), ptr(data), ptr(gt), stream())
     return data, gt
 
 
 def video_vote(pred, label, n_correct):
     """pc_video_vote: n_correct (int32 device, 1 element) += argmax(mean(pred, axis=0)) == label; pred contiguous float32 device [n,C]."""
-    if pred.dtype != torch.float32 or pred.dim() != 2 or not pred.is_contiguous():
-        raise ValueError("video_vote: contiguous float32 [n,C] scores")
-    if n_correct.dtype != torch.int32 or n_correct.numel() < 1:
+    _operand("video_vote", "pred", pred, torch.float32, dim=2, what="[n,C] scores")
+    if n_correct.dtype != torch.int32 or n_correct.numel() < 1:      # only its first element is touched: any stride will do
         raise ValueError("video_vote: n_correct must be an int32 device tensor")
     capi.call("pc_video_vote", ptr(pred), int(pred.shape[0]), int(pred.shape[1]), int(label), ptr(n_correct), stream())
 
@@ -616,10 +709,7 @@ def clips_from_u8(video, h0, w0, S, starts, f_skip=2, out=None):
     -> data [n,8,S,S,4] float32 (r, g, b, 0).  out: a contiguous float32 device tensor with room for n clips to write into."""
     F, H, W = _u8_video(video, "clips_from_u8")
     st, n = _starts_table(starts)
-    if out is None:
-        out = torch.empty(n, 8, S, S, 4, device=video.device)
-    elif out.dtype != torch.float32 or not out.is_contiguous() or out.numel() < n * 32 * S * S or out.device != video.device:
-        raise ValueError("clips_from_u8: out must be a contiguous float32 device tensor of at least n*8*S*S*4 elements")
+    out = _buffer("clips_from_u8", "out", out, (n, 8, S, S, 4), torch.float32, video.device, fill=False, exact=False)
     capi.call("pc_clips_from_u8", ptr(video), F, H, W, int(h0), int(w0), int(S), st, n, int(f_skip), ptr(out), stream())
     return out
 
@@ -631,22 +721,14 @@ def detect_frames_ws_bytes(n, S):
     return int(capi.lib().pc_detect_frames_ws_bytes(int(n), int(S)))
 
 
-def _detect_buffers(who, dev, F, H, W, mask, rec, ws, want_mask, ws_call, need):
-    """The mask / rec / ws of detect_frames and detect_frames_views: given ones checked, missing ones made (mask and rec zero-filled; no mask
-    with want_mask=False).  ws_call names the size function in the message; need: its value.  -> mask, rec, ws."""
-    if mask is None and want_mask:
-        mask = torch.zeros(F, H, W, dtype=torch.uint8, device=dev)
-    if mask is not None and (mask.dtype != torch.uint8 or not mask.is_contiguous() or mask.numel() != F * H * W or mask.device != dev):
-        raise ValueError("%s: mask must be a contiguous uint8 device tensor [F,H,W]" % who)
-    if rec is None:
-        rec = torch.zeros(F, DETECT_REC_WORDS, dtype=torch.int32, device=dev)
-    elif rec.dtype != torch.int32 or not rec.is_contiguous() or rec.numel() != F * DETECT_REC_WORDS or rec.device != dev:
-        raise ValueError("%s: rec must be a contiguous int32 device tensor [F,8]" % who)
-    if ws is None and need > 0:
-        ws = torch.empty(need, dtype=torch.uint8, device=dev)
-    elif ws is not None and (not ws.is_contiguous() or ws.numel() * ws.element_size() < need or ws.device != dev):
-        raise ValueError("%s: ws must hold %s = %d bytes" % (who, ws_call, need))
-    return mask, rec, ws
+def _detect_buffers(who, dev, F, H, W, mask, rec, ws, want_mask, ws_call, need, any_ws=True):
+    """The mask / rec / ws of the detect_frames family and prob_cut: given ones checked, missing ones made (mask and rec zero-filled; no mask
+    with want_mask=False).  ws_call names the size function in the message; need: its value; any_ws: _workspace's any_dtype.
+    -> mask, rec, ws."""
+    if mask is not None or want_mask:
+        mask = _buffer(who, "mask", mask, (F, H, W), torch.uint8, dev)
+    rec = _buffer(who, "rec", rec, (F, DETECT_REC_WORDS), torch.int32, dev)
+    return mask, rec, _workspace(who, ws, need, dev, ws_call, any_ws)
 
 
 def detect_frames(logits, starts, F, H, W, h0, w0, f_skip=2, row0=0, mask=None, rec=None, ws=None, want_mask=True):
@@ -672,18 +754,23 @@ def _view_table(views, who):
     return (C.c_int32 * (3 * len(rows)))(*[x for r in rows for x in r]), len(rows)
 
 
+def _view_stride(who, view_stride, n):
+    """The clip slots between two views of one clip (default: the n clips) -> int, or ValueError below n."""
+    stride = n if view_stride is None else int(view_stride)
+    if stride < n:
+        raise ValueError("%s: view_stride = %d below the %d clips" % (who, stride, n))
+    return stride
+
+
 def _clip_logits(who, logits, views, starts, view_stride):
     """The opening of the entries that take a forward's logits: contiguous float32 (S from the last dim) that hold view v of clip c at clip slot
     v * view_stride + c (default stride: n = len(starts)).  views=None: the centre entry, which has no view table and one view.
     -> (view table or None, V, starts table, n, S, view_stride)."""
-    if logits.dtype != torch.float32 or not logits.is_contiguous():
-        raise ValueError("%s: contiguous float32 logits" % who)
+    _operand(who, "logits", logits, torch.float32)
     tab, V = (None, 1) if views is None else _view_table(views, who)
     st, n = _starts_table(starts)
     S = int(logits.shape[-1])
-    stride = n if view_stride is None else int(view_stride)
-    if stride < n:
-        raise ValueError("%s: view_stride = %d below the %d clips" % (who, stride, n))
+    stride = _view_stride(who, view_stride, n)
     if int(logits.shape[-2]) != S or logits.numel() < ((V - 1) * stride + n) * 8 * S * S:
         if views is None:
             raise ValueError("%s: logits %s do not hold %d clips of 8 x %d x %d" % (who, tuple(logits.shape), n, S, S))
@@ -698,13 +785,9 @@ def clips_from_u8_views(video, views, S, starts, f_skip=2, view_stride=None, out
     F, H, W = _u8_video(video, "clips_from_u8_views")
     tab, V = _view_table(views, "clips_from_u8_views")
     st, n = _starts_table(starts)
-    stride = n if view_stride is None else int(view_stride)
-    if stride < n:
-        raise ValueError("clips_from_u8_views: view_stride = %d below the %d clips" % (stride, n))
-    if out is None:
-        out = torch.empty(V, stride, 8, S, S, 4, device=video.device)
-    elif out.dtype != torch.float32 or not out.is_contiguous() or out.numel() < ((V - 1) * stride + n) * 32 * S * S or out.device != video.device:
-        raise ValueError("clips_from_u8_views: out must be a contiguous float32 device tensor of at least ((V-1)*view_stride+n)*8*S*S*4 elements")
+    stride = _view_stride("clips_from_u8_views", view_stride, n)
+    out = _buffer("clips_from_u8_views", "out", out, (V, stride, 8, S, S, 4), torch.float32, video.device, fill=False, exact=False,
+                  n=((V - 1) * stride + n) * 32 * S * S)
     capi.call("pc_clips_from_u8_views", ptr(video), F, H, W, int(S), tab, V, stride, st, n, int(f_skip), ptr(out), stream())
     return out
 
@@ -725,24 +808,11 @@ def detect_frames_views(logits, views, starts, F, H, W, f_skip=2, view_stride=No
     return mask, rec
 
 
-_RESAMPLE_TABS = {}
-
-
 def resample_tables(Hs, Ws, H, W, device):
     """pc_resample_tables(Hs, Ws, H, W) on the device: int32 [2 * (H + W)], rows [H][2] then columns [W][2] of (first tap, float32 bits of the
     second tap's weight) that take a working frame of Hs x Ws back to the native H x W.  Host arithmetic in the library, cached per sizes and
     device."""
-    key = (int(Hs), int(Ws), int(H), int(W), str(torch.device(device)))
-    tab = _RESAMPLE_TABS.get(key)
-    if tab is None:
-        need = capi.lib().pc_resample_tables(key[0], key[1], key[2], key[3], None, 0)
-        if need < 0:
-            capi.check(int(need))
-        host = np.zeros(int(need), np.int32)
-        got = capi.lib().pc_resample_tables(key[0], key[1], key[2], key[3], C.c_void_p(host.ctypes.data), int(need))
-        assert got == need
-        tab = _RESAMPLE_TABS[key] = torch.from_numpy(host).to(device)
-    return tab
+    return _host_table("pc_resample_tables", (int(Hs), int(Ws), int(H), int(W)), device)
 
 
 def _native_buffers(who, dev, F, H, W, Hs, Ws, mask, prob, rec, ws, want_mask, ws_call, need):
@@ -750,7 +820,7 @@ def _native_buffers(who, dev, F, H, W, Hs, Ws, mask, prob, rec, ws, want_mask, w
     the tables on the device.  -> mask, prob, rec, ws, dev_tab."""
     mask, rec, ws = _detect_buffers(who, dev, F, H, W, mask, rec, ws, want_mask, ws_call, need)
     if prob is not None:
-        prob = _prob_tensor(who, prob, F, H, W, dev)
+        _buffer(who, "prob", prob, (F, H, W), _PROB_DTYPES, dev)
     return mask, prob, rec, ws, resample_tables(Hs, Ws, H, W, dev)
 
 
@@ -783,14 +853,8 @@ def clip_hop_starts(F, f_skip, hop):
     """pc_clip_hop_starts: the clip starts of a video of F frames cut into windows of 8 * f_skip frames every `hop` frames (host arithmetic
     in the library; csrc/cliphop.h states the rule) -> list of ints.  ValueError for F < 1 or a hop that is no multiple of f_skip in
     [f_skip, 8 * f_skip]."""
-    F, f_skip, hop = int(F), int(f_skip), int(hop)
-    need = int(capi.lib().pc_clip_hop_starts(F, f_skip, hop, None, 0))
-    if need < 0:
-        raise ValueError("clip_hop_starts: F = %d, f_skip = %d, hop = %d" % (F, f_skip, hop))
-    host = np.zeros(need, np.int32)
-    got = capi.lib().pc_clip_hop_starts(F, f_skip, hop, C.c_void_p(host.ctypes.data), need)
-    assert got == need
-    return host.tolist()
+    args = (int(F), int(f_skip), int(hop))
+    return _host_table("pc_clip_hop_starts", args, refuse="clip_hop_starts: F = %d, f_skip = %d, hop = %d" % args).tolist()
 
 
 def clip_planes_bytes(F, Hs, Ws, f_skip, hop):
@@ -804,8 +868,7 @@ def clip_plane_views(planes, F, Hs, Ws, f_skip, hop):
     need = clip_planes_bytes(F, Hs, Ws, f_skip, hop)
     if need < 0:
         raise ValueError("clip_planes: %d frames of %d x %d, f_skip = %d, hop = %d" % (F, Hs, Ws, f_skip, hop))
-    if planes.dtype != torch.uint8 or not planes.is_contiguous() or planes.numel() < need:
-        raise ValueError("clip_planes: planes must be a contiguous uint8 device tensor of clip_planes_bytes(F, Hs, Ws, f_skip, hop) = %d bytes" % need)
+    _operand("clip_planes", "planes", planes, torch.uint8, need, exact=False, what="clip_planes_bytes(F, Hs, Ws, f_skip, hop) = %d bytes" % need)
     ps = clip_planes_bytes(1, Hs, Ws, 1, 8) // 5                    # the library's own stride: one frame in one slot is 4 * ps + ps bytes
     M = (need - ps) // (4 * int(F) * ps)
     return planes[:need - ps].view(torch.float32).view(M, int(F), ps), planes[need - ps:need]
@@ -839,8 +902,8 @@ def detect_frames_planes(planes, F, H, W, Hs, Ws, V, f_skip, hop, f0=0, nf=None,
     PLANES_MAX_FRAMES; default: the rest of the video) detected at native size from the mean of the windows that hold each frame.
     -> (mask uint8 [F,H,W] or None, rec int32 [F,8]) as detect_frames_scaled, rec[:, 6] = row0 + V * (the first clip that holds the frame);
     prob as there.  Given tensors are written in place -- only the frames of the range -- fresh ones are zero-filled first."""
-    F, H, W, Hs, Ws, f0 = int(F), int(H), int(W), int(Hs), int(Ws), int(f0)
-    nf = F - f0 if nf is None else int(nf)
+    F, H, W, Hs, Ws = int(F), int(H), int(W), int(Hs), int(Ws)
+    f0, nf = _frame_range("detect_frames_planes", F, f0, nf, refuse=False)
     plane, cov = clip_plane_views(planes, F, Hs, Ws, f_skip, hop)
     need = detect_frames_planes_ws_bytes(nf, H, W)
     if need < 0 or f0 < 0 or f0 + nf > F:
@@ -854,7 +917,7 @@ def detect_frames_planes(planes, F, H, W, Hs, Ws, V, f_skip, hop, f0=0, nf=None,
 
 def decode_detect_records(rec):
     """Host int32 [F,8] records (numpy or torch) -> (counts int32 [F], boxes int32 [F,4] = x0, y0, x1, y1, frame_scores float32 [F], rows int32 [F])."""
-    r = np.ascontiguousarray(rec.cpu().numpy() if torch.is_tensor(rec) else rec, dtype=np.int32).reshape(-1, DETECT_REC_WORDS)
+    r = _host_words(rec).reshape(-1, DETECT_REC_WORDS)
     return r[:, 0].copy(), r[:, 1:5].copy(), r[:, 5].copy().view(np.float32), r[:, 6].copy()
 
 
@@ -867,23 +930,13 @@ def frame_instances(mask, f0=0, nf=None, conn=8, min_area=1, K=8, inst=None, ima
     """pc_frame_instances: mask contiguous uint8 device [F,H,W] (any non-zero byte is foreground) -> (inst int32 [F, 4 + 6K], imap uint8 [F,H,W]
     or None): the connected components (conn 4 or 8) of the frames f0 .. f0 + nf - 1 (default: all from f0 on), ranked by area.  Given tensors
     are written in place -- only those frames -- fresh ones are zero-filled first.  want_imap=False with imap=None: records only."""
-    if mask.dtype != torch.uint8 or mask.dim() != 3 or not mask.is_contiguous():
-        raise ValueError("frame_instances: contiguous uint8 [F,H,W] mask")
-    F, H, W = (int(v) for v in mask.shape)
-    K = int(K)
-    if not 1 <= K <= INST_MAX_K:
-        raise ValueError("frame_instances: K = %d outside 1..%d" % (K, INST_MAX_K))
-    words = INST_HDR + K * INST_WORDS
-    nf = F - int(f0) if nf is None else int(nf)
-    if inst is None:
-        inst = torch.zeros(F, words, dtype=torch.int32, device=mask.device)
-    elif inst.dtype != torch.int32 or not inst.is_contiguous() or inst.numel() != F * words or inst.device != mask.device:
-        raise ValueError("frame_instances: inst must be a contiguous int32 device tensor [F, %d]" % words)
-    if imap is None and want_imap:
-        imap = torch.zeros(F, H, W, dtype=torch.uint8, device=mask.device)
-    if imap is not None and (imap.dtype != torch.uint8 or not imap.is_contiguous() or imap.numel() != F * H * W or imap.device != mask.device):
-        raise ValueError("frame_instances: imap must be a contiguous uint8 device tensor [F,H,W]")
-    capi.call("pc_frame_instances", ptr(mask), F, H, W, int(f0), nf, int(conn), int(min_area), K, ptr(inst), ptr(imap), stream())
+    F, H, W = _frames("frame_instances", "mask", mask)
+    K = _bound("frame_instances", "K", K, INST_MAX_K)
+    f0, nf = _frame_range("frame_instances", F, f0, nf, refuse=False)
+    inst = _buffer("frame_instances", "inst", inst, (F, INST_HDR + K * INST_WORDS), torch.int32, mask.device)
+    if imap is not None or want_imap:
+        imap = _buffer("frame_instances", "imap", imap, (F, H, W), torch.uint8, mask.device)
+    capi.call("pc_frame_instances", ptr(mask), F, H, W, f0, nf, int(conn), int(min_area), K, ptr(inst), ptr(imap), stream())
     return inst, imap
 
 
@@ -891,23 +944,16 @@ def decode_instances(words, K):
     """Host int32 [F, 4 + 6K] records (numpy or torch) -> (n_comp int32 [F], kept int32 [F], n_runs int32 [F], flags int32 [F], areas int32 [F,K],
     boxes int32 [F,K,4] = x0, y0, x1, y1, first int32 [F,K])."""
     K = int(K)
-    r = np.ascontiguousarray(words.cpu().numpy() if torch.is_tensor(words) else words, dtype=np.int32).reshape(-1, INST_HDR + K * INST_WORDS)
+    r = _host_words(words).reshape(-1, INST_HDR + K * INST_WORDS)
     slots = r[:, INST_HDR:].reshape(-1, K, INST_WORDS)
     return r[:, 0].copy(), r[:, 1].copy(), r[:, 2].copy(), r[:, 3].copy(), slots[:, :, 0].copy(), slots[:, :, 1:5].copy(), slots[:, :, 5].copy()
 
 
 PROB_ONE, SCORE_WORDS = 65535, 3           # PC_PROB_ONE / PC_SCORE_WORDS of include/picons.h: probability 1.0 as uint16; lo, hi, npix of a slot
+# The probability map of frame_probs / instance_scores: a contiguous 16-bit integer device tensor [F,H,W], np.uint16 on the host
+# (prob.cpu().numpy().view(np.uint16)).  A missing one is made zero-filled as the first of these, int16: the dtype every torch build can
+# allocate and copy.
 _PROB_DTYPES = tuple(d for d in (torch.int16, getattr(torch, "uint16", None)) if d is not None)
-
-
-def _prob_tensor(who, prob, F, H, W, dev):
-    """The probability map of frame_probs / instance_scores: a contiguous 16-bit integer device tensor [F,H,W], np.uint16 on the host
-    (prob.cpu().numpy().view(np.uint16)).  A missing one is made zero-filled (int16: the dtype every torch build can allocate and copy)."""
-    if prob is None:
-        return torch.zeros(F, H, W, dtype=torch.int16, device=dev)
-    if prob.dtype not in _PROB_DTYPES or not prob.is_contiguous() or prob.numel() != F * H * W or prob.device != dev:
-        raise ValueError("%s: prob must be a contiguous 16-bit integer device tensor [F,H,W]" % who)
-    return prob
 
 
 def frame_probs(logits, views, starts, F, H, W, f_skip=2, view_stride=None, prob=None):
@@ -915,7 +961,7 @@ def frame_probs(logits, views, starts, F, H, W, f_skip=2, view_stride=None, prob
     device [F,H,W]: round(65535 * sigmoid(merged logit)) as uint16, 0 where no view covers the pixel.  A given tensor is written in place
     -- only the frames the clips address -- a fresh one is zero-filled first."""
     tab, V, st, n, S, stride = _clip_logits("frame_probs", logits, views, starts, view_stride)
-    prob = _prob_tensor("frame_probs", prob, int(F), int(H), int(W), logits.device)
+    prob = _buffer("frame_probs", "prob", prob, (int(F), int(H), int(W)), _PROB_DTYPES, logits.device)
     capi.call("pc_frame_probs", ptr(logits), int(F), int(H), int(W), S, tab, V, stride, st, n, int(f_skip), ptr(prob), stream())
     return prob
 
@@ -924,29 +970,21 @@ def instance_scores(imap, prob, K, f0=0, nf=None, out=None):
     """pc_instance_scores: imap contiguous uint8 device [F,H,W] (frame_instances' map of ranks) and prob (frame_probs') -> out int32
     [F, 3 * (K + 1)]: per slot the 64-bit sum of prob over its pixels as (lo, hi) and their number, for the frames f0 .. f0 + nf - 1
     (default: all from f0 on).  A given out is written in place -- only those frames -- a fresh one is zero-filled first."""
-    if imap.dtype != torch.uint8 or imap.dim() != 3 or not imap.is_contiguous():
-        raise ValueError("instance_scores: contiguous uint8 [F,H,W] imap")
-    F, H, W = (int(v) for v in imap.shape)
-    K = int(K)
-    if not 1 <= K <= INST_MAX_K:
-        raise ValueError("instance_scores: K = %d outside 1..%d" % (K, INST_MAX_K))
+    F, H, W = _frames("instance_scores", "imap", imap)
+    K = _bound("instance_scores", "K", K, INST_MAX_K)
     if prob is None:
         raise ValueError("instance_scores: prob is missing")
-    prob = _prob_tensor("instance_scores", prob, F, H, W, imap.device)
-    words = SCORE_WORDS * (K + 1)
-    nf = F - int(f0) if nf is None else int(nf)
-    if out is None:
-        out = torch.zeros(F, words, dtype=torch.int32, device=imap.device)
-    elif out.dtype != torch.int32 or not out.is_contiguous() or out.numel() != F * words or out.device != imap.device:
-        raise ValueError("instance_scores: out must be a contiguous int32 device tensor [F, %d]" % words)
-    capi.call("pc_instance_scores", ptr(imap), ptr(prob), F, H, W, int(f0), nf, K, ptr(out), stream())
+    _buffer("instance_scores", "prob", prob, (F, H, W), _PROB_DTYPES, imap.device)
+    f0, nf = _frame_range("instance_scores", F, f0, nf, refuse=False)
+    out = _buffer("instance_scores", "out", out, (F, SCORE_WORDS * (K + 1)), torch.int32, imap.device)
+    capi.call("pc_instance_scores", ptr(imap), ptr(prob), F, H, W, f0, nf, K, ptr(out), stream())
     return out
 
 
 def decode_instance_scores(words, K):
     """Host int32 [F, 3 * (K + 1)] records (numpy or torch) -> (sums int64 [F, K + 1], npix int32 [F, K + 1]); slot K: all other foreground."""
     K = int(K)
-    r = np.ascontiguousarray(words.cpu().numpy() if torch.is_tensor(words) else words, dtype=np.int32).reshape(-1, K + 1, SCORE_WORDS)
+    r = _host_words(words).reshape(-1, K + 1, SCORE_WORDS)
     lo, hi = r[:, :, 0].astype(np.int64) & 0xffffffff, r[:, :, 1].astype(np.int64) & 0xffffffff
     return (hi << 32) | lo, r[:, :, 2].copy()
 
@@ -959,29 +997,18 @@ def instance_overlaps(imap, K, L=1, f0=0, nf=None, out=None):
     out[f, l, a, b] the pixels whose slot is a in frame f and b in frame f + l + 1 (slot K: all other foreground; zeros where that frame
     does not exist), for the frames f0 .. f0 + nf - 1 (default: all from f0 on).  A given out is written in place -- only those frames -- a
     fresh one is zero-filled first."""
-    if imap.dtype != torch.uint8 or imap.dim() != 3 or not imap.is_contiguous():
-        raise ValueError("instance_overlaps: contiguous uint8 [F,H,W] imap")
-    F, H, W = (int(v) for v in imap.shape)
-    K, L = int(K), int(L)
-    if not 1 <= K <= INST_MAX_K:
-        raise ValueError("instance_overlaps: K = %d outside 1..%d" % (K, INST_MAX_K))
-    if not 1 <= L <= LINK_MAX_LAGS:
-        raise ValueError("instance_overlaps: L = %d outside 1..%d" % (L, LINK_MAX_LAGS))
-    words = L * (K + 1) * (K + 1)
-    nf = F - int(f0) if nf is None else int(nf)
-    if out is None:
-        out = torch.zeros(F, L, K + 1, K + 1, dtype=torch.int32, device=imap.device)
-    elif out.dtype != torch.int32 or not out.is_contiguous() or out.numel() != F * words or out.device != imap.device:
-        raise ValueError("instance_overlaps: out must be a contiguous int32 device tensor [F, %d, %d, %d]" % (L, K + 1, K + 1))
-    capi.call("pc_instance_overlaps", ptr(imap), F, H, W, int(f0), nf, K, L, ptr(out), stream())
+    F, H, W = _frames("instance_overlaps", "imap", imap)
+    K, L = _bound("instance_overlaps", "K", K, INST_MAX_K), _bound("instance_overlaps", "L", L, LINK_MAX_LAGS)
+    f0, nf = _frame_range("instance_overlaps", F, f0, nf, refuse=False)
+    out = _buffer("instance_overlaps", "out", out, (F, L, K + 1, K + 1), torch.int32, imap.device)
+    capi.call("pc_instance_overlaps", ptr(imap), F, H, W, f0, nf, K, L, ptr(out), stream())
     return out
 
 
 def decode_instance_overlaps(words, K, L):
     """Host int32 records of F * L * (K + 1)^2 words (numpy or torch, any shape) -> int32 [F, L, K + 1, K + 1]."""
     K, L = int(K), int(L)
-    r = np.ascontiguousarray(words.cpu().numpy() if torch.is_tensor(words) else words, dtype=np.int32)
-    return r.reshape(-1, L, K + 1, K + 1).copy()
+    return _host_words(words).reshape(-1, L, K + 1, K + 1).copy()
 
 
 RUN_WORDS = 2                              # PC_RUN_WORDS of include/picons.h: a run is (row | value << 24, x0 | x1 << 16)
@@ -990,13 +1017,8 @@ RUN_MAX_ROWS, RUN_MAX_PIXELS = 1 << 24, (1 << 31) - 1      # what one range of p
 
 def _run_range(who, map, f0, nf):
     """The map and frame range of mask_run_index / mask_runs -> (F, H, W, f0, nf), or ValueError."""
-    if not torch.is_tensor(map) or map.dtype != torch.uint8 or map.dim() != 3 or not map.is_contiguous():
-        raise ValueError("%s: contiguous uint8 [F,H,W] map" % who)
-    F, H, W = (int(v) for v in map.shape)
-    f0 = int(f0)
-    nf = F - f0 if nf is None else int(nf)
-    if f0 < 0 or nf < 1 or f0 + nf > F:
-        raise ValueError("%s: frames f0 = %d, nf = %d outside the %d of the map" % (who, f0, nf, F))
+    F, H, W = _frames(who, "map", map)
+    f0, nf = _frame_range(who, F, f0, nf)
     if H < 1 or not 1 <= W <= 65535 or nf * H > RUN_MAX_ROWS or nf * H * W > RUN_MAX_PIXELS:
         raise ValueError("%s: %d frames of %d x %d: W <= 65535, nf * H <= 2^24 and nf * H * W < 2^31 (export a longer video in ranges)" % (who, nf, H, W))
     return F, H, W, f0, nf
@@ -1007,10 +1029,7 @@ def mask_run_index(map, f0=0, nf=None, index=None):
     from f0 on): index[r] the row runs (maximal horizontal segments of one non-zero byte value) in the rows before row r = (f - f0) * H + y,
     index[nf * H] their total.  A given index is written in place, all of it."""
     F, H, W, f0, nf = _run_range("mask_run_index", map, f0, nf)
-    if index is None:
-        index = torch.empty(nf * H + 1, dtype=torch.int32, device=map.device)
-    elif index.dtype != torch.int32 or not index.is_contiguous() or index.numel() != nf * H + 1 or index.device != map.device:
-        raise ValueError("mask_run_index: index must be a contiguous int32 device tensor [%d]" % (nf * H + 1))
+    index = _buffer("mask_run_index", "index", index, (nf * H + 1,), torch.int32, map.device, fill=False)
     ws = torch.empty(capi.lib().pc_mask_run_ws_bytes(nf, H) // 4, dtype=torch.int32, device=map.device)
     capi.call("pc_mask_run_index", ptr(map), F, H, W, f0, nf, ptr(index), ptr(ws), stream())
     return index
@@ -1022,17 +1041,13 @@ def mask_runs(map, index, f0=0, nf=None, cap=None, runs=None):
     cap=None: the range's total is read from the index -- ONE host wait -- and the tensor holds exactly the runs.  A given cap: no wait; runs
     from cap on are not written (compare index[-1] with cap).  A given runs tensor [cap, 2] is written in place."""
     F, H, W, f0, nf = _run_range("mask_runs", map, f0, nf)
-    if not torch.is_tensor(index) or index.dtype != torch.int32 or not index.is_contiguous() or index.numel() != nf * H + 1 or index.device != map.device:
-        raise ValueError("mask_runs: index must be a contiguous int32 device tensor [%d]" % (nf * H + 1))
+    _operand("mask_runs", "index", index, torch.int32, nf * H + 1, map.device, what="[nf * H + 1]")
     if cap is None:
         cap = int(index[-1].item()) if runs is None else runs.numel() // RUN_WORDS
     cap = int(cap)
     if cap < 0:
         raise ValueError("mask_runs: cap = %d below 0" % cap)
-    if runs is None:
-        runs = torch.empty(cap, RUN_WORDS, dtype=torch.int32, device=map.device)
-    elif runs.dtype != torch.int32 or not runs.is_contiguous() or runs.numel() != cap * RUN_WORDS or runs.device != map.device:
-        raise ValueError("mask_runs: runs must be a contiguous int32 device tensor [%d, %d]" % (cap, RUN_WORDS))
+    runs = _buffer("mask_runs", "runs", runs, (cap, RUN_WORDS), torch.int32, map.device, fill=False)
     capi.call("pc_mask_runs", ptr(map), F, H, W, f0, nf, ptr(index), cap, ptr(runs), stream())
     return runs
 
@@ -1041,7 +1056,7 @@ def decode_mask_runs(runs, nf, H, W):
     """Host runs [n, 2] (numpy or torch, int32 or uint32 words) with rows numbered from 0 over nf frames of H rows -> numpy uint8 [nf, H, W]:
     every run's value on its pixels, 0 elsewhere.  ValueError for a run outside the frames."""
     nf, H, W = int(nf), int(H), int(W)
-    r = np.ascontiguousarray(runs.cpu().numpy() if torch.is_tensor(runs) else runs)
+    r = _host_words(runs, None)
     if r.dtype not in (np.int32, np.uint32) or r.size % RUN_WORDS:
         raise ValueError("decode_mask_runs: runs must be 32-bit words [n, %d], got %s %s" % (RUN_WORDS, r.dtype, r.shape))
     r = r.view(np.uint32).reshape(-1, RUN_WORDS)
@@ -1061,11 +1076,17 @@ CROSS_MAX_SLOTS = 32                       # PC_CROSS_MAX_SLOTS of include/picon
 
 def map_crosstab_ws_bytes(nf, H, W, P, A):
     """pc_map_crosstab_ws_bytes (host arithmetic): the bytes of workspace one map_crosstab call over nf frames of H x W takes."""
-    n = int(capi.lib().pc_map_crosstab_ws_bytes(int(nf), int(H), int(W), int(P), int(A)))
-    if n < 0:
-        raise ValueError("map_crosstab_ws_bytes: nf = %d frames of %d x %d with P = %d, A = %d: nf, H, W >= 1, H * W < 2^31, P and A in 1..%d"
-                         % (nf, H, W, P, A, CROSS_MAX_SLOTS))
-    return n
+    return _ws_bytes("map_crosstab_ws_bytes", "nf = %d frames of %d x %d with P = %d, A = %d: nf, H, W >= 1, H * W < 2^31, P and A in 1..%d",
+                     nf, H, W, P, A, tail=(CROSS_MAX_SLOTS,))
+
+
+def _same_frames(who, a, ta, b, tb, dtypes=torch.uint8):
+    """The two maps [F,H,W] a call holds against each other (ta of `dtypes`, tb uint8): one shape, one device -> F, H, W."""
+    _operand(who, a, ta, dtypes, dim=3, what="[F,H,W]")
+    _operand(who, b, tb, torch.uint8, dim=3, what="[F,H,W]")
+    if ta.shape != tb.shape or ta.device != tb.device:
+        raise ValueError("%s: %s %s and %s %s must have one shape and lie on one device" % (who, a, tuple(ta.shape), b, tuple(tb.shape)))
+    return (int(v) for v in ta.shape)
 
 
 def map_crosstab(pred, truth, P, A, f0=0, nf=None, out=None, ws=None):
@@ -1073,27 +1094,11 @@ def map_crosstab(pred, truth, P, A, f0=0, nf=None, out=None, ws=None):
     pixels of frame f with pred slot p (0 background, v for a byte 1..P, P + 1 for any byte above P) and truth slot a (the same with A),
     cell [0, 0] included, for the frames f0 .. f0 + nf - 1 (default: all from f0 on).  A given out is written in place -- only those frames
     -- a fresh one is zero-filled first.  ws: uint8 device scratch of at least map_crosstab_ws_bytes(nf, H, W, P, A) bytes, made when None."""
-    for name, t in (("pred", pred), ("truth", truth)):
-        if not torch.is_tensor(t) or t.dtype != torch.uint8 or t.dim() != 3 or not t.is_contiguous():
-            raise ValueError("map_crosstab: contiguous uint8 [F,H,W] %s" % name)
-    if pred.shape != truth.shape or pred.device != truth.device:
-        raise ValueError("map_crosstab: pred %s and truth %s must have one shape and lie on one device" % (tuple(pred.shape), tuple(truth.shape)))
-    F, H, W = (int(v) for v in pred.shape)
-    P, A, f0 = int(P), int(A), int(f0)
-    if not 1 <= P <= CROSS_MAX_SLOTS or not 1 <= A <= CROSS_MAX_SLOTS:
-        raise ValueError("map_crosstab: P = %d, A = %d outside 1..%d" % (P, A, CROSS_MAX_SLOTS))
-    nf = F - f0 if nf is None else int(nf)
-    if f0 < 0 or nf < 1 or f0 + nf > F:
-        raise ValueError("map_crosstab: frames f0 = %d, nf = %d outside the %d of the map" % (f0, nf, F))
-    if out is None:
-        out = torch.zeros(F, P + 2, A + 2, dtype=torch.int32, device=pred.device)
-    elif out.dtype != torch.int32 or not out.is_contiguous() or out.numel() != F * (P + 2) * (A + 2) or out.device != pred.device:
-        raise ValueError("map_crosstab: out must be a contiguous int32 device tensor [F, %d, %d]" % (P + 2, A + 2))
-    need = map_crosstab_ws_bytes(nf, H, W, P, A)
-    if ws is None:
-        ws = torch.empty(need, dtype=torch.uint8, device=pred.device)
-    elif ws.dtype != torch.uint8 or not ws.is_contiguous() or ws.numel() < need or ws.device != pred.device:
-        raise ValueError("map_crosstab: ws must be a contiguous uint8 device tensor of at least %d bytes" % need)
+    F, H, W = _same_frames("map_crosstab", "pred", pred, "truth", truth)
+    P, A = _bound("map_crosstab", "P", P, CROSS_MAX_SLOTS), _bound("map_crosstab", "A", A, CROSS_MAX_SLOTS)
+    f0, nf = _frame_range("map_crosstab", F, f0, nf)
+    out = _buffer("map_crosstab", "out", out, (F, P + 2, A + 2), torch.int32, pred.device)
+    ws = _workspace("map_crosstab", ws, map_crosstab_ws_bytes(nf, H, W, P, A), pred.device, "map_crosstab_ws_bytes(nf, H, W, P, A)")
     capi.call("pc_map_crosstab", ptr(pred), ptr(truth), F, H, W, f0, nf, P, A, ptr(out), ptr(ws), stream())
     return out
 
@@ -1101,8 +1106,7 @@ def map_crosstab(pred, truth, P, A, f0=0, nf=None, out=None, ws=None):
 def decode_map_crosstab(words, P, A):
     """Host int32 tables of F * (P + 2) * (A + 2) words (numpy or torch, any shape) -> int32 [F, P + 2, A + 2]."""
     P, A = int(P), int(A)
-    r = np.ascontiguousarray(words.cpu().numpy() if torch.is_tensor(words) else words, dtype=np.int32)
-    return r.reshape(-1, P + 2, A + 2).copy()
+    return _host_words(words).reshape(-1, P + 2, A + 2).copy()
 
 
 SWEEP_MAX_THRESHOLDS = 64                  # PC_SWEEP_MAX_THRESHOLDS of include/picons.h: the threshold words one histogram is split by
@@ -1111,7 +1115,7 @@ SWEEP_MAX_THRESHOLDS = 64                  # PC_SWEEP_MAX_THRESHOLDS of include/
 def _sweep_words(who, words):
     """Threshold words -> contiguous np.uint16 [N]: 1..SWEEP_MAX_THRESHOLDS integers in 1..PROB_ONE, strictly ascending, or ValueError."""
     try:
-        w = np.asarray(words.cpu().numpy() if torch.is_tensor(words) else words)
+        w = np.asarray(words.cpu().numpy() if torch.is_tensor(words) else words)       # (not _host_words: a scalar must stay 0-d to be refused)
     except (TypeError, ValueError):
         raise ValueError("%s: words = %r are not integers" % (who, words)) from None
     if w.ndim != 1 or not 1 <= w.size <= SWEEP_MAX_THRESHOLDS or w.dtype.kind not in "iu":
@@ -1124,11 +1128,8 @@ def _sweep_words(who, words):
 
 def prob_truth_hist_ws_bytes(nf, H, W, N):
     """pc_prob_truth_hist_ws_bytes (host arithmetic): the bytes of workspace one prob_truth_hist call over nf frames of H x W takes."""
-    n = int(capi.lib().pc_prob_truth_hist_ws_bytes(int(nf), int(H), int(W), int(N)))
-    if n < 0:
-        raise ValueError("prob_truth_hist_ws_bytes: nf = %d frames of %d x %d with N = %d: nf, H, W >= 1, H * W < 2^31, N in 1..%d"
-                         % (nf, H, W, N, SWEEP_MAX_THRESHOLDS))
-    return n
+    return _ws_bytes("prob_truth_hist_ws_bytes", "nf = %d frames of %d x %d with N = %d: nf, H, W >= 1, H * W < 2^31, N in 1..%d",
+                     nf, H, W, N, tail=(SWEEP_MAX_THRESHOLDS,))
 
 
 def prob_truth_hist(prob, truth, words, f0=0, nf=None, out=None, ws=None):
@@ -1137,27 +1138,12 @@ def prob_truth_hist(prob, truth, words, f0=0, nf=None, out=None, ws=None):
     truth byte is zero (t = 0) or not (t = 1) and whose probability word has exactly b of the words at or below it, cell [0, 0] included, for
     the frames f0 .. f0 + nf - 1 (default: all from f0 on).  A given out is written in place -- only those frames -- a fresh one is
     zero-filled first.  ws: uint8 device scratch of at least prob_truth_hist_ws_bytes(nf, H, W, N) bytes, made when None."""
-    if not torch.is_tensor(prob) or prob.dtype not in _PROB_DTYPES or prob.dim() != 3 or not prob.is_contiguous():
-        raise ValueError("prob_truth_hist: contiguous 16-bit integer [F,H,W] prob")
-    if not torch.is_tensor(truth) or truth.dtype != torch.uint8 or truth.dim() != 3 or not truth.is_contiguous():
-        raise ValueError("prob_truth_hist: contiguous uint8 [F,H,W] truth")
-    if prob.shape != truth.shape or prob.device != truth.device:
-        raise ValueError("prob_truth_hist: prob %s and truth %s must have one shape and lie on one device" % (tuple(prob.shape), tuple(truth.shape)))
-    F, H, W = (int(v) for v in prob.shape)
+    F, H, W = _same_frames("prob_truth_hist", "prob", prob, "truth", truth, _PROB_DTYPES)
     w = _sweep_words("prob_truth_hist", words)
-    N, f0 = int(w.size), int(f0)
-    nf = F - f0 if nf is None else int(nf)
-    if f0 < 0 or nf < 1 or f0 + nf > F:
-        raise ValueError("prob_truth_hist: frames f0 = %d, nf = %d outside the %d of the map" % (f0, nf, F))
-    if out is None:
-        out = torch.zeros(F, 2, N + 1, dtype=torch.int32, device=prob.device)
-    elif not torch.is_tensor(out) or out.dtype != torch.int32 or not out.is_contiguous() or out.numel() != F * 2 * (N + 1) or out.device != prob.device:
-        raise ValueError("prob_truth_hist: out must be a contiguous int32 device tensor [F, 2, %d]" % (N + 1))
-    need = prob_truth_hist_ws_bytes(nf, H, W, N)
-    if ws is None:
-        ws = torch.empty(need, dtype=torch.uint8, device=prob.device)
-    elif not torch.is_tensor(ws) or ws.dtype != torch.uint8 or not ws.is_contiguous() or ws.numel() < need or ws.device != prob.device:
-        raise ValueError("prob_truth_hist: ws must be a contiguous uint8 device tensor of at least %d bytes" % need)
+    N = int(w.size)
+    f0, nf = _frame_range("prob_truth_hist", F, f0, nf)
+    out = _buffer("prob_truth_hist", "out", out, (F, 2, N + 1), torch.int32, prob.device)
+    ws = _workspace("prob_truth_hist", ws, prob_truth_hist_ws_bytes(nf, H, W, N), prob.device, "prob_truth_hist_ws_bytes(nf, H, W, N)")
     capi.call("pc_prob_truth_hist", ptr(prob), ptr(truth), F, H, W, f0, nf, w.ctypes.data_as(C.c_void_p), N, ptr(out), ptr(ws), stream())
     return out
 
@@ -1165,16 +1151,12 @@ def prob_truth_hist(prob, truth, words, f0=0, nf=None, out=None, ws=None):
 def decode_prob_truth_hist(words, N):
     """Host int32 tables of F * 2 * (N + 1) words (numpy or torch, any shape) -> int32 [F, 2, N + 1]."""
     N = int(N)
-    r = np.ascontiguousarray(words.cpu().numpy() if torch.is_tensor(words) else words, dtype=np.int32)
-    return r.reshape(-1, 2, N + 1).copy()
+    return _host_words(words).reshape(-1, 2, N + 1).copy()
 
 
 def prob_cut_ws_bytes(nf, H, W):
     """pc_prob_cut_ws_bytes (host arithmetic): the bytes of workspace one prob_cut call over nf frames of H x W takes."""
-    n = int(capi.lib().pc_prob_cut_ws_bytes(int(nf), int(H), int(W)))
-    if n < 0:
-        raise ValueError("prob_cut_ws_bytes: nf = %d frames of %d x %d: nf, H, W >= 1, H * W < 2^31" % (nf, H, W))
-    return n
+    return _ws_bytes("prob_cut_ws_bytes", "nf = %d frames of %d x %d: nf, H, W >= 1, H * W < 2^31", nf, H, W)
 
 
 def prob_cut(prob, word, f0=0, nf=None, mask=None, rec=None, ws=None, want_mask=True):
@@ -1184,68 +1166,34 @@ def prob_cut(prob, word, f0=0, nf=None, mask=None, rec=None, ws=None, want_mask=
     the positive pixels / 65535; words 6 and 7 of a record are left as they are.  Given tensors are written in place -- only those frames --
     fresh ones are zero-filled first.  want_mask=False with mask=None: records only.  ws: uint8 device scratch of at least
     prob_cut_ws_bytes(nf, H, W) bytes, made when None."""
-    if not torch.is_tensor(prob) or prob.dtype not in _PROB_DTYPES or prob.dim() != 3 or not prob.is_contiguous() or not prob.is_cuda:
-        raise ValueError("prob_cut: contiguous 16-bit integer [F,H,W] device prob")
+    F, H, W = _frames("prob_cut", "prob", prob, _PROB_DTYPES)
+    if not prob.is_cuda:
+        raise ValueError("prob_cut: prob must be a device tensor")
     if isinstance(word, (bool, np.bool_)) or not isinstance(word, (int, np.integer)) or not 1 <= int(word) <= PROB_ONE:
         raise ValueError("prob_cut: word = %r is no integer in 1..%d" % (word, PROB_ONE))
-    F, H, W = (int(v) for v in prob.shape)
-    f0 = int(f0)
-    nf = F - f0 if nf is None else int(nf)
-    if f0 < 0 or nf < 1 or f0 + nf > F:
-        raise ValueError("prob_cut: frames f0 = %d, nf = %d outside the %d of the map" % (f0, nf, F))
-    dev = prob.device
-    if mask is None and want_mask:
-        mask = torch.zeros(F, H, W, dtype=torch.uint8, device=dev)
-    elif mask is not None and (not torch.is_tensor(mask) or mask.dtype != torch.uint8 or not mask.is_contiguous() or mask.numel() != F * H * W
-                               or mask.device != dev):
-        raise ValueError("prob_cut: mask must be a contiguous uint8 device tensor [F,H,W]")
-    if rec is None:
-        rec = torch.zeros(F, DETECT_REC_WORDS, dtype=torch.int32, device=dev)
-    elif not torch.is_tensor(rec) or rec.dtype != torch.int32 or not rec.is_contiguous() or rec.numel() != F * DETECT_REC_WORDS or rec.device != dev:
-        raise ValueError("prob_cut: rec must be a contiguous int32 device tensor [F,8]")
-    need = prob_cut_ws_bytes(nf, H, W)
-    if ws is None:
-        ws = torch.empty(need, dtype=torch.uint8, device=dev)
-    elif not torch.is_tensor(ws) or ws.dtype != torch.uint8 or not ws.is_contiguous() or ws.numel() < need or ws.device != dev:
-        raise ValueError("prob_cut: ws must be a contiguous uint8 device tensor of at least %d bytes" % need)
+    f0, nf = _frame_range("prob_cut", F, f0, nf)
+    mask, rec, ws = _detect_buffers("prob_cut", prob.device, F, H, W, mask, rec, ws, want_mask, "prob_cut_ws_bytes(nf, H, W)",
+                                    prob_cut_ws_bytes(nf, H, W), any_ws=False)
     capi.call("pc_prob_cut", ptr(prob), F, H, W, f0, nf, int(word), ptr(mask), ptr(rec), ptr(ws), stream())
     return mask, rec
 
 
 def video_class(scores, out=None):
     """pc_video_class: scores contiguous float32 device [n,C] -> float32 device [C + 2]: mean class scores, arg-max (as a float), its mean."""
-    if scores.dtype != torch.float32 or scores.dim() != 2 or not scores.is_contiguous():
-        raise ValueError("video_class: contiguous float32 [n,C] scores")
-    n, C_ = (int(v) for v in scores.shape)
-    if out is None:
-        out = torch.empty(C_ + 2, device=scores.device)
-    elif out.dtype != torch.float32 or not out.is_contiguous() or out.numel() != C_ + 2 or out.device != scores.device:
-        raise ValueError("video_class: out must be a contiguous float32 device tensor of C + 2 elements")
+    n, C_ = (int(v) for v in _operand("video_class", "scores", scores, torch.float32, dim=2, what="[n,C]").shape)
+    out = _buffer("video_class", "out", out, (C_ + 2,), torch.float32, scores.device, fill=False)
     capi.call("pc_video_class", ptr(scores), n, C_, ptr(out), stream())
     return out
-
-
-_RESIZE_TABS = {}
 
 
 def resize_u8(src, Ho, Wo, interpolation, binarize=False):
     """cv2.resize(src, (Wo, Ho), interpolation) on uint8 device images (pc_resize_u8): src [n,H,W,C] or [n,H,W] contiguous;
     interpolation = cv2's flag value (0 nearest, 1 linear, 3 area).  The coordinate / coefficient table is computed on the
     host by the library (pc_resize_tables) and cached on the device per (interpolation, sizes, device)."""
-    if src.dtype != torch.uint8 or not src.is_contiguous() or src.dim() not in (3, 4):
-        raise ValueError("resize_u8: contiguous uint8 [n,H,W,C] or [n,H,W]")
-    n, H, W = int(src.shape[0]), int(src.shape[1]), int(src.shape[2])
+    _operand("resize_u8", "src", src, torch.uint8, dim=(3, 4), what="[n,H,W,C] or [n,H,W]")
+    n, H, W = (int(v) for v in src.shape[:3])
     Cc = int(src.shape[3]) if src.dim() == 4 else 1
-    key = (int(interpolation), H, W, int(Ho), int(Wo), str(src.device))
-    tab = _RESIZE_TABS.get(key)
-    if tab is None:
-        need = capi.lib().pc_resize_tables(int(interpolation), H, W, int(Ho), int(Wo), None, 0)
-        if need < 0:
-            capi.check(int(need))
-        host = np.zeros(int(need), np.int32)
-        got = capi.lib().pc_resize_tables(int(interpolation), H, W, int(Ho), int(Wo), C.c_void_p(host.ctypes.data), int(need))
-        assert got == need
-        tab = _RESIZE_TABS[key] = torch.from_numpy(host).to(src.device)
+    tab = _host_table("pc_resize_tables", (int(interpolation), H, W, int(Ho), int(Wo)), src.device)
     dst = torch.empty((n, int(Ho), int(Wo)) + ((Cc,) if src.dim() == 4 else ()), dtype=torch.uint8, device=src.device)
     capi.call("pc_resize_u8", ptr(src), n, H, W, Cc, int(Ho), int(Wo), ptr(tab), int(bool(binarize)), ptr(dst), stream())
     return dst

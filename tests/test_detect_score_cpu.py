@@ -11,10 +11,11 @@ import subprocess
 
 import numpy as np
 import pytest
+import torch
 
 import __graft_entry__ as ge
 from oracle import evalmetrics as oeval
-from picons_amd import capi, detect, evalmetrics, ops
+from picons_amd import capi, detect, evalmetrics, evalstep, ops
 
 from tests import map_crosstab_ref as ref
 
@@ -241,3 +242,30 @@ def test_score_pass_skips_a_video_without_truth_and_keeps_the_evaluators_keys():
     assert v0.instance_iou().shape == (2, 1, 1) and v0.instance_iou()[0, 0, 0] == 1.0
     empty = detect.score_pass([], [], [], C_)
     assert empty.videos == [] and empty.n_skipped == 0 and empty.result["n_correct"] == 0
+
+
+@pytest.mark.parametrize("who", ["score", "sweep"])
+def test_truth_label_and_count_checks_refuse_what_score_and_sweep_refuse(who):
+    """The bad truths / bad labels of tests/test_detect_score_gpu.py::test_refusals_are_value_errors_before_anything_is_enqueued against the
+    pure functions both calls (and EvalEngine.add_video) check with: ValueError, `who` in front, the word the GPU test matches inside."""
+    F, H, W, C_ = 3, 8, 12, 24
+    every = [np.zeros((F, H, W), np.uint8) for _ in range(3)]
+    for truths, labels, n, word in ((every, [0, 1, 2], 2, "truths"), (every[:2], [0, 1, 2], 3, "truths"), (every, [0, 1], 3, "labels")):
+        with pytest.raises(ValueError, match="^%s: .*%s" % (who, word)):
+            evalstep.check_counts(who, truths, labels, n)
+    truths, labels = evalstep.check_counts(who, iter(every), (0, 1, 2), 3)
+    assert isinstance(truths, list) and isinstance(labels, list) and labels == [0, 1, 2] and all(a is b for a, b in zip(truths, every))
+    for label in (24, -1, 1.5, None, "one", 1 << 40):
+        with pytest.raises(ValueError, match="^%s: label" % who):
+            evalstep.check_label(who, label, C_)
+    assert [evalstep.check_label(who, l, C_) for l in (0, 23, np.int64(5), 7.0)] == [0, 23, 5, 7]
+    good = every[1]
+    for bad, word in ((good[:2], "shape"), (good[:, :, :10], "shape"), (good[:, :6], "shape"), (good[..., None, None], "shape"), (good[0], "shape"),
+                      (good.astype(np.float32), "uint8"), (good.astype(np.int32), "uint8"), (good.tolist(), "uint8"), (None, "uint8")):
+        with pytest.raises(ValueError, match="^%s: truth of video 1.*%s" % (who, word)):
+            evalstep.check_truth(who, bad, F, H, W, 1)
+        with pytest.raises(ValueError, match="^%s: truth.*%s" % (who, word)):
+            evalstep.check_truth(who, bad, F, H, W)
+    for ok in (good, good[..., None], torch.from_numpy(good), torch.from_numpy(good)[..., None]):
+        t = evalstep.check_truth(who, ok, F, H, W, 1)
+        assert torch.is_tensor(t) and t.dtype == torch.uint8 and tuple(t.shape) == (F, H, W) and t.data_ptr() == torch.from_numpy(good).data_ptr()
