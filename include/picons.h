@@ -71,7 +71,7 @@ typedef void* pc_stream;            /* hipStream_t */
  * pc_mask_run_index / pc_mask_runs with PC_RUN_WORDS, pc_map_crosstab / pc_map_crosstab_ws_bytes with PC_CROSS_MAX_SLOTS, and pc_resample_tables / pc_detect_frames_scaled_ws_bytes /
  * pc_detect_frames_scaled, and pc_clip_hop_starts / pc_clip_planes_bytes / pc_clip_planes / pc_detect_frames_planes_ws_bytes /
  * pc_detect_frames_planes with PC_PLANES_MAX_FRAMES, and pc_prob_truth_hist_ws_bytes / pc_prob_truth_hist with PC_SWEEP_MAX_THRESHOLDS, and
- * pc_prob_cut_ws_bytes / pc_prob_cut: came later, move nothing).  Descriptors must be zero-initialised by the caller:
+ * pc_prob_cut_ws_bytes / pc_prob_cut, and pc_paint_boxes with PC_BOX_MAX / PC_BOX_WORDS: came later, move nothing).  Descriptors must be zero-initialised by the caller:
  * fields added later read as "old behaviour" when 0.  pc_version() returns the value the library was built with; the Python host
  * (capi.lib()) refuses a library whose version differs from the header it mirrors. */
 #define PC_VERSION 107
@@ -591,6 +591,26 @@ int     pc_prob_truth_hist(const uint16_t* prob, const uint8_t* truth, int F, in
  * W < 1; H * W >= 2^31; f0 < 0, nf < 1, f0 + nf > F; word outside 1..PC_PROB_ONE; prob not 2-byte, rec not 4-byte, ws not 8-byte aligned. */
 int64_t pc_prob_cut_ws_bytes(int nf, int H, int W);
 int     pc_prob_cut(const uint16_t* prob, int F, int H, int W, int f0, int nf, int word, uint8_t* mask, int32_t* rec, void* ws, pc_stream s);
+/* A video's truth map painted from boxes on the device (csrc/truthboxes.hip; picons_amd/evalstep.py: BoxTruth; EvalEngine.add_video,
+ * DetectEngine.score / sweep).  rects: DEVICE int32 [F][R][PC_BOX_WORDS], a row for every frame of the video, indexed by absolute frame; a
+ * rect is (x0, x1, y0, y1, value) in frame coordinates, half-open.  truth uint8 [F][H][W], contiguous (a frame may start at any byte address,
+ * H * W may be odd; frame offsets are 64-bit).
+ * pc_paint_boxes writes, for each of the frames f0 .. f0 + nf - 1 and no other byte of truth, every byte of the frame exactly once: a pixel's
+ * byte is the low byte of `value` of the LAST rect, in table order, that contains it, 0 if none does; with binary != 0 it is 1 instead of that
+ * value.  That is what painting the rects in order gives (bbox[f, y0:y1, x0:x1] = value: a later annotation overwrites an earlier one).  A
+ * rect paints nothing if x1 <= x0, y1 <= y0 or value & 255 == 0.  Nothing is read from truth: its prior contents are irrelevant and no fill
+ * precedes the launch.
+ * SAFE BY CONSTRUCTION: a rect word never becomes part of an address.  Each thread owns output bytes of a frame inside the checked range and
+ * only tests whether a rect contains them, so a rect that reaches outside the frame -- or any 32-bit pattern at all -- is simply intersected
+ * with the frame; the entry cannot write out of bounds whatever the table holds.
+ * One launch (a map of more frames than the grid limit is cut into several): bpf blocks per frame (a function of H * W alone, at most 64),
+ * the frame's R rects loaded once per block into LDS, each block strides over its share of the frame's four-pixel groups and stores them as
+ * dwords where the address allows.  No atomics, no floating point, nothing waits on another block: bit-identical from run to run.  Refusals
+ * (PC_E_ARG before any HIP call): null rects or truth; F, H, W < 1; H * W >= 2^31; R outside 1..PC_BOX_MAX; f0 < 0, nf < 1, f0 + nf > F; rects
+ * not 4-byte aligned. */
+#define PC_BOX_MAX   32     /* rects per frame */
+#define PC_BOX_WORDS 5      /* x0, x1, y0, y1, value */
+int     pc_paint_boxes(const int32_t* rects, int R, int F, int H, int W, int f0, int nf, int binary, uint8_t* truth, pc_stream s);
 /* Detection on a resized working frame, results at native size (csrc/detectscale.hip; picons_amd/detect.py: DetectEngine.set_working_frame).
  * The views are crops of an Hs x Ws WORKING frame; mask, box, score and probability stand on the H x W NATIVE frame.
  * pc_resample_tables is HOST arithmetic with pc_resize_tables' call shape: it returns the word count 2 * (H + W) and writes `tab` if `cap`

@@ -165,6 +165,7 @@ _SIGS = {
     "pc_prob_truth_hist": (i32, [vp, vp, i32, i32, i32, i32, i32, vp, i32, vp, vp, vp]),
     "pc_prob_cut_ws_bytes": (i64, [i32, i32, i32]),
     "pc_prob_cut": (i32, [vp, i32, i32, i32, i32, i32, i32, vp, vp, vp, vp]),
+    "pc_paint_boxes": (i32, [vp, i32, i32, i32, i32, i32, i32, i32, vp, vp]),
     "pc_resample_tables": (i64, [i32, i32, i32, i32, vp, i64]),
     "pc_detect_frames_scaled_ws_bytes": (i64, [i32, i32, i32, i32, i32]),
     "pc_detect_frames_scaled": (i32, [vp, i32, i32, i32, i32, i32, i32, C.POINTER(C.c_int32), i32, i32, C.POINTER(C.c_int32), i32, i32, i32, vp, vp, vp, vp,

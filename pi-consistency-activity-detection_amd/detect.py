@@ -72,7 +72,7 @@ import numpy as np
 import torch
 
 from . import evalmetrics, ops
-from .evalstep import ClipEngine, _as_u8, centre_crop, check_counts, check_label, check_truth, clip_starts, ring_place
+from .evalstep import BoxTruth, ClipEngine, _as_u8, centre_crop, check_counts, check_label, check_truth, clip_starts, ring_place
 
 PIN_CHUNK_WORDS = 1 << 18          # page-locked staging of the records, 1 MiB at a time
 MAX_VIEWS = ops.MAX_VIEWS          # views of one video (one launch cuts, one merges, all of them)
@@ -752,6 +752,7 @@ class DetectEngine(ClipEngine):
         # score: two page-locked slots the truths go up through (as up_pin), the tables' staging and the kernel's workspace; all made by the first call
         self.tr_pin, self.tr_done, self.tr_slot = [None, None], [None, None], 0
         self.score_pin = self.score_ws = None
+        self.bx_pin, self.bx_done, self.bx_slot = [None, None], [None, None], 0       # box truths: a pair of slots all rect tables of a call go up through, in one copy
         self.keep_probs = False              # set_keep_probs: the probability map of the videos to come without instance scores
         self.sweep_pin = self.sweep_ws = None        # sweep: the histograms' staging and the kernel's workspace, made by the first call
         self._clear()
@@ -1210,8 +1211,12 @@ class DetectEngine(ClipEngine):
         main = torch.cuda.current_stream(self.dev)
         ws = self._grow(who + "_ws", ws_need)
         tab_dev = torch.empty(total, dtype=torch.int32, device=self.dev)
+        tables = self._box_tables([t for _rec, t, _at in jobs if isinstance(t, BoxTruth)], main)
         for rec, t, at in jobs:
-            launch(rec, self._truth_to_device(t, main), tab_dev[at], ws)
+            if isinstance(t, BoxTruth):                              # painted on the device with the rects' values (they carry the actors); the fresh map is written whole
+                launch(rec, ops.paint_boxes(next(tables), *t.shape), tab_dev[at], ws)
+            else:
+                launch(rec, self._truth_to_device(t, main), tab_dev[at], ws)
         pin = self._grow(who + "_pin", total, torch.int32)[:total]
         pin.copy_(tab_dev, non_blocking=True)
         main.synchronize()                                           # the call's one wait on the compute stream
@@ -1264,6 +1269,29 @@ class DetectEngine(ClipEngine):
         main.wait_event(self.tr_done[slot])
         d.record_stream(main)
         return d
+
+    def _box_tables(self, truths, main):
+        """The rect tables of a call's BoxTruths on the device, in order: all of them (F * R * 20 bytes each) through ONE page-locked slot of
+        a pair of their own and ONE copy, in front of the paint launches on `main` -- per video nothing but its pc_paint_boxes launch is
+        left.  The host waits only if the copy that used the slot two calls ago has not left it.  -> an iterator of int32 [F,R,5] tensors."""
+        if not truths:
+            return iter(())
+        slot = self.bx_slot
+        self.bx_slot ^= 1
+        if self.bx_done[slot] is not None and not self.bx_done[slot].query():
+            self.bx_done[slot].synchronize()
+        words = sum(t.rects.size for t in truths)
+        stage = self._grow("bx_pin", words, torch.int32, slot)[:words]
+        host, at, o = stage.numpy(), [], 0
+        for t in truths:
+            host[o:o + t.rects.size] = t.rects.reshape(-1)
+            at.append((o, t.rects.shape))
+            o += t.rects.size
+        dev = torch.empty(words, dtype=torch.int32, device=self.dev)
+        dev.copy_(stage, non_blocking=True)
+        self.bx_done[slot] = torch.cuda.Event()
+        self.bx_done[slot].record(main)
+        return (dev[o:o + int(np.prod(shape))].view(shape) for o, shape in at)
 
     def detect(self, frames_u8):
         """One video on its own: begin(), add_video, results()[0]."""

@@ -9,6 +9,10 @@ plan, the upload pool, batch forming, the class-score ring and the batch itself.
 
 The only host wait per video is for its F per-frame truth counts (pc_truth_frame_flags on the copy stream): they decide on the host which
 clips exist (`clip_starts`), as `np.sum(clips[-1][1]) == 0` does in the reference.  The compute stream is never waited for.
+
+Truth may also come as boxes (BoxTruth: per frame a few rects, as UCF101-24 annotates it).  The host then knows which frames hold truth
+inside the crop before anything is uploaded, so that wait, the flags launch and the truth upload fall away: the rect table goes up behind the
+frames and pc_paint_boxes (csrc/truthboxes.hip) paints the truth part of the video's buffer on the copy stream.
 """
 from types import SimpleNamespace
 
@@ -73,10 +77,125 @@ def _as_u8(a, what):
     return t
 
 
+def _slice_clip(a, b, n):
+    """slice(a, b).indices(n)[:2] on integer arrays, an empty range as (start, start): how numpy clips x[a:b] on an axis of n -- a negative
+    bound counts from the end."""
+    a, b = np.asarray(a, np.int64), np.asarray(b, np.int64)
+    lo = np.where(a < 0, np.maximum(a + n, 0), np.minimum(a, n))
+    hi = np.where(b < 0, np.maximum(b + n, 0), np.minimum(b, n))
+    return lo, np.maximum(hi, lo)
+
+
+def pick_annotation(annotations):
+    """The annotation the eval loader paints (datasets/ucf_dataloader_eval.py:134-140): the first, or with more than one a draw of
+    np.random.randint -- consumed only then, as the loader consumes it.  -> its index."""
+    return int(np.random.randint(0, len(annotations))) if len(annotations) > 1 else 0
+
+
+class BoxTruth:
+    """A video's truth as boxes: shape = (F, H, W) and rects, int32 [F, R, 5] -- per frame R rects (x0, x1, y0, y1, value), half-open, inside
+    the frame, painted in table order, so that a later rect overwrites an earlier one; a rect with x1 == x0, y1 == y0 or value 0 paints
+    nothing (an unused slot is all zeros).  What EvalEngine.add_video and DetectEngine.score / sweep take next to a dense uint8 truth: the
+    table goes to the device and pc_paint_boxes paints the map there.  Host only; `dense` is the definition the device is held to."""
+    MAX_RECTS, WORDS = 32, 5               # ops.BOX_MAX, ops.BOX_WORDS (PC_BOX_MAX, PC_BOX_WORDS of include/picons.h)
+
+    def __init__(self, shape, rects):
+        try:
+            F, H, W = (int(v) for v in shape)
+        except (TypeError, ValueError):
+            raise ValueError("BoxTruth: shape %r is not (F, H, W)" % (shape,)) from None
+        if F < 1 or H < 1 or W < 1:
+            raise ValueError("BoxTruth: shape %r: F, H, W must be at least 1" % ((F, H, W),))
+        r = np.asarray(rects)
+        if r.dtype.kind not in "iu" or r.ndim != 3 or r.shape[0] != F or r.shape[2] != self.WORDS:
+            raise ValueError("BoxTruth: rects must be an integer array [%d, R, %d], got %s %s" % (F, self.WORDS, r.dtype, r.shape))
+        if not 1 <= r.shape[1] <= self.MAX_RECTS:
+            raise ValueError("BoxTruth: R = %d rects per frame outside 1..%d" % (r.shape[1], self.MAX_RECTS))
+        r = r.astype(np.int64)
+        x0, x1, y0, y1, v = (r[..., k] for k in range(5))
+        if ((x0 < 0) | (x0 > x1) | (x1 > W)).any():
+            raise ValueError("BoxTruth: a rect does not keep 0 <= x0 <= x1 <= W = %d" % W)
+        if ((y0 < 0) | (y0 > y1) | (y1 > H)).any():
+            raise ValueError("BoxTruth: a rect does not keep 0 <= y0 <= y1 <= H = %d" % H)
+        if ((v < 0) | (v > 255)).any():
+            raise ValueError("BoxTruth: a rect's value lies outside 0..255")
+        self.shape = (F, H, W)
+        self.rects = np.ascontiguousarray(r, dtype=np.int32)
+
+    @classmethod
+    def from_xywh(cls, boxes, H, W, values=None):
+        """boxes: an int array [F, R, 4] of (x, y, w, h) as annotations hold them, clipped exactly as numpy clips bbox[f, y:y+h, x:x+w] -- a
+        negative x or y counts from the far edge, a box that is empty after that paints nothing.  values: None (every slot 1) or R values,
+        slot r's."""
+        b = np.asarray(boxes)
+        if b.dtype.kind not in "iu" or b.ndim != 3 or b.shape[2] != 4:
+            raise ValueError("BoxTruth.from_xywh: boxes must be an integer array [F, R, 4], got %s %s" % (b.dtype, b.shape))
+        F, R = b.shape[:2]
+        vals = np.ones(R, np.int64) if values is None else np.asarray(values)
+        if vals.shape != (R,) or vals.dtype.kind not in "iu":
+            raise ValueError("BoxTruth.from_xywh: values must be %d integers, one per slot" % R)
+        b = b.astype(np.int64)
+        x0, x1 = _slice_clip(b[..., 0], b[..., 0] + b[..., 2], int(W))
+        y0, y1 = _slice_clip(b[..., 1], b[..., 1] + b[..., 3], int(H))
+        return cls((F, H, W), np.stack([x0, x1, y0, y1, np.broadcast_to(vals.astype(np.int64), (F, R))], axis=2))
+
+    @classmethod
+    def from_annotations(cls, anns, F, H, W, values=None):
+        """Annotations (start, end, label, boxes, ...), annotation i in slot i with value i + 1 (values: others), frames start ..
+        min(F, end + 1) - 1 each, boxes[f - start] = (x, y, w, h): what painting them in order with their values gives -- the actors of
+        DetectEngine.score(actors=A)."""
+        anns = list(anns)
+        boxes = np.zeros((int(F), max(len(anns), 1), 4), np.int64)
+        for i, ann in enumerate(anns):
+            start, end = int(ann[0]), int(ann[1])
+            if start < 0:
+                raise ValueError("BoxTruth: annotation %d starts at frame %d" % (i, start))
+            for f in range(start, min(int(F), end + 1)):
+                boxes[f, i] = ann[3][f - start]
+        return cls.from_xywh(boxes, H, W, np.arange(1, boxes.shape[1] + 1) if values is None else values)
+
+    @classmethod
+    def from_annotation(cls, ann, F, H, W, value=1):
+        """One annotation as the eval loader's load_video paints it (datasets/ucf_dataloader_eval.py:142-147), with `value`."""
+        return cls.from_annotations([ann], F, H, W, [value])
+
+    @property
+    def nbytes(self):
+        """The bytes of the table: what travels instead of F * H * W."""
+        return int(self.rects.nbytes)
+
+    def dense(self, binary=False):
+        """numpy uint8 [F, H, W]: the rects painted in table order on the host (binary: 1 for every value that paints)."""
+        F, H, W = self.shape
+        out = np.zeros(self.shape, np.uint8)
+        for f in range(F):
+            for x0, x1, y0, y1, v in self.rects[f]:
+                if v & 255:
+                    out[f, y0:y1, x0:x1] = 1 if binary else v
+        return out
+
+    def flags(self, h0, w0, S):
+        """int32 [F]: 1 where a rect of the frame that paints meets the S x S crop at (h0, w0), else 0 -- non-zero exactly where
+        pc_truth_frame_flags of dense() is: the last rect over a pixel that a painting rect covers is itself one that paints."""
+        x0, x1, y0, y1, v = (self.rects[..., k] for k in range(5))
+        hit = (v != 0) & (np.maximum(x0, w0) < np.minimum(x1, w0 + S)) & (np.maximum(y0, h0) < np.minimum(y1, h0 + S))
+        return hit.any(axis=1).astype(np.int32)
+
+
 # What a caller hands in next to a video -- EvalEngine.add_video, DetectEngine.score / sweep (who) -- checked on the host: no GPU use.
 def check_truth(who, truth, F, H, W, video=None):
-    """A truth mask (of video `video` of a pass): uint8, of shape (F, H, W) or (F, H, W, 1) -> torch uint8 [F, H, W] (no copy), or ValueError."""
+    """A truth mask (of video `video` of a pass): uint8, of shape (F, H, W) or (F, H, W, 1) -> torch uint8 [F, H, W] (no copy), or a BoxTruth
+    of shape (F, H, W) -> itself; or ValueError."""
     name = "%s: truth" % who if video is None else "%s: truth of video %d" % (who, video)
+    if isinstance(truth, BoxTruth):
+        if truth.shape != (F, H, W):
+            raise ValueError("%s has shape %s, expected (%d, %d, %d) or (%d, %d, %d, 1)" % (name, tuple(truth.shape), F, H, W, F, H, W))
+        r = truth.rects                      # a table changed behind the constructor's back: what sizes the upload and the launch is looked at again
+        if not (isinstance(r, np.ndarray) and r.dtype == np.int32 and r.ndim == 3 and r.shape[0] == F and r.shape[2] == BoxTruth.WORDS
+                and 1 <= r.shape[1] <= BoxTruth.MAX_RECTS and r.flags.c_contiguous):
+            raise ValueError("%s: rects must be a contiguous int32 array [%d, R, %d] with R in 1..%d, got %s %s"
+                             % (name, F, BoxTruth.WORDS, BoxTruth.MAX_RECTS, getattr(r, "dtype", type(r)), getattr(r, "shape", None)))
+        return truth
     t = _as_u8(truth, name)
     if t.dim() == 4 and t.shape[3] == 1:
         t = t.reshape(t.shape[:3])
@@ -311,6 +430,9 @@ class EvalEngine(ClipEngine):
         self.tables = torch.zeros(2 * C_ * T + 2 * C_ + 1, dtype=torch.int32, device=self.dev)
         self.acc = self._accumulator(self.tables)
         self.pin_flags = self.dev_flags = None
+        # a BoxTruth video has no host wait of its own, so the one staging buffer above would be filled again while the upload in front still
+        # reads it: two page-locked slots with their upload events, as DetectEngine.add_video has them
+        self.up_pin, self.up_done, self.up_slot = [None, None], [None, None], 0
 
     def _accumulator(self, flat):
         C_, T = self.C, evalmetrics.N_THR
@@ -354,6 +476,8 @@ class EvalEngine(ClipEngine):
         page-locked memory on the copy stream; its kept clips join the batches.  -> the number of clips (0: "Video has no bounding boxes",
         evaluate_ucf101.py:99-101, the video is skipped)."""
         v, t, lab = self.check_video(frames_u8, truth_u8, label)
+        if isinstance(t, BoxTruth):
+            return self._add_video_boxes(v, t, lab)
         F, H, W = (int(s) for s in v.shape[:3])
         h0, w0 = centre_crop(H, W, self.hw)
         if self.dev_flags is None or self.dev_flags.numel() < F:
@@ -378,6 +502,57 @@ class EvalEngine(ClipEngine):
         except ValueError:
             self._release(rec)
             raise
+        self._join(rec, row0, pos)
+        return rec.rows
+
+    def _add_video_boxes(self, v, bt, lab):
+        """add_video with the truth as a BoxTruth.  Which frames hold truth inside the crop is known on the host (BoxTruth.flags), so the
+        clips are decided before anything is enqueued: a video without one costs nothing, and for the others the frames go up alone, the
+        rect table behind them through the same page-locked slot, and pc_paint_boxes writes the truth part of the pool entry on the copy
+        stream in front of rec.ready -- binary, whatever the values: pc_seg_frame_counts needs the truth value 1.  No flags launch and no
+        wait per video: the host waits at most for its own upload of two videos ago, if that has not left its slot yet."""
+        F, H, W = bt.shape
+        h0, w0 = centre_crop(H, W, self.hw)
+        starts = clip_starts(F, bt.flags(h0, w0, self.hw), self.f_skip)
+        if not starts:
+            self.n_skipped += 1
+            return 0
+        row0, pos = ring_place(self.pos, len(starts), self.capacity, self.bs)
+        slot = self.up_slot
+        self.up_slot ^= 1
+        if self.up_done[slot] is not None and not self.up_done[slot].query():
+            self.up_done[slot].synchronize()                          # an upload on the copy stream, two videos back: never the compute stream
+        host = not v.is_cuda
+        nv, nt, nr = v.numel(), F * H * W, bt.nbytes
+        o_t = (nv + 255) // 256 * 256 if host else 0                  # where the truth starts in the pool entry, and the table in the slot
+        pin = self.up_pin[slot]
+        if pin is None or pin.numel() < o_t + nr:
+            pin = self.up_pin[slot] = torch.empty(o_t + nr, dtype=torch.uint8).pin_memory()
+        if host:
+            pin[:nv].view(v.shape).copy_(v)
+        table = pin[o_t:o_t + nr].view(torch.int32).view(bt.rects.shape)
+        table.copy_(torch.from_numpy(bt.rects))
+        main = torch.cuda.current_stream(self.dev)
+        if host:
+            entry = self._acquire(o_t + nt)                           # sized for frames + truth, as with a dense truth; the truth part is painted
+        else:
+            entry, dv = None, v.to(self.dev).contiguous()
+            self.copy_stream.wait_stream(main)                        # whatever produced the frames
+        rec = SimpleNamespace(entry=entry, F=F, H=H, W=W, h0=h0, w0=w0, label=lab, ready=torch.cuda.Event(), waited=False, starts=starts,
+                              rows=len(starts), done=0)
+        with torch.cuda.stream(self.copy_stream):
+            if host:
+                entry["buf"][:nv].copy_(pin[:nv], non_blocking=True)
+                dv, dt = entry["buf"][:nv].view(v.shape), entry["buf"][o_t:o_t + nt].view(F, H, W)
+            else:
+                dt = torch.empty(F, H, W, dtype=torch.uint8, device=self.dev)
+                dt.record_stream(main)                                # made on the copy stream, read and let go on the compute stream
+            rects = torch.empty(bt.rects.shape, dtype=torch.int32, device=self.dev)
+            rects.copy_(table, non_blocking=True)
+            ops.paint_boxes(rects, F, H, W, binary=True, truth=dt)
+            rec.ready.record(self.copy_stream)
+        self.up_done[slot] = rec.ready
+        rec.video, rec.truth = dv, dt
         self._join(rec, row0, pos)
         return rec.rows
 

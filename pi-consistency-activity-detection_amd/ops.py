@@ -1178,6 +1178,31 @@ def prob_cut(prob, word, f0=0, nf=None, mask=None, rec=None, ws=None, want_mask=
     return mask, rec
 
 
+BOX_MAX = 32                               # PC_BOX_MAX of include/picons.h: the rects of one frame
+BOX_WORDS = 5                              # PC_BOX_WORDS: a rect is (x0, x1, y0, y1, value), half-open, frame coordinates
+
+
+def paint_boxes(rects, F, H, W, f0=0, nf=None, binary=False, truth=None):
+    """pc_paint_boxes: rects a contiguous int32 device tensor [F,R,5], a row of R rects (x0, x1, y0, y1, value) for every frame of the video ->
+    truth uint8 [F,H,W]: in the frames f0 .. f0 + nf - 1 (default: all from f0 on) a pixel holds the low byte of the value of the last rect of
+    its frame's row that contains it, 0 if none does -- binary=True: 1 instead of the value.  A rect is intersected with the frame; one with
+    x1 <= x0, y1 <= y0 or a zero low byte paints nothing.  A given truth is written in place, in those frames only; a fresh one is as the
+    allocator left it where the launch writes all of it (f0 = 0, nf = F) and zero-filled first otherwise."""
+    F, H, W = int(F), int(H), int(W)
+    if F < 1 or H < 1 or W < 1 or H * W >= 1 << 31:
+        raise ValueError("paint_boxes: F = %d frames of %d x %d: F, H, W >= 1, H * W < 2^31" % (F, H, W))
+    _operand("paint_boxes", "rects", rects, torch.int32, dim=3, what="[F,R,5]")
+    if not rects.is_cuda:
+        raise RuntimeError("picons ops need CUDA/HIP tensors (no CPU fallback)")
+    if int(rects.shape[0]) != F or int(rects.shape[2]) != BOX_WORDS:
+        raise ValueError("paint_boxes: rects of shape %s, expected (%d, R, %d)" % (tuple(rects.shape), F, BOX_WORDS))
+    R = _bound("paint_boxes", "R", rects.shape[1], BOX_MAX)
+    f0, nf = _frame_range("paint_boxes", F, f0, nf)
+    truth = _buffer("paint_boxes", "truth", truth, (F, H, W), torch.uint8, rects.device, fill=not (f0 == 0 and nf == F))
+    capi.call("pc_paint_boxes", ptr(rects), R, F, H, W, f0, nf, int(bool(binary)), ptr(truth), stream())
+    return truth
+
+
 def video_class(scores, out=None):
     """pc_video_class: scores contiguous float32 device [n,C] -> float32 device [C + 2]: mean class scores, arg-max (as a float), its mean."""
     n, C_ = (int(v) for v in _operand("video_class", "scores", scores, torch.float32, dim=2, what="[n,C]").shape)

@@ -206,6 +206,34 @@ def make_eval_videos_u8(n, seed=1234, num_classes=24, hw=224, frames_hw=None):
     return out
 
 
+def make_eval_videos_boxes(n, seed=1234, num_classes=24, hw=224, frames_hw=None):
+    """make_eval_videos_u8's videos -- the same draws in the same order -- with the truth as an evalstep.BoxTruth of two rects per frame instead of
+    the dense array: the moving box in slot 0 (video 1: its corner block, one box), the single centre pixel of the first truth frame as a 1 x 1 box in
+    slot 1.  BoxTruth.dense(binary=True) of video i equals make_eval_videos_u8(...)[i]'s truth."""
+    from .evalstep import BoxTruth
+    rng = np.random.default_rng(seed)
+    H, W = frames_hw if frames_hw is not None else (hw + 16, hw + 32)
+    h0, w0 = int((H - hw) / 2), int((W - hw) / 2)
+    if H <= hw or W <= hw or min(h0, w0) < 2:
+        raise ValueError("make_eval_videos_boxes: frames of %d x %d leave no margin of 2 around the %d crop" % (H, W, hw))
+    out = []
+    for vi in range(n):
+        F = int(rng.integers(8, 41))
+        boxes = np.zeros((F, 2, 4), np.int64)                  # (x, y, w, h)
+        f0 = int(rng.integers(0, max(1, F - 6))); f1 = int(rng.integers(f0 + 3, F + 1))
+        h, w = int(rng.integers(hw // 6, hw // 2)), int(rng.integers(hw // 6, hw // 2))
+        y, x = int(rng.integers(0, H - h)), int(rng.integers(0, W - w))
+        frames = rng.integers(0, 256, (F, H, W, 3), dtype=np.uint8)
+        if vi == 1:
+            boxes[f0:f1, 0] = (0, 0, w0, h0)                   # the corner the crop leaves out
+        else:
+            for f in range(f0, f1):
+                boxes[f, 0] = (min(W - w, x + 2 * (f - f0)), min(H - h, y + (f - f0)), w, h)
+            boxes[f0, 1] = (w0 + hw // 2, h0 + hw // 2, 1, 1)  # whatever the draw: truth inside the crop
+        out.append((frames, BoxTruth.from_xywh(boxes, H, W), vi % num_classes))
+    return out
+
+
 def make_decoded_video(seed, labeled=True, num_classes=24, frames_hw=(240, 320)):
     """One synthetic decoded training video in the form datasets/ucf_dataloader.py `load_video` consumes after `vread`:
     (uint8 frames [F,H,W,3], annotations [(start, end, label, [[x,y,w,h] per frame], [annotated frame ids], labeled_vid)])."""

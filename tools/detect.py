@@ -28,6 +28,10 @@ v-mAP at 0.2 and 0.5 and the accuracy are printed, and score_table_i int32 [F, 3
 (inter, union, gt), score_label_i and the arrays of the result (score_fmAP [20], score_vmAP [20], score_frame_ious, score_video_ious,
 score_n_tot_frames, score_n_vids, score_n_correct, score_accuracy) are stored.  The truth is taken on the full frame, not inside the centre
 crop as evalstep.EvalEngine takes it.  With --synthetic the truth and label of synthetic.make_eval_videos_u8 are used (--score).
+--truth_boxes b0.npy ... instead of --truth: one int [F,R,4] file of (x, y, w, h) boxes per video, clipped as numpy clips a slice
+(evalstep.BoxTruth.from_xywh); the rect table goes to the device and pc_paint_boxes paints the map there, so F * R * 20 bytes travel instead of
+F * H * W.  --actors A: slot r of a frame's boxes is actor r + 1 and the pass is scored with A actors.  --score --boxes: the synthetic truth
+as boxes (synthetic.make_eval_videos_boxes).  --sweep and --recut take them as they take dense truths.
 --frame_size Hs Ws [--interp area|linear|nearest]: every video is resized on the device to an Hs x Ws working frame (cv2.resize's arithmetic;
 the JHMDB loader's is 256 256 area), cut and run there, and detected at its NATIVE size (DetectEngine.set_working_frame: the merged logits
 resampled bilinearly to every native pixel in front of the threshold).  Everything stored stays in native coordinates but views_i, which are
@@ -51,7 +55,7 @@ mask_threshold and mask_word record the threshold and its word.
 
     python tools/detect.py --out detections.npz [--ckpt best_model.pth] [--synthetic 4 | video.npy ...] [--masks] [--pack] [--tile] [--flip]
                            [--max-gap 0] [--min-pixels 1] [--instances K] [--min_area 1] [--conn 8] [--instance_maps] [--instance_scores]
-                           [--instance_links L] [--link box|mask] [--mask_runs] [--truth t0.npy ... --labels l0 ... | --score]
+                           [--instance_links L] [--link box|mask] [--mask_runs] [--truth t0.npy ... --labels l0 ... | --truth_boxes b0.npy ... --labels l0 ... [--actors A] | --score [--boxes]]
                            [--frame_size Hs Ws [--interp area|linear|nearest]] [--hop N] [--sweep [t ...] [--recut]] [--threshold t]
 """
 import argparse
@@ -63,7 +67,7 @@ import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import picons_amd  # noqa: F401,E402
-from picons_amd import detect, synthetic, trainstate  # noqa: E402
+from picons_amd import detect, evalstep, synthetic, trainstate  # noqa: E402
 
 
 def main():
@@ -92,6 +96,9 @@ def main():
     ap.add_argument("--truth", nargs="+", default=None, help="one .npy of uint8 truth [F,H,W] or [F,H,W,1] per video: score the pass against them")
     ap.add_argument("--labels", nargs="+", type=int, default=None, help="with --truth: one class id per video")
     ap.add_argument("--score", action="store_true", help="with synthetic videos: score the pass against their own truth and labels")
+    ap.add_argument("--truth_boxes", nargs="+", default=None, help="instead of --truth: one .npy of int boxes [F,R,4] = (x, y, w, h) per video (evalstep.BoxTruth: the table goes up, the map is painted on the device)")
+    ap.add_argument("--boxes", action="store_true", help="with --score: the synthetic truth as boxes (synthetic.make_eval_videos_boxes)")
+    ap.add_argument("--actors", type=int, default=None, metavar="A", help="with --truth_boxes: slot r of a frame's boxes is actor r + 1, and the pass is scored with A actors")
     ap.add_argument("--frame_size", nargs=2, type=int, default=None, metavar=("Hs", "Ws"), help="resize every video to this working frame on the device; results stay at native size")
     ap.add_argument("--interp", default="area", choices=sorted(detect.INTERPOLATIONS), help="with --frame_size: cv2.resize's interpolation")
     ap.add_argument("--hop", type=int, default=None, help="cut overlapping clips that start every N frames and average the clips that hold a frame (a multiple of 2 in 2..16; 16: today's cut)")
@@ -99,13 +106,22 @@ def main():
     ap.add_argument("--threshold", type=float, default=None, metavar="t", help="cut the masks at probability >= t in (0, 1] instead of at sigmoid(x) >= 0.5 (DetectEngine.set_mask_threshold)")
     ap.add_argument("--recut", action="store_true", help="with --sweep: cut the finished pass again on the device at the best threshold of the sweep before anything is stored (DetectEngine.recut)")
     a = ap.parse_args()
-    if (a.truth is None) != (a.labels is None) or (a.truth is not None and not (len(a.truth) == len(a.labels) == len(a.videos))):
+    if (a.truth is None and a.truth_boxes is None) != (a.labels is None) or (a.truth is not None and not (len(a.truth) == len(a.labels) == len(a.videos))):
         raise SystemExit("tools/detect.py: --truth and --labels go together, one of each per video file")
+    if a.truth_boxes is not None:
+        if a.truth is not None:
+            raise SystemExit("tools/detect.py: --truth and --truth_boxes exclude each other")
+        if a.labels is None or not (len(a.truth_boxes) == len(a.labels) == len(a.videos)):
+            raise SystemExit("tools/detect.py: --truth_boxes and --labels go together, one of each per video file")
+    if a.actors is not None and (a.truth_boxes is None or not 1 <= a.actors <= 32):
+        raise SystemExit("tools/detect.py: --actors A (1..32) numbers the slots of --truth_boxes")
+    if a.boxes and not a.score:
+        raise SystemExit("tools/detect.py: --boxes is the truth of --score as boxes")
     if a.score and a.videos:
         raise SystemExit("tools/detect.py: --score is for the synthetic videos; give --truth and --labels for video files")
     if a.sweep is not None:
-        if a.truth is None and not a.score:
-            raise SystemExit("tools/detect.py: --sweep scores against truth: give --truth and --labels, or --score with synthetic videos")
+        if a.truth is None and a.truth_boxes is None and not a.score:
+            raise SystemExit("tools/detect.py: --sweep scores against truth: give --truth (or --truth_boxes) and --labels, or --score with synthetic videos")
         try:
             detect.threshold_words(a.sweep or None)
         except ValueError as e:
@@ -141,9 +157,17 @@ def main():
     if names:
         videos = [np.load(n) for n in names]
         truths, labels = ([np.load(t) for t in a.truth], list(a.labels)) if a.truth else (None, None)
+        if a.truth_boxes:
+            try:
+                truths, labels = [], list(a.labels)
+                for v, t in zip(videos, a.truth_boxes):
+                    b = np.load(t)
+                    truths.append(evalstep.BoxTruth.from_xywh(b, v.shape[1], v.shape[2], None if a.actors is None else np.arange(1, b.shape[1] + 1)))
+            except (ValueError, IndexError) as e:
+                raise SystemExit("tools/detect.py: --truth_boxes %s: %s" % (t, e))
     else:
         n = a.synthetic or 4
-        made = synthetic.make_eval_videos_u8(n, num_classes=a.classes, hw=a.hw)
+        made = (synthetic.make_eval_videos_boxes if a.boxes else synthetic.make_eval_videos_u8)(n, num_classes=a.classes, hw=a.hw)
         videos = [v[0] for v in made]
         truths, labels = ([v[1] for v in made], [v[2] for v in made]) if a.score else (None, None)
         names = ["synthetic_%d" % i for i in range(n)]
@@ -199,7 +223,7 @@ def main():
             for i, r in enumerate(engine.mask_runs(which)):
                 out.update({"%s_runs_%d" % (key, i): r.runs, "%s_run_offsets_%d" % (key, i): r.offsets, "%s_shape_%d" % (key, i): np.array(r.shape, np.int64)})
     if truths is not None:
-        ps = engine.score(truths, labels)
+        ps = engine.score(truths, labels, actors=a.actors or 1)
         r = ps.result
         with np.errstate(invalid="ignore", divide="ignore"):          # printed: the mean over the classes that hold a video (the stored fmAP / vmAP are
             fm = np.nanmean(r["frame_ious"] / r["n_tot_frames"], axis=0)  # the evaluator's, NaN as soon as one class holds none)
